@@ -14,13 +14,20 @@ are gathered into rank 0's frame buffer with one RCCL gather per frame.  The fra
 scaling, BASELINE config 3).  Rank 0 prints ONE JSON line.
 
 Workload (BASELINE.json configs[1]): grid_mesh(G=708, seed=1) = 1,002,528 triangles, camera A
-("top-down", 100 % coverage), kDepth, 1 spp.  The build time and the CPU baseline are reported as extra fields of
-the same line; --other-camera adds camera B ("oblique").
+("top-down", 100 % coverage), kDepth, 1 spp.  With --full the build time and the CPU baseline are reported as extra
+fields of the same line; --other-camera adds camera B ("oblique").
 
 What `value` is: K frames / wall time of the timed region with `--inflight` (default 8) frames in flight on separate HIP
-streams (the stream argument of rt_trace; the frames of a camera path are independent).  The one-frame-at-a-time rate
-(`serial_mrays`: median of >= 20 single launches timed with events) is on the same line, and
-`--inflight 1` makes it the headline.
+streams (the stream argument of rt_trace; the frames of a camera path are independent).  `--inflight 1` makes the
+one-frame-at-a-time rate the headline.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` and the workload).  `--full`
+adds everything else on the same line: the one-frame-at-a-time rate (`serial_mrays`: median of >= 20 single launches
+timed with events), the test counts per ray, the roofline, the build / sort / SAH-build / graph / stream-copy
+timings, the N > 1 diagnostics and the CPU baseline with its parity check against the timed frame.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's frame as float32 RGBA, its test counters as
+float64) to DIR/*.npy; the inputs are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -45,7 +52,7 @@ GATHER_CEILING_GBS = 256 * 16 / 0.69 * 2.4
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; 10 with --preset config5)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--grid", type=int, default=708, help="G of grid_mesh (708 -> 1,002,528 triangles)")
     ap.add_argument("--width", type=int, default=1920)
@@ -72,12 +79,18 @@ def parse():
     ap.add_argument("--preset", choices=["config2", "config4", "config5"], default=None,
                     help="BASELINE.json configs: config2 = 1M tris 1080p (default); config4 = 10M-triangle scene "
                          "(full LBVH rebuild, builder-bound); config5 = 1M tris, 3840x2160, 16 spp (traversal-bound)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: serial rate, test counts, roofline, build "
+                         "timings, N > 1 diagnostics, CPU baseline + parity (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's frame, its test counters) as DIR/<name>.npy")
     a = ap.parse_args()
     if a.preset == "config4":
         a.grid = 2237
     elif a.preset == "config5":
         a.width, a.height, a.spp = 3840, 2160, 16
-        a.steps = min(a.steps, 10)
+    if a.steps is None:
+        a.steps = 10 if a.preset == "config5" else 50
     return a
 
 
@@ -195,7 +208,8 @@ def main():
     build()
     torch.cuda.synchronize()
     build_ms = None
-    if not args.no_extras:
+    extras_on = args.full and not args.no_extras
+    if extras_on:
         times = []
         for _ in range(args.build_reps):
             e0, e1 = ev(), ev()
@@ -219,7 +233,7 @@ def main():
     # ---- the build's radix sort on its own (the stage entry points of the C ABI): the scene's Morton codes, sorted on 30
     # bits exactly as the builder does; HIP events around the sort alone, input restored (untimed) before every run
     sort_us = None
-    if not args.no_extras and args.type == "bottom-up" and world == 1 and n > 0:
+    if extras_on and args.type == "bottom-up" and world == 1 and n > 0:
         import numpy as np  # noqa: PLC0415
         d_aabb = torch.zeros(8, dtype=torch.int32, device="cuda")
         k0 = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -348,13 +362,14 @@ def main():
         for _ in range(warmup):
             step(cam_key)
         drain()
-        evs = [(ev(), ev()) for _ in range(steps)]
+        # per-launch events only for --full (roofline.inflight_mean_launch_ms); a plain run times the steps alone
+        evs = [(ev(), ev()) for _ in range(steps)] if args.full else None
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(steps):
-            step(cam_key, events=evs[i])
+            step(cam_key, events=evs[i] if evs else None)
         drain()                              # every gather (and de-interleave) of the K timed frames has completed
         if world > 1:
             dist.barrier()
@@ -364,7 +379,7 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device=ctl_dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        kern_ms = statistics.mean(a.elapsed_time(b) for a, b in evs)
+        kern_ms = statistics.mean(a.elapsed_time(b) for a, b in evs) if evs else None
         return dt, kern_ms
 
     def test_counts(cam_key):
@@ -379,52 +394,57 @@ def main():
             dist.all_reduce(c)
         return [int(v) for v in c.tolist()]
 
-    box, tri, wsteps_box, wsteps_leaf = test_counts(cam)   # whole-frame sums (all ranks)
+    if args.full:
+        box, tri, wsteps_box, wsteps_leaf = test_counts(cam)   # whole-frame sums (all ranks)
     dt, kern_ms = timed(cam, args.steps, args.warmup)
     rays = W * H * args.spp
     value = rays * args.steps / dt / 1e6
-    gpu_frame = frames[(step_no[0] - 1) % S].cpu().numpy().reshape(H, W, 4) if rank == 0 else None   # last timed frame
+    last = (step_no[0] - 1) % S
+    gpu_frame = frames[last].cpu().numpy().reshape(H, W, 4) if rank == 0 else None   # last timed frame
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, gpu_frame, frame_counters[last].cpu().numpy())
 
-    # ---- this rank's part alone on the GPU, one launch at a time (events around the trace kernel,
-    # median of >= 20): the duration the kernel's own quality is judged by.  Issued as the OTHER colour conversion of the
-    # same traversal (kBoxtests <-> kDepth: same rays, same tests, a different one-line colour conversion) so that a
-    # profiler's per-kernel average keeps the in-flight launches of the timed region and these serial ones apart.
-    counters.zero_()
-    if strips:
-        trace_strips(compact[0], cam, args.render_type, counters)
-    else:
-        trace_band(frame, cam, args.render_type, counters)
-    torch.cuda.synchronize()
-    lbox, ltri = int(counters[0].item()), int(counters[1].item())
-    my_rows = (min(H, len(sharding.my_strips(H, world, rank)) * sharding.STRIP_ROWS) if strips else (y1 - y0))
-    alg_bytes = 32 * lbox + 64 * ltri + 4 * W * my_rows
-    iso_rt = 1 if args.render_type == 0 else 0
-    iso = []
-    for _ in range(24):
-        e0, e1 = ev(), ev()
+    if args.full:
+        # ---- this rank's part alone on the GPU, one launch at a time (events around the trace kernel,
+        # median of >= 20): the duration the kernel's own quality is judged by.  Issued as the OTHER colour conversion of
+        # the same traversal (kBoxtests <-> kDepth: same rays, same tests, a different one-line colour conversion) so that
+        # a profiler's per-kernel average keeps the in-flight launches of the timed region and these serial ones apart.
         counters.zero_()
-        e0.record()
         if strips:
-            trace_strips(compact[0], cam, iso_rt, counters)
+            trace_strips(compact[0], cam, args.render_type, counters)
         else:
-            trace_band(scratch_frame, cam, iso_rt, counters)
-        e1.record()
-        e1.synchronize()
-        iso.append(e0.elapsed_time(e1))
-    serial_ms = statistics.median(iso[2:])
-    serial_l1 = alg_bytes / (serial_ms * 1e-3) / 1e9       # GB/s of node + leaf bytes delivered to the lanes
-    if world > 1:                                          # the slowest rank's part bounds a serial multi-GPU frame
-        t = torch.tensor([serial_ms], dtype=torch.float64, device=ctl_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        serial_ms_max = float(t.item())
-    else:
-        serial_ms_max = serial_ms
+            trace_band(frame, cam, args.render_type, counters)
+        torch.cuda.synchronize()
+        lbox, ltri = int(counters[0].item()), int(counters[1].item())
+        my_rows = (min(H, len(sharding.my_strips(H, world, rank)) * sharding.STRIP_ROWS) if strips else (y1 - y0))
+        alg_bytes = 32 * lbox + 64 * ltri + 4 * W * my_rows
+        iso_rt = 1 if args.render_type == 0 else 0
+        iso = []
+        for _ in range(24):
+            e0, e1 = ev(), ev()
+            counters.zero_()
+            e0.record()
+            if strips:
+                trace_strips(compact[0], cam, iso_rt, counters)
+            else:
+                trace_band(scratch_frame, cam, iso_rt, counters)
+            e1.record()
+            e1.synchronize()
+            iso.append(e0.elapsed_time(e1))
+        serial_ms = statistics.median(iso[2:])
+        serial_l1 = alg_bytes / (serial_ms * 1e-3) / 1e9       # GB/s of node + leaf bytes delivered to the lanes
+        if world > 1:                                          # the slowest rank's part bounds a serial multi-GPU frame
+            t = torch.tensor([serial_ms], dtype=torch.float64, device=ctl_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            serial_ms_max = float(t.item())
+        else:
+            serial_ms_max = serial_ms
 
     # ---- N > 1 diagnostics (outside the timed region): one frame at a time -- this rank's launch, then the gather alone
     # (events on the launch stream; the gather's time is rank 0's view of the whole collective).  They tell a reader of a
     # scaling record where a step's time goes: the slowest rank's part, or the collection on rank 0.
     diag = None
-    if world > 1:
+    if args.full and world > 1:
         tr, ga = [], []
         for _ in range(6):
             dist.barrier()
@@ -457,14 +477,14 @@ def main():
                       "as seen from that rank; the timed region overlaps these across frames"}
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         extras = {
             "build_ms": round(build_ms, 4),
             "build_gbps_algorithmic": round(512.0 * n / (build_ms * 1e-3) / 1e9, 1),  # 512 B/triangle, SURVEY 8(d)
             "build_frac_of_hbm_peak": round(512.0 * n / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             "build": build_record(n, build_ms, sort_us, args.type, G, build_b2b_ms),
         }
-    if not args.no_extras and args.type == "bottom-up" and world == 1:
+    if extras_on and args.type == "bottom-up" and world == 1:
         # the SAH builder (the reference's default --type) on the same triangles: build time only here, so that every
         # trace_kernel launch of the default command stays the headline workload; `--type sah` traces through it
         sinp = rt.BuildInput.allocate(tris, sah=True)
@@ -480,7 +500,7 @@ def main():
             ts.append(e0.elapsed_time(e1))
         extras["sah_build_ms"] = round(statistics.median(ts), 4)
         del sinp
-    if not args.no_extras and args.type == "bottom-up" and world == 1:
+    if extras_on and args.type == "bottom-up" and world == 1:
         # (1) rebuild + trace per frame as one HIP graph (nothing in that path synchronises or allocates);
         # (2) an on-box stream ceiling (device-to-device copy, read + write bytes) beside the 8 TB/s spec figure
         try:
@@ -525,8 +545,8 @@ def main():
         extras[f"camera_{other}_mrays"] = round(rays * max(args.steps // 2, 5) / odt / 1e6, 2)
         extras[f"camera_{other}_box_tests_per_ray"] = round(obox / rays, 2)
 
-    rc = 0
-    if rank == 0:
+    roof = None
+    if rank == 0 and args.full:
         # HBM bytes per launch from the PMC counters (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md "HBM"): a counter
         # pass cannot run inside this process, so the figure is the committed result of `tools/collect.sh run <round> pmc` on this same
         # command; it is attached only to the exact workload it was collected on and labelled with its source.
@@ -581,6 +601,8 @@ def main():
             "inflight_mean_launch_ms": round(kern_ms, 4),
             "inflight_mean_launch_ms_is": f"mean start-to-end time of the timed region's launches, {S} of which overlap",
         }
+    rc = 0
+    if rank == 0:
         out = {
             "metric": "Mrays/s at 1920x1080 primary rays + BVH build ms, 1M-tri scene",
             "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -589,13 +611,10 @@ def main():
             "value_is": f"K frames / wall time with {S} frame(s) in flight on {S} HIP stream(s)"
                         + ("" if S > 1 else " (= one frame at a time)"),
             "inflight": S,
-            "serial_mrays": round(rays / (serial_ms_max * 1e-3) / 1e6, 2),
-            "serial_ms_per_frame": round(serial_ms_max, 4),
             "counters_in_timed_region": True,
             "counters_is": "every timed and every serial launch resets and passes the num_tests buffer, as the reference's Trace() does "
                            "(main.cu:153-157, Tracer.cu:503)",
-            "serial_is": "one launch at a time (the reference's frame loop): median of 22 event-timed launches"
-                         + ("; slowest rank's part, gather not included" if world > 1 else ""),
+            "full": args.full,
             "config": {"workload": f"grid_mesh(G={G}, seed=1) = {n} triangles, {W}x{H}, {args.spp} spp, camera "
                                    f"{cam.upper()} ({'top-down' if cam == 'a' else 'oblique'}), render_type {args.render_type}; "
                                    + ({"bottom-up": "LBVH", "bottom-up-pairs": "LBVH with triangle pairs", "hybrid": "LBVH + SAH top tree (hybrid)", "sah": "SAH tree",
@@ -610,13 +629,20 @@ def main():
                       "note": (None if backend == "nccl" or world == 1 else
                                f"REHEARSAL: {world} ranks share {ndev} GPU(s), collectives over gloo with host staging -- "
                                "exercises the N > 1 control flow, not a scaling measurement")},
-            "box_tests_per_ray": round(box / rays, 2), "tri_tests_per_ray": round(tri / rays, 3),
-            "wave_steps": {"box_phase": wsteps_box, "leaf_phase": wsteps_leaf,
-                           "lane_utilisation_box_phase": round(box / 2 / max(wsteps_box, 1) / 64, 3)},
-            "roofline": roof,
         }
+        if args.full:
+            out.update({
+                "serial_mrays": round(rays / (serial_ms_max * 1e-3) / 1e6, 2),
+                "serial_ms_per_frame": round(serial_ms_max, 4),
+                "serial_is": "one launch at a time (the reference's frame loop): median of 22 event-timed launches"
+                             + ("; slowest rank's part, gather not included" if world > 1 else ""),
+                "box_tests_per_ray": round(box / rays, 2), "tri_tests_per_ray": round(tri / rays, 3),
+                "wave_steps": {"box_phase": wsteps_box, "leaf_phase": wsteps_leaf,
+                               "lane_utilisation_box_phase": round(box / 2 / max(wsteps_box, 1) / 64, 3)},
+                "roofline": roof,
+            })
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], ok = cpu_baseline(tris, cams[cam], W, H, args.spp, args.render_type, G, args.type,
                                                    gpu_frame, (box, tri))
             if not ok:
@@ -628,6 +654,27 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     sys.exit(rc)
+
+
+DUMP_FRAME_MAX_BYTES = 48 << 20   # the frame's float32 copy; a larger frame (config5: 133 MB) is sampled by pixel
+DUMP_SAMPLE_PIXELS = 2_000_000    # 32 MB of RGBA + 16 MB of float64 pixel indices
+
+
+def dump_outputs(out_dir, frame, counters):
+    """What the last timed step returned to its caller, as .npy (float32 / float64), at most 64 MB in all:
+    frame.npy = rank 0's RGBA frame [H, W, 4] (or, above DUMP_FRAME_MAX_BYTES, frame_sample.npy = the RGBA of a fixed
+    seeded sample of pixels [k, 4] and frame_sample_pixels.npy = their row-major pixel indices), counters.npy = the
+    step's test counters (box tests, triangle tests, box-phase and leaf-phase wave steps; rank 0's part)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, _ = frame.shape
+    if frame.size * 4 <= DUMP_FRAME_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame.astype(np.float32))
+    else:
+        pix = np.sort(np.random.default_rng(0).choice(h * w, size=DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), frame.reshape(h * w, 4)[pix].astype(np.float32))
+        np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), pix.astype(np.float64))
+    np.save(os.path.join(out_dir, "counters.npy"), np.asarray(counters).astype(np.float64))
 
 
 def build_record(n, build_ms, sort_us, tree, G, b2b_ms=None):

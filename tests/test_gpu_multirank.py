@@ -77,7 +77,7 @@ def test_bench_one_rank_rccl_api():
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
             env.pop(k, None)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--grid", "100",
-                            "--width", "640", "--height", "360", "--no-extras", "--partition", partition],
+                            "--width", "640", "--height", "360", "--no-extras", "--partition", partition, "--full"],
                            env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-3000:]
         d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -87,11 +87,11 @@ def test_bench_one_rank_rccl_api():
 
 
 def test_bench_line_schema():
-    """The one JSON line of `python bench.py` (N = 1, a small workload): every field of the driver's contract plus the
+    """The one JSON line of `python bench.py --full` (N = 1, a small workload): every field of the driver's contract plus the
     roofline and cpu_baseline objects, and the parity verdict the CPU-baseline leg attaches."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--grid", "120",
-                        "--width", "640", "--height", "360"], env=env, capture_output=True, text=True, timeout=600)
+                        "--width", "640", "--height", "360", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout
@@ -112,3 +112,41 @@ def test_bench_line_schema():
     assert c["kind"] == "port" and c["parity"]["gpu_frame_rows_equal_oracle"] is True
     assert c["parity"]["sum_box_tri_tests_equal_oracle"] is True
     assert abs(d["value"] - 640 * 360 * 6 / (d["ms_per_step"] * 6 * 1e-3) / 1e6) / d["value"] < 0.01
+
+
+def _bench_plain(argv, tmp_path, tag):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = str(tmp_path / tag)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", out], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0]), out
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path, scenes, ora):
+    """A plain `python bench.py` (no --full): the headline fields over exactly --steps timed steps and nothing of --full;
+    --dump-outputs writes the last timed frame and its counters, the same in two runs with the same arguments and equal
+    to the oracle's frame and test counts."""
+    import numpy as np
+    G, W, H, K = 120, 640, 360, 7
+    argv = ["--steps", str(K), "--warmup", "2", "--grid", str(G), "--width", str(W), "--height", str(H)]
+    d, out = _bench_plain(argv, tmp_path, "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "serial_mrays", "build_ms", "box_tests_per_ray"):
+        assert k not in d, k
+    assert d["steps"] == K and d["full"] is False and d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - W * H * K / (d["ms_per_step"] * K * 1e-3) / 1e6) / d["value"] < 0.01
+    frame, ctr = np.load(os.path.join(out, "frame.npy")), np.load(os.path.join(out, "counters.npy"))
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 4) and ctr.dtype == np.float64 and ctr.shape == (4,)
+
+    _, out2 = _bench_plain(argv, tmp_path, "b")
+    assert (np.load(os.path.join(out2, "frame.npy")) == frame).all()
+    assert (np.load(os.path.join(out2, "counters.npy")) == ctr).all()
+
+    o = ora.build_bvh(scenes.grid_mesh(G, 1))
+    img, oc = ora.trace(o["leaves"], o["nodes"], 0, 2, scenes.camera_a(G), W, H)
+    assert (frame == img.astype(np.float32)).all(), "dumped frame differs from the oracle's"
+    assert ctr[0] == float(oc[0]) and ctr[1] == float(oc[1]), "dumped test counters differ from the oracle's"

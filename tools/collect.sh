@@ -20,7 +20,7 @@ if [ "$MODE" = run ]; then
   cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
   O=gpurun_out/$R; mkdir -p $O
   prof() { rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -- "${@:2}" > $O/$1.log 2>&1 && python3 tools/kstats.py $O/$1 > $O/$1_kernel_stats.txt; }
-  B1="--inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline"   # one launch at a time: clean per-launch counters
+  B1="--inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline --full"   # one launch at a time: clean per-launch counters
   pmc() { mkdir -p $(dirname $1); rocprofv3 --kernel-trace --pmc ${@:3} --kernel-include-regex trace_kernel --output-format csv -d $1 -- python3 bench.py $B1 $2 > $1.log 2>&1 || echo "pmc pass $1 failed"; }
   pmcset() {   # $1 = output dir prefix, $2 = extra bench arguments
     pmc $1/a "$2" SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR
@@ -36,16 +36,16 @@ if [ "$MODE" = run ]; then
     tail -2 $O/pytest.log
   fi
   if has bench; then
-    python3 bench.py --steps 50 --warmup 5 > $O/bench_default.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
-    prof prof_bench python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_profiled.json || exit 1
-    python3 bench.py --steps 30 --warmup 5 --inflight 1 --no-cpu-baseline > $O/bench_inflight1.json 2>> $O/bench.err || exit 1
-    python3 bench.py --steps 30 --warmup 5 --camera b --no-cpu-baseline --no-extras > $O/bench_lbvh_camera_b.json 2>> $O/bench.err || exit 1
-    python3 bench.py --preset config4 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_config4.json 2>> $O/bench.err || exit 1
-    python3 bench.py --preset config5 --steps 5 --warmup 1 > $O/bench_config5.json 2>> $O/bench.err || exit 1
+    python3 bench.py --steps 50 --warmup 5 --full > $O/bench_default.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+    prof prof_bench python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --full > $O/bench_profiled.json || exit 1
+    python3 bench.py --steps 30 --warmup 5 --inflight 1 --no-cpu-baseline --full > $O/bench_inflight1.json 2>> $O/bench.err || exit 1
+    python3 bench.py --steps 30 --warmup 5 --camera b --no-cpu-baseline --no-extras --full > $O/bench_lbvh_camera_b.json 2>> $O/bench.err || exit 1
+    python3 bench.py --preset config4 --steps 10 --warmup 2 --no-cpu-baseline --full > $O/bench_config4.json 2>> $O/bench.err || exit 1
+    python3 bench.py --preset config5 --steps 5 --warmup 1 --full > $O/bench_config5.json 2>> $O/bench.err || exit 1
     for t in sah bottom-up-pairs sah-pairs hybrid; do
-      python3 bench.py --type $t --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_$t.json 2>> $O/bench.err
+      python3 bench.py --type $t --steps 30 --warmup 5 --no-cpu-baseline --full > $O/bench_$t.json 2>> $O/bench.err
     done
-    python3 bench.py --gpus 2 --steps 20 --warmup 3 --no-extras --no-cpu-baseline > $O/bench_2ranks_one_gpu_rehearsal.json 2>> $O/bench.err
+    python3 bench.py --gpus 2 --steps 20 --warmup 3 --no-extras --no-cpu-baseline --full > $O/bench_2ranks_one_gpu_rehearsal.json 2>> $O/bench.err
     for cam in a b; do
       for k in 1 4; do
         echo -n "rt_cli --gpus 1 --inflight $k, grid 708 (1M triangles), 1920x1080, camera $cam: "

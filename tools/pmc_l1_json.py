@@ -21,7 +21,7 @@ def medians(root):
 
 a, na = medians(l1dir)
 c, nc = medians(cdir)
-rec = {"source": f"rocprofv3 --kernel-trace --pmc passes of `bench.py --inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline` "
+rec = {"source": f"rocprofv3 --kernel-trace --pmc passes of `bench.py --inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline --full` "
                  f"({date}; tools/collect.sh pmc section; per-launch medians over all trace_kernel launches of a pass)",
        "launches_per_pass": max(list(na.values()) + [0])}
 if "TA_TA_BUSY_sum" in a and "GRBM_GUI_ACTIVE" in a:

@@ -15,9 +15,9 @@ for v in lean0 nosteps; do
 done
 for v in orig lean0 nosteps; do
   cp /tmp/librt_amd$([ $v = orig ] && echo .orig || echo _$v).so librt_amd.so
-  (cd $GRAFT_REPO_ROOT && python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'camera a: inflight', d['value'], 'serial', d['serial_mrays'])") >> $O/spill_experiment.txt
-  (cd $GRAFT_REPO_ROOT && python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras --type sah 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'camera a, SAH tree: inflight', d['value'], 'serial', d['serial_mrays'])") >> $O/spill_experiment.txt
-  (cd $GRAFT_REPO_ROOT && rocprofv3 --kernel-trace --pmc WRITE_SIZE --kernel-include-regex trace_kernel --output-format csv -d $O/w_$v -- python3 bench.py --inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline > $O/w_$v.log 2>&1)
+  (cd ../.. && python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras --full 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'camera a: inflight', d['value'], 'serial', d['serial_mrays'])") >> $O/spill_experiment.txt
+  (cd ../.. && python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras --full --type sah 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'camera a, SAH tree: inflight', d['value'], 'serial', d['serial_mrays'])") >> $O/spill_experiment.txt
+  (cd ../.. && rocprofv3 --kernel-trace --pmc WRITE_SIZE --kernel-include-regex trace_kernel --output-format csv -d $O/w_$v -- python3 bench.py --inflight 1 --steps 3 --warmup 1 --no-extras --no-cpu-baseline --full > $O/w_$v.log 2>&1)
   (cd $GRAFT_REPO_ROOT && python3 tools/pmc_summary.py $O/w_$v | grep -E "trace_kernel|WRITE_SIZE" | sed "s/^/$v  /") >> $O/spill_experiment.txt
 done
 cp /tmp/librt_amd.orig.so librt_amd.so

@@ -10,7 +10,7 @@ done
 for v in orig chunk1 chunk2 chunk4 chunk8 chunk15 chunk60; do
   if [ $v = orig ]; then cp /tmp/librt_amd.orig.so librt_amd.so; else cp /tmp/librt_amd_$v.so librt_amd.so; fi
   for cfg in "--camera a" "--camera b" "--camera a --type sah" "--camera b --type sah"; do
-    (cd $GRAFT_REPO_ROOT && python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras $cfg 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', '$cfg', 'inflight', d['value'], 'serial', d['serial_mrays'])")
+    (cd ../.. && python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --full $cfg 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', '$cfg', 'inflight', d['value'], 'serial', d['serial_mrays'])")
   done
 done
 cp /tmp/librt_amd.orig.so librt_amd.so
