@@ -172,6 +172,31 @@ def _flat_attributes(t, e1, e2, material_ids):
     return at
 
 
+def smooth_uv_attributes(triangles: np.ndarray, material_ids=None, seed: int = 1, uv_scale: float = 0.25, axes=(0, 2),
+                         normal_jitter: float = 0.35, uv_jitter: float = 0.08, facing=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """Attributes whose three corners all differ: per corner, the face normal (flipped to face `facing`) plus a seeded
+    perturbation of up to `normal_jitter` per component, renormalised; and the planar uv of planar_uv_attributes plus a
+    seeded jitter of up to `uv_jitter` * uv_scale per component.  With the jitter well below the edge length in uv, the
+    duv determinant of TangentMatrix (Tracer.cu:88-91) stays bounded away from 0 on well-shaped triangles.  A corner
+    permutation, a bu / bv swap or a sign error in the shading frame changes what these attributes shade."""
+    t = triangles.reshape(-1, 3, 3).astype(np.float32)
+    n = t.shape[0]
+    at = planar_uv_attributes(triangles, material_ids, uv_scale, axes)
+    face = at["normal"][:, 0, :].astype(np.float32)
+    flip = (face @ np.asarray(facing, np.float32)) < 0
+    face[flip] = -face[flip]
+    idx = np.arange(n * 15, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        r = (pcg_hash(idx + np.uint32((seed * 0x01000193) & 0xFFFFFFFF)) >> np.uint32(8)).astype(np.float32)
+    r = (r * np.float32(2.0 ** -23) - np.float32(1.0)).reshape(n, 15)          # [-1, 1)
+    nrm = face[:, None, :] + r[:, :9].reshape(n, 3, 3) * np.float32(normal_jitter)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):    # (degenerate triangles: NaN, as flat_attributes)
+        nrm = nrm / np.sqrt((nrm * nrm).sum(axis=2, keepdims=True, dtype=np.float32)).astype(np.float32)
+    at["normal"] = nrm.astype(np.float32)
+    at["uv"] = (at["uv"] + r[:, 9:].reshape(n, 3, 2) * np.float32(uv_jitter * uv_scale)).astype(np.float32)
+    return at
+
+
 def default_materials(k: int = 3) -> np.ndarray:
     m = np.zeros(k, dtype=MATERIAL)
     pal = np.array([[0.8, 0.3, 0.2], [0.2, 0.7, 0.3], [0.25, 0.35, 0.9], [0.9, 0.8, 0.2]], dtype=np.float32)

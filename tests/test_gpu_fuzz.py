@@ -1,7 +1,7 @@
 """Randomised GPU-vs-oracle parity over scene shapes the fixed tests do not enumerate: random sizes (incl. just above /
 below workgroup and tile boundaries), clustered and duplicated triangles, flat axes, huge and tiny triangles mixed,
 every builder (bottom-up, pairs, hybrid, SAH with pairs / splits) -- Node[] and TrianglePair[] bit-exact, kDepth and
-kBoxtests frames byte-exact, counters equal.  Seeds are fixed: failures reproduce."""
+kBoxtests frames and one surface mode per seed (textured, per-corner attributes) byte-exact, counters equal.  Seeds are fixed: failures reproduce."""
 import numpy as np
 import pytest
 
@@ -87,3 +87,16 @@ def test_fuzz_builders_and_traces(seed, rt, scenes, ora):
         exp, oc = ora.trace(o["leaves"], o["nodes"], root, count, cam, 200, 144, render_type=render)
         assert (got == exp).all(), (seed, render)
         assert int(gc[0]) == int(oc[0]) and int(gc[1]) == int(oc[1])
+    # one surface mode per seed (kMaterialID .. kTextureLitShadows) with distinct per-corner normals and uv, textures,
+    # a bump map and a normal map: the attribute path (rotation of pair leaves, ids of split references) byte-exact
+    import texture_scene
+    render = 3 + seed % 6
+    mats, chains = texture_scene.materials_and_chains(scenes, ora, 4)
+    at = scenes.smooth_uv_attributes(tris, np.arange(n, dtype=np.int32) % 4, seed=seed + 1)
+    lo, hi = tris.reshape(-1, 3).min(axis=0), tris.reshape(-1, 3).max(axis=0)
+    light = tuple(float(x) for x in hi + (hi - lo) * np.float32(0.5))
+    kw = dict(attributes=at, materials=mats, light=light, textures=chains)
+    got, gc = gpu_trace(build, cam, 200, 144, render, root=root, count=count, **kw)
+    exp, oc = ora.trace(o["leaves"], o["nodes"], root, count, cam, 200, 144, render_type=render, **kw)
+    assert (got == exp).all(), (seed, render, int((got != exp).any(axis=-1).sum()))
+    assert int(gc[0]) == int(oc[0]) and int(gc[1]) == int(oc[1])

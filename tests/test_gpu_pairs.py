@@ -53,7 +53,8 @@ def test_pairs_build_bit_exact(name, rt, scenes, ora):
         oi, oc = ora.trace(o["leaves"], o["nodes"], 0, 2, cam, 200, 150, render_type=rtype, attributes=at,
                            materials=mats, light=light)
         d = np.abs(gi.astype(int) - oi.astype(int))
-        assert d.max() <= (1 if rtype == 5 else 0), f"render {rtype}"
+        # exact in every mode: kDiffuse's 1-LSB allowance dated from before the specular pow() was rt_math.h on both sides
+        assert d.max() == 0, f"render {rtype}: {int((d.max(axis=-1) > 0).sum())} pixels differ, max {d.max()}"
         assert (gc == oc[:2]).all()
         if rtype in (0, 3):   # same surfaces as the unpaired tree
             pi, _ = ora.trace(plain["leaves"], plain["nodes"], 0, 2, cam, 200, 150, render_type=rtype, attributes=at,
