@@ -4,7 +4,8 @@ Python is only the harness language here (tests, bench): the product is ``csrc/l
 HIP kernels for gfx950 behind the C ABI of ``include/rt_abi.h`` -- and the C++ host mirror in ``host/``.
 This module binds that C ABI with ctypes and mirrors the reference's entry points by name
 (``BuildInput``, ``BuMemoryRequirements``, ``RunBottomUpBuild``, ``RadixSort``, ``Trace``; reference
-``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``).  torch is used for device
+``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``), plus ray queries over any built
+tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
 
@@ -36,6 +37,13 @@ MATERIAL = np.dtype([("ambient", "<f4", 3), ("diffuse", "<f4", 3), ("specular", 
                      ("specular_exp", "<f4"), ("texture", "<i4"), ("bump", "<i4"), ("disp", "<i4")])  # 52 B
 assert TRIANGLE.itemsize == 36 and NODE.itemsize == 32 and TRIANGLE_PAIR.itemsize == 64
 assert CAMERA.itemsize == 64 and ATTRIBUTES.itemsize == 72 and MATERIAL.itemsize == 52
+# ray queries (rt_intersect_rays / rt_generate_camera_rays)
+RAY = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])                 # 32 B
+HIT = np.dtype([("t", "<f4"), ("primitive_id", "<u4"), ("u", "<f4"), ("v", "<f4")])                          # 16 B
+assert RAY.itemsize == 32 and HIT.itemsize == 16
+MISS = 0xFFFFFFFF
+kClosestHit, kAnyHit = 0, 1
+kRaysRowMajor, kRaysTiled = 0, 1
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -96,7 +104,8 @@ class _SahScratchLayout(ctypes.Structure):
 EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_build", "rt_bu_scratch_layout_get",
            "rt_sah_memory_requirements", "rt_run_sah_build", "rt_sah_scratch_layout_get",
            "rt_calculate_scene_aabb", "rt_generate_morton_codes", "rt_radix_sort_scratch_bytes",
-           "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips", "rt_error_string", "rt_version_string"]
+           "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
+           "rt_intersect_rays", "rt_generate_camera_rays", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -147,6 +156,10 @@ def lib() -> ctypes.CDLL:
     L.rt_trace.argtypes = [ctypes.POINTER(_Accel), ctypes.POINTER(_Scene), vp, i32, vp, u32, u32, u32, u32, u32, vp]
     L.rt_trace_strips.restype = i32
     L.rt_trace_strips.argtypes = [ctypes.POINTER(_Accel), ctypes.POINTER(_Scene), vp, i32, vp, u32, u32, u32, u32, u32, u32, vp]
+    L.rt_intersect_rays.restype = i32
+    L.rt_intersect_rays.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, i32, u32, vp, vp]
+    L.rt_generate_camera_rays.restype = i32
+    L.rt_generate_camera_rays.argtypes = [vp, u32, u32, u32, i32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -354,6 +367,47 @@ def Trace(triangles, nodes, rgba8, dims, camera, root: int, count: int, *, rende
                int(num_primitives), num_materials, textures.count if textures is not None else 0)
     _check(lib().rt_trace(ctypes.byref(a), ctypes.byref(s), _ptr(counters), render_type, _ptr(rgba8), w, h, y0, y1,
                           spp, _stream_ptr(stream)), "rt_trace")
+
+
+def _nbytes(t) -> int:
+    return int(t.numel()) * int(t.element_size())
+
+
+def CameraRayCount(w: int, h: int, spp: int = 1, tiled: bool = False) -> int:
+    """Number of rays GenerateCameraRays writes: w*h*spp row-major, ceil(w/8)*ceil(h/8)*spp*64 tiled."""
+    return ((w + 7) // 8) * ((h + 7) // 8) * spp * 64 if tiled else w * h * spp
+
+
+def GenerateCameraRays(camera, w: int, h: int, rays, *, spp: int = 1, tiled: bool = False, stream=None) -> int:
+    """rt_generate_camera_rays: the primary rays Trace() traces, as RAY records (`rays`: a contiguous device tensor of at
+    least CameraRayCount(w, h, spp, tiled) * 32 bytes, e.g. float32 [N, 8]; `camera`: a 64-byte device buffer as for Trace).
+    Row-major: ray (y*w + x)*spp + s.  Tiled: ray (tile*spp + s)*64 + lane, 8x8 tiles row by row, lane = Morton position in
+    the tile; off-frame lanes get tmax < tmin.  Returns the number of rays written."""
+    n = CameraRayCount(int(w), int(h), int(spp), tiled)
+    if not rays.is_contiguous() or _nbytes(rays) < 32 * n:
+        raise ValueError(f"rays must be a contiguous device buffer of >= {32 * n} bytes")
+    _check(lib().rt_generate_camera_rays(_ptr(camera), int(w), int(h), int(spp), kRaysTiled if tiled else kRaysRowMajor,
+                                         _ptr(rays), _stream_ptr(stream)), "rt_generate_camera_rays")
+    return n
+
+
+def IntersectRays(triangles, nodes, root: int, count: int, rays, hits, *, any_hit: bool = False, num_primitives: int = 0,
+                  counters=None, stream=None) -> None:
+    """rt_intersect_rays: one HIT record per RAY record of `rays` (a contiguous device tensor of 32-byte records, e.g.
+    float32 [N, 8]) into `hits` (>= 16 N bytes, e.g. float32 [N, 4]; view it as int32 for primitive_id).  Any tree Trace()
+    takes (`triangles` / `nodes` as for Trace, root / count of its root node).  Closest hit by default; any_hit=True
+    ends each ray at its first accepted triangle.  A miss is {+inf, MISS, 0, 0}.  counters: optional int64[4] device
+    tensor, added to as by Trace.  num_primitives: scene-size hint as for Trace.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_intersect_rays(ctypes.byref(a), _ptr(rays), _ptr(hits), n, kAnyHit if any_hit else kClosestHit,
+                                   int(num_primitives), _ptr(counters), _stream_ptr(stream)), "rt_intersect_rays")
 
 
 def version() -> str:

@@ -267,6 +267,28 @@ int rt_trace_strips(const rt_accel* as, const rt_scene* scene, uint64_t* counter
                         strip_stride, stream);
 }
 
+int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
+                      uint32_t num_primitives, uint64_t* counters, void* stream)
+{
+    if (!as || !rays || !hits || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (reinterpret_cast<uintptr_t>(hits) & 15u)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_query(*as, rays, hits, num_rays, mode == RT_RAY_ANY_HIT, num_primitives, counters,
+                                   static_cast<hipStream_t>(stream)));
+}
+
+int rt_generate_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, int layout, rt_ray* rays,
+                            void* stream)
+{
+    if (!camera || !rays || (reinterpret_cast<uintptr_t>(rays) & 15u)) return RT_ERR_INVALID_ARGUMENT;
+    if (layout != RT_RAYS_ROW_MAJOR && layout != RT_RAYS_TILED) return RT_ERR_INVALID_ARGUMENT;
+    if (spp != 1 && spp != 4 && spp != 16) return RT_ERR_INVALID_ARGUMENT;
+    if (w == 0 || h == 0) return RT_OK;
+    return hip_rc(launch_camera_rays(camera, w, h, spp, layout == RT_RAYS_TILED, rays, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -285,7 +307,8 @@ const char* rt_version_string(void)
 {
     return "rt_amd gfx950 | sort: LSD 3x10bit Morton keys (4x8bit generic), tile 4096 | lbvh: LDS agglomerative, 512 leaves/wg (4 wg per CU), leaves and node pairs staged in LDS and streamed out + one chained launch for all upper levels (last-arriver tickets, fan 48 or 64; passes of <= 1023 open roots by range searches over sparse tables), hybrid SAH top | "
            "sah: 4x4x4 grid + level-synchronous binned SAH (fixed launch count, no host round trip), workgroup-per-task stragglers, wave-per-task below 64 items, pairs, splits | "
-           "trace: wave64 8x8 tiles, two-phase schedule, LDS stack 16, XCD chunks of 8 workgroups, pair prefetch from 8M primitives, counters through 16-row slots";
+           "trace: wave64 8x8 tiles, two-phase schedule, LDS stack 16, XCD chunks of 8 workgroups, pair prefetch from 8M primitives, counters through 16-row slots | "
+           "rays: caller rays through the same traversal, 64 consecutive rays per wave, closest / any hit, 16-byte records, camera rays row-major or 8x8-tiled";
 }
 
 }  // extern "C"

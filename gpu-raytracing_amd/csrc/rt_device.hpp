@@ -14,6 +14,9 @@ static_assert(sizeof(rt_camera) == 64, "Camera layout (Common.cuh:44)");
 static_assert(sizeof(rt_attributes) == 72, "Attributes layout (Common.cuh:55)");
 static_assert(sizeof(rt_material) == 52, "Material POD mirror");
 static_assert(sizeof(rt_texture) == 216, "Texture POD mirror");
+static_assert(sizeof(rt_ray) == 32 && offsetof(rt_ray, tmin) == 12 && offsetof(rt_ray, dir) == 16 && offsetof(rt_ray, tmax) == 28,
+              "rt_ray: two 16-byte halves (origin, tmin | dir, tmax)");
+static_assert(sizeof(rt_hit) == 16 && offsetof(rt_hit, primitive_id) == 4 && offsetof(rt_hit, v) == 12, "rt_hit: one 16-byte record");
 
 namespace rt {
 

@@ -181,4 +181,10 @@ struct TraceLaunch {
 };
 hipError_t launch_trace(const TraceLaunch& t, hipStream_t st);
 
+// ray_query.hip: rt_intersect_rays / rt_generate_camera_rays after their argument checks (num_rays > 0, w * h > 0)
+hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
+                            uint32_t num_primitives, uint64_t* counters, hipStream_t st);
+hipError_t launch_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, bool tiled, rt_ray* rays,
+                              hipStream_t st);
+
 }  // namespace rt

@@ -36,19 +36,11 @@
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_math.h"
+#include "rt_traverse.hpp"   // Ray, Hit, Trav, box_step, trace_ray, camera_ray (shared with ray_query.hip)
 
 namespace rt {
 
-constexpr int kStackLds = 16;    // LDS-resident stack entries per lane (bench scenes peak at 10)
-constexpr int kStackMax = 64;    // reference stack size (Tracer.cu:314)
-constexpr uint32_t kPrefetchMinPrims = 8u << 20;   // scenes from here on take the pair-prefetch instantiation (see trace_kernel)
-#ifndef RT_TRACE_WAVES
-#define RT_TRACE_WAVES 4
-#endif
-constexpr int kTraceWaves = RT_TRACE_WAVES;   // waves (8x8 tiles) per workgroup
-#ifndef RT_TRACE_MIN_WAVES
-#define RT_TRACE_MIN_WAVES 7   // waves per SIMD the register allocator must fit (72 VGPRs: no spills; 8 -> 64 VGPRs spills)
-#endif
+// (the traversal constants kStackLds, kStackMax, kPrefetchMinPrims, kTraceWaves live in rt_traverse.hpp)
 // Tuning build only (make TUNING=1 -> -DRT_TRACE_TUNING; never in the shipped library): render type 100 writes the raw
 // u32 box-test count per pixel (tools/divergence_stats.py) and RT_TRACE_PARK="num,den" overrides the park threshold.
 #ifdef RT_TRACE_TUNING
@@ -56,10 +48,8 @@ constexpr int kRenderDebugBoxCount = 100;
 #else
 constexpr int kRenderDebugBoxCount = -1;   // matches no render type: every use below folds away
 #endif
-// the wave runs a box step while  stepping * park_den >= parked * park_num  (else one leaf phase)
-constexpr int kParkNum = 8, kParkDen = 1;   // (round-2 sweep under the chunked XCD order, tools/sweep_park.sh: 4..8 equal on the 1080p LBVH frame; 4 is +5 % on the SAH tree but -4 % on the 4K x 16 spp frame)
+// (the park threshold kParkNum / kParkDen: rt_traverse.hpp)
 
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
 // ---- publication of the test counters (see the end of trace_kernel).  The caller's four counters are ONE 32-byte target
 // for every workgroup of a frame, and same-address device atomics queue at the memory side at ~18 ns each: 8,100
@@ -98,254 +88,6 @@ struct TraceParams {
     uint32_t ctr_slot;   // counters != null: this launch's slot of g_ctr
 };
 
-struct Ray {
-    float ox, oy, oz, dx, dy, dz, ix, iy, iz, tmin, tmax;
-};
-struct Hit {
-    uint32_t primitive_id, tri_id;
-    float bu, bv;
-};
-
-// Tracer.cu:256-291
-__device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, float v1x, float v1y, float v1z,
-                                              float v2x, float v2y, float v2z, Ray& r, Hit& h, uint32_t tri_id,
-                                              uint32_t prim_id)
-{
-    const float epsilon = 0.000000001f;
-    const float e1x = v1x - v0x, e1y = v1y - v0y, e1z = v1z - v0z;
-    const float e2x = v2x - v0x, e2y = v2y - v0y, e2z = v2z - v0z;
-    const float hx = r.dy * e2z - r.dz * e2y, hy = r.dz * e2x - r.dx * e2z, hz = r.dx * e2y - r.dy * e2x;
-    const float a = e1x * hx + e1y * hy + e1z * hz;
-    if (a > -epsilon && a < epsilon) return false;
-    const float f = 1.0f / a;
-    const float sx = r.ox - v0x, sy = r.oy - v0y, sz = r.oz - v0z;
-    const float u = f * (sx * hx + sy * hy + sz * hz);
-    if (u < 0.0f || u > 1.0f) return false;
-    const float qx = sy * e1z - sz * e1y, qy = sz * e1x - sx * e1z, qz = sx * e1y - sy * e1x;
-    const float v = f * (r.dx * qx + r.dy * qy + r.dz * qz);
-    if (v < 0.0f || (u + v) > 1.0f) return false;
-    const float t = f * (e2x * qx + e2y * qy + e2z * qz);
-    if (t < r.tmin || t > r.tmax) return false;
-    r.tmax = t;
-    h.primitive_id = prim_id;
-    h.tri_id = tri_id;
-    h.bu = u;
-    h.bv = v;
-    return true;
-}
-
-// per-lane traversal state
-enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3 };
-constexpr uint32_t kNoNear = 0xFFFFFFFFu;  // "no Box child hit yet" (child 2^29-1, count 7: not a real entry)
-
-// The private spill array is NOT a member: a dynamically indexed member would pin the whole struct in scratch.
-typedef uint32_t SpillArray[kStackMax - kStackLds];
-
-struct Trav {
-    lds_u32* lds;  // this lane's stack column: entry k at lds[k * 64]
-    uint32_t* spill;
-    int sp;
-    uint32_t cur;       // slots still to visit of the current node: first slot : 29 | slot count : 3
-    uint32_t near_e;    // nearest Box child so far (packed like cur) or kNoNear
-    float near_d;       // its front distance (+inf while kNoNear)
-    uint32_t phase;
-    uint32_t leaf;      // pending leaf: index : 29 | count : 3
-    // second slot of the current pair, kept while parked in PH_LEAF0
-    float f1, k1;       // front / back
-    uint32_t e1;        // child : 29 | count : 3
-    uint32_t t1;        // type, 0 = none / absent
-    uint32_t box_tests, tri_tests;
-    // PF instantiations only (scenes whose tree does not fit the caches, see launch_trace): the next pair's four 16-byte
-    // loads, issued as soon as advance() has picked it -- before the wave's next vote -- and carried in registers
-    uint4 pf0, pf1, pf2, pf3;
-
-    __device__ __forceinline__ void push(uint32_t e)
-    {
-        if (sp < kStackLds) lds[sp * 64] = e;
-        else if (sp < kStackMax) spill[sp - kStackLds] = e;
-        sp = min(sp + 1, kStackMax);  // a push onto a full stack is dropped (the reference overruns its array, Tracer.cu:353-369)
-    }
-    // A Box child (Tracer.cu:338-363), predicated on `in`: the first hit becomes `near`; a closer one (ties:
-    // larger child index) displaces `near` onto the stack; otherwise it is pushed itself.  Bitwise logic on
-    // purpose (no short-circuit branches); with no near yet near_d = +inf makes every hit "closer".
-    __device__ __forceinline__ void inner_hit(bool in, uint32_t e, float front)
-    {
-        const bool closer = (front < near_d) | ((front == near_d) & ((e & kIndexMask) > (near_e & kIndexMask)));
-        if (in & (near_e != kNoNear)) push(closer ? near_e : e);
-        const bool take = in & closer;
-        near_e = take ? e : near_e;
-        near_d = take ? front : near_d;
-    }
-    // the current pair is finished: remaining slots of the same node (count > 2 only, never in an LBVH), else
-    // the nearest child (the reference pushes it last and pops it first -- so on a FULL stack that push is dropped
-    // like any other and the entry below it is popped instead: same rule as the oracle), else a popped entry, else done
-    __device__ __forceinline__ void advance()
-    {
-        const uint32_t cnt = cur >> 29;
-        if (cnt > 2) { cur = ((cur & kIndexMask) + 2) | ((cnt - 2) << 29); return; }
-        const bool keep = (near_e != kNoNear) & (sp < kStackMax);
-        if (keep) cur = near_e;
-        else if (sp == 0) phase = PH_DONE;
-        else { --sp; cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds]; }
-        near_e = kNoNear;
-        near_d = __builtin_inff();
-    }
-    // second slot of the pair, evaluated with the CURRENT tmax (after any leaf hit of the first slot)
-    __device__ __forceinline__ void second_slot(float tmin, float tmax)
-    {
-        const bool valid = t1 != RT_CHILD_NONE;
-        const bool hit = valid & (k1 >= f1) & (f1 <= tmax) & (k1 >= tmin);
-        box_tests += valid ? 1u : 0u;
-        const bool is_leaf = hit & (t1 == RT_CHILD_TRI);
-        inner_hit(hit & !is_leaf, e1, f1);
-        if (is_leaf) { leaf = e1; phase = PH_LEAF1; }
-    }
-};
-
-// IntersectRayAabb without the tmax/tmin comparisons (Tracer.cu:187-197): front/back of one slot
-__device__ __forceinline__ void slab(const uint4& a, const uint4& b, const Ray& r, float& front, float& back)
-{
-    // x and y go through v_pk_add_f32 / v_pk_mul_f32 (two IEEE f32 ops per instruction, same rounding)
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f o2 = {r.ox, r.oy}, i2 = {r.ix, r.iy};
-    const v2f lo = {__uint_as_float(a.x), __uint_as_float(a.y)}, hi = {__uint_as_float(b.x), __uint_as_float(b.y)};
-    const v2f t1 = (lo - o2) * i2, t2 = (hi - o2) * i2;
-    const float t1z = (__uint_as_float(a.z) - r.oz) * r.iz, t2z = (__uint_as_float(b.z) - r.oz) * r.iz;
-    front = fmaxf(fmaxf(fminf(t1.x, t2.x), fminf(t1.y, t2.y)), fminf(t1z, t2z));
-    back = fminf(fminf(fmaxf(t1.x, t2.x), fmaxf(t1.y, t2.y)), fmaxf(t1z, t2z));
-}
-
-template <bool PF>
-__device__ __forceinline__ void prefetch_pair(const TraceParams& p, Trav& t)
-{
-    if constexpr (PF) {
-        if (t.phase == PH_STEP) {
-            const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
-            const int o1 = (t.cur >> 29) > 1 ? 2 : 0;
-            t.pf0 = np[0]; t.pf1 = np[1]; t.pf2 = np[o1]; t.pf3 = np[o1 + 1];
-        }
-    }
-}
-
-// One box step of a lane (Tracer.cu:323-352 for one pair): both slots of the current pair are loaded and both slabs
-// computed before the ordered tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.
-template <bool PF>
-__device__ __forceinline__ void box_step(const TraceParams& p, const Ray& r, Trav& t)
-{
-    const uint32_t cnt = t.cur >> 29;
-    const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
-#ifdef RT_EXP_BOX_PAD   // experiment arm (csrc/Makefile librt_amd_exp.so): N extra VALU instructions per box step -- which pipe bounds the kernel?
-#pragma unroll
-    for (int q = 0; q < RT_EXP_BOX_PAD; q++) asm volatile("v_mov_b32 %0, %0" : "+v"(t.box_tests));
-#endif
-    const bool two = cnt > 1;
-    const int o1 = two ? 2 : 0;  // all four loads issue together; a lone slot is simply read twice
-    uint4 a0, b0, a1, b1;
-    if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
-    else { a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1]; }
-    float f0, k0;
-    slab(a0, b0, r, f0, k0);
-    slab(a1, b1, r, t.f1, t.k1);
-    t.e1 = (b1.w & kIndexMask) | (a1.w & ~kIndexMask);
-    t.t1 = two ? (b1.w >> 29) : (uint32_t)RT_CHILD_NONE;
-    const uint32_t type0 = b0.w >> 29;
-    const uint32_t e0 = (b0.w & kIndexMask) | (a0.w & ~kIndexMask);
-    const bool valid0 = type0 != RT_CHILD_NONE;
-    const bool hit0 = valid0 & (k0 >= f0) & (f0 <= r.tmax) & (k0 >= r.tmin);
-    t.box_tests += valid0 ? 1u : 0u;
-    const bool leaf0 = hit0 & (type0 == RT_CHILD_TRI);
-    t.inner_hit(hit0 & !leaf0, e0, f0);
-    if (leaf0) { t.leaf = e0; t.phase = PH_LEAF0; }
-    else {
-        t.second_slot(r.tmin, r.tmax);
-        if (t.phase == PH_STEP) { t.advance(); prefetch_pair<PF>(p, t); }
-    }
-}
-
-// Tracer.cu:308-374, restructured as described in the file header.  Returns tri_hit.
-// steps[0] / steps[1] count the wave's box-phase / leaf-phase iterations (profiling aid).
-template <bool PF>
-__device__ __forceinline__ bool trace_ray(const TraceParams& p, Ray& r, Hit& h, Trav& t, bool active, uint32_t* steps)
-{
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    prefetch_pair<PF>(p, t);
-    bool tri_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-#ifdef RT_EXP_UNIFORM_STATS
-    uint32_t ustat[4] = {0, 0, 0, 0};
-#endif
-
-    while (true) {
-        // ---------------------------------------------------- box phase: step while enough lanes want to
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;   // two box steps per vote (below)
-#ifdef RT_EXP_UNIFORM_STATS   // experiment: how often do the stepping lanes of a wave sit on <= 1 / 2 / 4 distinct pairs?  (steps[1] = histogram packed 16 bits each)
-            {
-                uint64_t rest = stepping;
-                int distinct = 0;
-                while (rest && distinct < 5) {
-                    const int l0 = __ffsll((unsigned long long)rest) - 1;
-                    const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)t.cur, l0);
-                    rest &= ~__builtin_amdgcn_ballot_w64(t.phase == PH_STEP && t.cur == c0);
-                    distinct++;
-                }
-                ustat[distinct <= 1 ? 0 : (distinct == 2 ? 1 : (distinct <= 4 ? 2 : 3))]++;
-            }
-#endif
-            if (t.phase == PH_STEP) box_step<PF>(p, r, t);
-            // second step under the same vote: halves the per-step loop overhead (ballots, branch, copies)
-            if (t.phase == PH_STEP) box_step<PF>(p, r, t);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase (Tracer.cu:333-337, 293-306)
-        nleaf++;
-        if ((t.phase - 1u) < 2u) {
-            t.tri_tests++;
-            const uint32_t li = t.leaf & kIndexMask;
-            const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + li);
-            const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-            bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                         __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                         __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                         r, h, li << 1, l0.w);
-            // triangle B = (v2, v1, v3) is requested whenever count > 0; for a single triangle v3 == v2
-            // bit for bit, B's edge2 is exactly 0, a == 0 and the reference rejects it: skipped, same result.
-            if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
-                hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                         __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                         __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                         r, h, (li << 1) + 1, l1.w);
-            tri_hit |= hit_tri;
-            const bool was_first = t.phase == PH_LEAF0;
-            t.phase = PH_STEP;
-            if (was_first) t.second_slot(r.tmin, r.tmax);
-            if (t.phase == PH_STEP) { t.advance(); prefetch_pair<PF>(p, t); }
-        }
-    }
-#ifdef RT_EXP_UNIFORM_STATS
-    steps[0] += ustat[RT_EXP_UNIFORM_STATS == 1 ? 0 : 2];   // votes whose stepping lanes sit on 1 (arm 1) / 3-4 (arm 2) distinct pairs
-    steps[1] += ustat[RT_EXP_UNIFORM_STATS == 1 ? 1 : 3];   // ... 2 (arm 1) / more than 4 (arm 2)
-    (void)nbox; (void)nleaf;
-#elif !defined(RT_TRACE_NO_STEPS)
-    steps[0] += nbox;
-    steps[1] += nleaf;
-#endif
-    return tri_hit;
-}
 
 __device__ __forceinline__ float clampf(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }
 
@@ -500,19 +242,10 @@ __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_came
                                              float ox, float oy, Trav& t, bool active, uint32_t& box_acc,
                                              uint32_t& tri_acc, uint32_t* steps, float& R, float& G, float& B, float& A)
 {
-    const float ndcx = 2 * (((float)x + ox) / (float)p.w) - 1;
-    const float ndcy = 2 * (((float)y + oy) / (float)p.h) - 1;
-    const float px = (ndcx * cam.u.x + ndcy * cam.v.x) + 1.0f * cam.w.x;
-    const float py = (ndcx * cam.u.y + ndcy * cam.v.y) + 1.0f * cam.w.y;
-    const float pz = (ndcx * cam.u.z + ndcy * cam.v.z) + 1.0f * cam.w.z;
-    const float inv_len = 1.0f / sqrtf(px * px + py * py + pz * pz);  // normalize = v * rsqrtf(dot) (helper_math.h:1318)
     const float max_depth = cam.max_depth;
     Ray r;
-    r.dx = px * inv_len; r.dy = py * inv_len; r.dz = pz * inv_len;
-    r.ox = cam.position.x; r.oy = cam.position.y; r.oz = cam.position.z;
+    camera_ray(cam, p.w, p.h, x, y, ox, oy, r);
     r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
-    r.tmin = 0.00001f;
-    r.tmax = max_depth;
     Hit h = {0u, 0u, 0.f, 0.f};
     const bool hit = trace_ray<PF>(p, r, h, t, active, steps);
     const uint32_t box_tests = t.box_tests, tri_tests = t.tri_tests;
@@ -675,15 +408,7 @@ __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_came
 // spill and it is 2 - 5 x slower everywhere (profiles/r04_trace_10m_experiments.txt).  launch_trace picks it by scene size.
 template <int RENDER, bool PF>
 // kDepth / kBoxtests / kTriangleTests end in a one-line colour conversion: they fit 64 VGPRs (8 waves per SIMD); the
-// shading of the other render types would spill there, they keep 72 VGPRs (7 waves)
-// (RT_TRACE_LEAN_EXTRA = 0 and RT_TRACE_NO_STEPS are the compile-time arms of tools/trace_spill_experiment.sh, which priced
-// the spills of the 64-VGPR instantiations: see DESIGN section 5)
-#ifndef RT_TRACE_LEAN_EXTRA
-#define RT_TRACE_LEAN_EXTRA 1
-#endif
-#ifndef RT_TRACE_PF_WAVES
-#define RT_TRACE_PF_WAVES 5
-#endif
+// shading of the other render types would spill there, they keep 72 VGPRs (7 waves) (RT_TRACE_LEAN_EXTRA: rt_traverse.hpp)
 __global__ __launch_bounds__(kTraceWaves * 64, PF ? RT_TRACE_PF_WAVES : ((RENDER <= 2 || RENDER == kRenderDebugBoxCount) ? RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA : RT_TRACE_MIN_WAVES))
 void trace_kernel(TraceParams p)
 {
@@ -697,21 +422,8 @@ void trace_kernel(TraceParams p)
         __syncthreads();
     }
 
-    // XCD-aware remap: hardware deals workgroup b to XCD b % 8; give XCD x a contiguous run of tiles.
-    // Tile order vs XCDs: hardware deals workgroup b to XCD b % 8.  XCD x takes chunks of kXcdChunk consecutive workgroups
-    // (8 x 4 tiles = a 256 x 8 pixel run: neighbouring rays meet in one L2) dealt round-robin over the whole frame, so
-    // every XCD sees every region of the image.  (Round 1 gave each XCD one contiguous eighth of the frame: fine for a
-    // uniform view, but a view whose cost is concentrated in part of the frame -- camera B: the foreground rows -- then
-    // runs on two or three XCDs while the others idle: 1297 vs 3490 Mrays/s serial, 2548 vs 5397 with frames in flight.)
-    // RT_TRACE_XCD_CHUNK overrides the chunk at compile time (tools/xcd_chunk_experiment.sh).
-#ifndef RT_TRACE_XCD_CHUNK
-#define RT_TRACE_XCD_CHUNK 8
-#endif
-    const uint32_t nb = gridDim.x, bid = blockIdx.x;
-    constexpr uint32_t kXcdChunk = RT_TRACE_XCD_CHUNK;
-    const uint32_t full = nb / (8u * kXcdChunk) * (8u * kXcdChunk);   // (the last < 8 * chunk workgroups keep their index)
-    const uint32_t xcd = bid & 7u, loc = bid >> 3;
-    const uint32_t vb = bid < full ? (loc / kXcdChunk) * (8u * kXcdChunk) + xcd * kXcdChunk + (loc % kXcdChunk) : bid;
+    // XCD-aware remap (xcd_chunk_block, rt_traverse.hpp): an XCD takes runs of 8 consecutive workgroups = 8 x 4 tiles
+    const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
     const uint32_t tile = vb * kTraceWaves + wave;
 
     // lane -> pixel inside the 8x8 tile, Morton order

@@ -10,7 +10,8 @@
  * -(hipError_t) - 1000 when a HIP call failed (the reference calls exit() instead, Common.cuh:358-366).
  *
  * POD layouts are byte-identical to the reference's (sizes checked by static_assert in the library):
- *   rt_triangle 36, rt_node 32, rt_triangle_pair 64, rt_camera 64, rt_attributes 72.
+ *   rt_triangle 36, rt_node 32, rt_triangle_pair 64, rt_camera 64, rt_attributes 72 (rt_ray 32, rt_hit 16: no reference
+ *   counterpart).
  */
 #ifndef RT_ABI_H
 #define RT_ABI_H
@@ -218,6 +219,43 @@ int rt_trace(const rt_accel* as, const rt_scene* scene, uint64_t* counters, int 
 int rt_trace_strips(const rt_accel* as, const rt_scene* scene, uint64_t* counters, int render_type,
                     uint8_t* rgba8_compact, uint32_t w, uint32_t h, uint32_t strip_rows, uint32_t first_strip,
                     uint32_t strip_stride, uint32_t spp, void* stream);
+
+/* ---- ray queries (no reference counterpart: the reference only traces its own camera rays, Tracer.cu:471-595).
+ * rt_ray: origin, tmin, direction, tmax -- 32 bytes, two 16-byte halves.  The direction need not be normalised; t is in units
+ * of |dir|; tmax = +inf is allowed.  A ray with tmin > tmax or a NaN component is not traced (a miss, no tests counted).
+ * rt_hit: closest hit (or, RT_RAY_ANY_HIT, some hit) of a ray -- 16 bytes:
+ *   t             hit distance, in [tmin, tmax]
+ *   primitive_id  the caller's triangle index (the leaf's primitive_id_0/1: split references report their original triangle)
+ *   u, v          barycentric weights of the caller's corners v1 and v2: o + t*d ~= (1-u-v)*v0 + u*v1 + v*v2 (pair leaves
+ *                 store rotated triangles; the weights are mapped back through rt_triangle_pair.rotations as the shading does)
+ *   a miss is {+inf, RT_MISS, 0, 0}. */
+typedef struct rt_ray { rt_float3 origin; float tmin; rt_float3 dir; float tmax; } rt_ray;
+typedef struct rt_hit { float t; uint32_t primitive_id; float u, v; } rt_hit;
+#define RT_MISS 0xFFFFFFFFu
+enum { RT_RAY_CLOSEST_HIT = 0, RT_RAY_ANY_HIT = 1 };
+enum { RT_RAYS_ROW_MAJOR = 0, RT_RAYS_TILED = 1 };
+
+/* hits[i] for rays[i], i < num_rays, through any tree rt_trace takes.  Per-ray semantics are rt_trace's exactly (slab test,
+ * Moller-Trumbore with the same epsilon, slot order, nearest child first, 64-entry stack with dropped pushes, pops not
+ * re-culled), so through the same rays the closest-hit records and test counts equal rt_trace's.  mode RT_RAY_ANY_HIT ends a
+ * ray's traversal at its first accepted triangle.  rays / hits: 16-byte aligned device arrays; hits[i >= num_rays] are not
+ * written.  counters: optional device uint64[4], as for rt_trace ([0] += sum of box tests, [1] += sum of triangle tests,
+ * [2] / [3] += wave-level box-phase / leaf-phase steps); one LDS reduction + 4 device atomics per workgroup of 256 rays.
+ * num_primitives: scene-size hint as rt_scene.num_attributes (0 = unknown; from 8M on the pair-prefetch traversal).
+ * num_rays = 0: nothing runs. */
+int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
+                      uint32_t num_primitives, uint64_t* counters, void* stream);
+
+/* The primary rays rt_trace traces for a w x h frame at spp in {1, 4, 16}, bit for bit (direction, origin = camera position,
+ * tmin = 0.00001, tmax = camera->max_depth; the same stratified sub-pixel offsets).  camera: device pointer.  Layouts:
+ *   RT_RAYS_ROW_MAJOR  w*h*spp rays; ray (y*w + x)*spp + s is sample s of pixel (x, y)
+ *   RT_RAYS_TILED      tiles_x*tiles_y*spp*64 rays, tiles_x = ceil(w/8), tiles_y = ceil(h/8); ray (tile*spp + s)*64 + lane,
+ *                      tile = ty*tiles_x + tx, pixel (8*tx + lx, 8*ty + ly) with lane = Morton(lx, ly): lx = lane bits 0, 2, 4,
+ *                      ly = lane bits 1, 3, 5 -- one wave of rt_intersect_rays gets one 8 x 8 tile and one sample, rt_trace's
+ *                      coherence.  Off-frame lanes of edge tiles get a ray with tmax = -1 < tmin (a miss, nothing traced).
+ * rays: 16-byte aligned.  w*h = 0: nothing runs. */
+int rt_generate_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, int layout, rt_ray* rays,
+                            void* stream);
 
 /* static string for a return code */
 const char* rt_error_string(int code);
