@@ -5,7 +5,8 @@ HIP kernels for gfx950 behind the C ABI of ``include/rt_abi.h`` -- and the C++ h
 This module binds that C ABI with ctypes and mirrors the reference's entry points by name
 (``BuildInput``, ``BuMemoryRequirements``, ``RunBottomUpBuild``, ``RadixSort``, ``Trace``; reference
 ``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``), plus ray queries over any built
-tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out).  torch is used for device
+tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
+vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
 
@@ -44,6 +45,8 @@ assert RAY.itemsize == 32 and HIT.itemsize == 16
 MISS = 0xFFFFFFFF
 kClosestHit, kAnyHit = 0, 1
 kRaysRowMajor, kRaysTiled = 0, 1
+# refit status flags (rt_refit_plan_layout.status)
+RT_REFIT_BAD_TREE, RT_REFIT_PLAN_MISMATCH, RT_REFIT_PAIR_BROKEN = 1, 2, 4
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -101,11 +104,17 @@ class _SahScratchLayout(ctypes.Structure):
                 ("num_leaves", ctypes.c_size_t), ("cell_counts", ctypes.c_size_t), ("total", ctypes.c_size_t)]
 
 
+class _RefitPlanLayout(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
+                ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
+
+
 EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_build", "rt_bu_scratch_layout_get",
            "rt_sah_memory_requirements", "rt_run_sah_build", "rt_sah_scratch_layout_get",
            "rt_calculate_scene_aabb", "rt_generate_morton_codes", "rt_radix_sort_scratch_bytes",
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
-           "rt_intersect_rays", "rt_generate_camera_rays", "rt_error_string", "rt_version_string"]
+           "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
+           "rt_build_refit_plan", "rt_refit", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -160,6 +169,14 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, i32, u32, vp, vp]
     L.rt_generate_camera_rays.restype = i32
     L.rt_generate_camera_rays.argtypes = [vp, u32, u32, u32, i32, vp, vp]
+    L.rt_refit_plan_bytes.restype = ctypes.c_size_t
+    L.rt_refit_plan_bytes.argtypes = [u32]
+    L.rt_refit_plan_layout_get.restype = i32
+    L.rt_refit_plan_layout_get.argtypes = [u32, ctypes.POINTER(_RefitPlanLayout)]
+    L.rt_build_refit_plan.restype = i32
+    L.rt_build_refit_plan.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
+    L.rt_refit.restype = i32
+    L.rt_refit.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -408,6 +425,45 @@ def IntersectRays(triangles, nodes, root: int, count: int, rays, hits, *, any_hi
     a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
     _check(lib().rt_intersect_rays(ctypes.byref(a), _ptr(rays), _ptr(hits), n, kAnyHit if any_hit else kClosestHit,
                                    int(num_primitives), _ptr(counters), _stream_ptr(stream)), "rt_intersect_rays")
+
+
+def RefitPlanBytes(num_triangles: int) -> int:
+    """rt_refit_plan_bytes: device bytes of a refit plan for n triangles (36 per triangle + about 18 KB)."""
+    return int(lib().rt_refit_plan_bytes(num_triangles))
+
+
+def refit_plan_layout(num_triangles: int) -> _RefitPlanLayout:
+    out = _RefitPlanLayout()
+    _check(lib().rt_refit_plan_layout_get(num_triangles, ctypes.byref(out)), "rt_refit_plan_layout_get")
+    return out
+
+
+def _build_input(inp: BuildInput) -> _BuildInput:
+    return _BuildInput(_ptr(inp.triangles_in), _ptr(inp.triangles_out), inp.num_triangles, _ptr(inp.nodes_out),
+                       _ptr(inp.scratch))
+
+
+def BuildRefitPlan(inp: BuildInput, root: int, count: int, plan, stream=None) -> None:
+    """rt_build_refit_plan: walk the tree built into `inp` from its root (root, count as for Trace) and fill `plan` (a device
+    buffer of >= RefitPlanBytes(n) bytes, 256-byte aligned, e.g. device_bytes(RefitPlanBytes(n))).  Once per build.
+    Asynchronous on `stream`; errors land in the plan's status word (refit_status)."""
+    ci = _build_input(inp)
+    _check(lib().rt_build_refit_plan(ctypes.byref(ci), int(root), int(count), _ptr(plan), _stream_ptr(stream)),
+           "rt_build_refit_plan")
+
+
+def Refit(inp: BuildInput, root: int, count: int, plan, stream=None) -> None:
+    """rt_refit: inp.triangles_in holds the NEW positions (same triangles, same order as at build time); rewrites the leaf
+    records in inp.triangles_out and the boxes of the reachable slots in inp.nodes_out.  `plan` from BuildRefitPlan on the
+    same tree.  Asynchronous on `stream`, one launch; status flags in the plan (refit_status)."""
+    ci = _build_input(inp)
+    _check(lib().rt_refit(ctypes.byref(ci), int(root), int(count), _ptr(plan), _stream_ptr(stream)), "rt_refit")
+
+
+def refit_status(plan, num_triangles: int) -> int:
+    """The plan's RT_REFIT_* flags (copies the status word back: waits for the work queued before it on the current stream).
+    Sticky: BuildRefitPlan clears them, every Refit only adds to them."""
+    return int(to_host(plan, np.uint32, 1, refit_plan_layout(num_triangles).status)[0])
 
 
 def version() -> str:

@@ -289,6 +289,49 @@ int rt_generate_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uin
     return hip_rc(launch_camera_rays(camera, w, h, spp, layout == RT_RAYS_TILED, rays, static_cast<hipStream_t>(stream)));
 }
 
+size_t rt_refit_plan_bytes(uint32_t num_triangles) { return refit_layout(num_triangles).total; }
+
+int rt_refit_plan_layout_get(uint32_t num_triangles, rt_refit_plan_layout* out)
+{
+    if (!out) return RT_ERR_INVALID_ARGUMENT;
+    const RefitLayout L = refit_layout(num_triangles);
+    out->status = L.status;
+    out->parents = L.parents;
+    out->arrivals = L.arrive;
+    out->leaves = L.list;
+    out->total = L.total;
+    return RT_OK;
+}
+
+// the checks both refit entry points share; 1 = valid and there is work, 0 = valid and n = 0, < 0 = an RT_ERR_*
+static int refit_args(const rt_build_input* input, uint32_t count, const void* plan, bool need_positions)
+{
+    if (!input || !plan || count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(plan) & 255u) return RT_ERR_INVALID_ARGUMENT;
+    const uint32_t n = input->num_triangles;
+    if (n > RT_REFIT_MAX_TRIANGLES) return RT_ERR_TOO_LARGE;
+    if (n == 0) return 0;
+    if (!input->nodes_out || !input->triangles_out || (need_positions && !input->triangles_in)) return RT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(input->triangles_in) & 15u) || (reinterpret_cast<uintptr_t>(input->triangles_out) & 63u) ||
+        (reinterpret_cast<uintptr_t>(input->nodes_out) & 63u))
+        return RT_ERR_INVALID_ARGUMENT;
+    return 1;
+}
+
+int rt_build_refit_plan(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream)
+{
+    const int rc = refit_args(input, count, plan, false);
+    if (rc <= 0) return rc;
+    return hip_rc(launch_refit_plan(*input, root, count, plan, static_cast<hipStream_t>(stream)));
+}
+
+int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream)
+{
+    const int rc = refit_args(input, count, plan, true);
+    if (rc <= 0) return rc;
+    return hip_rc(launch_refit(*input, root, count, plan, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -308,7 +351,9 @@ const char* rt_version_string(void)
     return "rt_amd gfx950 | sort: LSD 3x10bit Morton keys (4x8bit generic), tile 4096 | lbvh: LDS agglomerative, 512 leaves/wg (4 wg per CU), leaves and node pairs staged in LDS and streamed out + one chained launch for all upper levels (last-arriver tickets, fan 48 or 64; passes of <= 1023 open roots by range searches over sparse tables), hybrid SAH top | "
            "sah: 4x4x4 grid + level-synchronous binned SAH (fixed launch count, no host round trip), workgroup-per-task stragglers, wave-per-task below 64 items, pairs, splits | "
            "trace: wave64 8x8 tiles, two-phase schedule, LDS stack 16, XCD chunks of 8 workgroups, pair prefetch from 8M primitives, counters through 16-row slots | "
-           "rays: caller rays through the same traversal, 64 consecutive rays per wave, closest / any hit, 16-byte records, camera rays row-major or 8x8-tiled";
+           "rays: caller rays through the same traversal, 64 consecutive rays per wave, closest / any hit, 16-byte records, camera rays row-major or 8x8-tiled | "
+           "refit: top-down plan walk (one wide launch per level + one-workgroup tail, one CAS per run), one thread per leaf slot "
+           "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max";
 }
 
 }  // extern "C"

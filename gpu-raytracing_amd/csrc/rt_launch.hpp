@@ -187,4 +187,18 @@ hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits
 hipError_t launch_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, bool tiled, rt_ray* rays,
                               hipStream_t st);
 
+// refit.hip: rt_build_refit_plan / rt_refit after their argument checks (n > 0)
+struct RefitLayout {
+    size_t status;    // the plan header (256 bytes; word 0 = RT_REFIT_* flags)
+    size_t parents;   // uint32[slots]
+    size_t arrive;    // uint8[slots]
+    size_t list;      // uint32[slots]
+    size_t total;
+    uint32_t slots;   // rt_nodes_bytes(n) / 32
+};
+RefitLayout refit_layout(uint32_t n);
+uint32_t refit_plan_wide_levels(uint32_t n);   // wide walk launches of a plan build (then one single-workgroup launch)
+hipError_t launch_refit_plan(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
+hipError_t launch_refit(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
+
 }  // namespace rt

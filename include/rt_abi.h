@@ -257,6 +257,67 @@ int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint
 int rt_generate_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, int layout, rt_ray* rays,
                             void* stream);
 
+/* ---- refit (no reference counterpart: the reference's bottom-up box pass exists only inside its LBVH build,
+ * BottomUpBuilder.cu:217-285).  Keeps the topology and leaf assignment of a built tree and recomputes its geometry after the
+ * caller's vertices moved: the leaf records' vertices and the box of every slot reachable from (root, count).
+ *
+ * rt_build_refit_plan, once per build: walks the tree top-down from (root, count) and fills `plan` (the parent of every
+ * reachable slot run, its expected arrivals, the leaf-slot list, a status word and a fingerprint of nodes_out, root, count and
+ * n).  It reads input->nodes_out and input->triangles_out only.
+ * rt_refit, every frame: input->triangles_in holds the NEW positions (same count, same order as at build time).  It rewrites
+ * the vertices of the leaf records in input->triangles_out and the boxes of the reachable slots in input->nodes_out; every
+ * other byte is left as it is (the w12 / w28 words, primitive ids, rotations, pad3, NONE slots, unreachable slots).
+ * Both are asynchronous (no host copy, no synchronisation: hipGraph-capturable), with a fixed number of launches for a given
+ * n: the plan 5 + ceil(log2 n) launches, the refit one.
+ *
+ * Leaf records.  A record is rebuilt from input->triangles_in; its ids and rotations stay as the build wrote them.  Every
+ * builder writes a single-triangle record with primitive_id_1 = 0 and a pair record with primitive_id_1 = primitive_id_0 + 1
+ * (lbvh_levels.hip, sah_build.hip, the oracle): that is how the two are told apart.
+ *   single: v0..v2 = triangle primitive_id_0, v3 = v2 bit for bit (the traversal relies on v3 == v2).
+ *   pair:   A = triangle primitive_id_0 rotated by rotations[0] (1: (v2, v0, v1), 2: (v1, v2, v0), else as is), v3 = corner
+ *           v0 (rotations[1] = 2), v1 (1) or v2 (else) of B = triangle primitive_id_0 + 1 -- CreateTrianglePair's layout.
+ *   With splits (rt_run_sah_build, enable_splits) a record is shared by several leaf slots: each writes the same bytes.
+ * Boxes.  A leaf slot gets the ordered min / max of its record's triangle corners (A, plus B for a pair); a box slot the
+ * ordered union of the boxes of the non-NONE slots of its child run [child, child + count) (any run length 1..7).  Ordered
+ * min / max compare the floats' monotone integer image, -0 below +0: the result does not depend on arrival order and is
+ * bit-identical from run to run.
+ *   An identity refit (the build's own positions) gives back the build's bytes, with two documented exceptions:
+ *   - signed zeros: the LBVH builder's leaf boxes use fminf / fmaxf, so where a box bound is a zero whose sign differs
+ *     between corners the refitted box may carry the other zero.  The boxes are equal as numbers.
+ *   - split trees: a refit writes UNCLIPPED leaf boxes (the record's own bound), where the build clipped each reference to
+ *     its grid cell.  Conservative and correct, but looser than the build's boxes.
+ *
+ * Status word (rt_refit_plan_layout.status, uint32, RT_REFIT_* flags), to be read after the stream has run.  The flags are
+ * sticky: rt_build_refit_plan clears them, every later rt_refit on the plan only adds to them.
+ *   RT_REFIT_BAD_TREE       the walk found something that is not a tree: a run reached twice (or two runs sharing a slot), a
+ *                           slot index at or beyond rt_nodes_bytes(n)/32, a box slot with count 0 or whose run has no
+ *                           non-NONE slot, a child type above 2, a record index at or beyond n, or a record whose ids are
+ *                           neither a single's nor a pair's.  The plan is unusable: rt_refit writes nothing.
+ *   RT_REFIT_PLAN_MISMATCH  rt_refit was given nodes_out, root, count or n other than the plan's.  Nothing is written.
+ *   RT_REFIT_PAIR_BROKEN    after the update a pair record's B no longer shares A's edge: B's corners on the edge named by
+ *                           rotations[1] differ from (v2, v1) of the rotated A, compared as the pairing test compares
+ *                           corners (float ==).  The record cannot represent B; boxes still bound both triangles.  Rebuild.
+ *
+ * plan: rt_refit_plan_bytes(n) bytes of device memory, 256-byte aligned, owned by the caller; no initialisation needed.
+ * Size: with S = rt_nodes_bytes(n) / 32 = 4 (n + 512) slots, 256 + 9 S bytes rounded up to three 256-byte aligned arrays --
+ * 36 bytes per triangle + about 18 KB.
+ * Argument errors, returned before any GPU work: RT_ERR_INVALID_ARGUMENT for a null input / plan / buffer, a plan not
+ * 256-byte aligned, triangles_in not 16-, triangles_out or nodes_out not 64-byte aligned, count > 7; RT_ERR_TOO_LARGE for
+ * n > RT_REFIT_MAX_TRIANGLES (every slot index must fit 29 bits with one value to spare).  n = 0: nothing runs. */
+#define RT_REFIT_MAX_TRIANGLES ((1u << 27) - 1024u)
+enum { RT_REFIT_BAD_TREE = 1, RT_REFIT_PLAN_MISMATCH = 2, RT_REFIT_PAIR_BROKEN = 4 };
+size_t rt_refit_plan_bytes(uint32_t num_triangles);
+typedef struct rt_refit_plan_layout {
+    size_t status;    /* uint32: RT_REFIT_* flags (the first word of a 256-byte header) */
+    size_t parents;   /* uint32[S]: run-first slot: parent slot : 29 | expected arrivals : 3; other reached slot: its offset */
+    size_t arrivals;  /* uint8[S]: arrivals so far at a run-first slot (0 between refits); bit 7: the slot is a reached leaf */
+    size_t leaves;    /* uint32[S]: the reached leaf slots (their number: header word 1) */
+    size_t total;     /* = rt_refit_plan_bytes(n) */
+} rt_refit_plan_layout;
+int rt_refit_plan_layout_get(uint32_t num_triangles, rt_refit_plan_layout* out);
+int rt_build_refit_plan(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
+int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
+
 /* static string for a return code */
 const char* rt_error_string(int code);
 
