@@ -418,3 +418,145 @@ def box_helpers(which: str):
     return (lambda v9: call("triangle_centre", [v9], 3), lambda v9: call("triangle_box", [v9], 6),
             lambda b6: call("box_centre", [b6], 3), lambda a6, b6: call("box_combine", [a6, b6], 6),
             lambda a6, b6: call("box_intersection", [a6, b6], 6, ret_int=True))
+
+
+# ---------------------------------------------------------------- the reference's own kernels, run on the CPU
+# oracle/_ref/libref_kernels.so: BottomUpBuilder.cu and Tracer.cu from the reference tree, #included by
+# oracle/ref_kernels_driver.cpp, which emulates each launch serially (TraceRays: rows on up to 16 threads).
+REF_KERNELS_PATH = os.path.join(_HERE, "_ref", "libref_kernels.so")
+_refk = None
+
+
+def ref_kernels_available() -> bool:
+    return os.path.exists(REF_KERNELS_PATH)
+
+
+def _refkernels():
+    global _refk
+    if _refk is None:
+        R = ctypes.CDLL(REF_KERNELS_PATH)
+        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+        R.ref_morton.argtypes = [vp, u32, vp, vp, vp]
+        R.ref_morton.restype = None
+        R.ref_morton_pairs.argtypes = [vp, u32, vp, vp, vp]
+        R.ref_morton_pairs.restype = u32
+        R.ref_hierarchy.argtypes = [vp, u32, vp, vp]
+        R.ref_hierarchy.restype = None
+        R.ref_triangles.argtypes = [vp, vp, vp, u32]
+        R.ref_triangles.restype = None
+        R.ref_aabbs.argtypes = [vp, vp, vp, vp, u32]
+        R.ref_aabbs.restype = None
+        R.ref_trace.argtypes = [vp, vp, u32, u32, vp, vp, u32, vp, u32, vp, u32, vp, ctypes.c_int, ctypes.c_int,
+                                ctypes.c_int, vp, vp]
+        R.ref_trace.restype = None
+        _refk = R
+    return _refk
+
+
+def _tris9(tris):
+    return np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 9)
+
+
+def ref_morton(tris: np.ndarray, aabb_ordered: np.ndarray):
+    """GenerateMortonCodes (BottomUpBuilder.cu:98-115): (codes, values) in input order."""
+    t = _tris9(tris)
+    n = t.shape[0]
+    codes, vals = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    _refkernels().ref_morton(_p(t), n, _p(np.ascontiguousarray(aabb_ordered, np.int32)), _p(codes), _p(vals))
+    return codes[:n], vals[:n]
+
+
+def ref_morton_pairs(tris: np.ndarray, aabb_ordered: np.ndarray):
+    """GenerateMortonCodesPairs (BottomUpBuilder.cu:117-164), threads in gid order: (codes, values) of the L leaves in
+    slot order.  values: first triangle's index, | 0x80000000 for a pair."""
+    t = _tris9(tris)
+    n = t.shape[0]
+    codes, vals = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    L = int(_refkernels().ref_morton_pairs(_p(t), n, _p(np.ascontiguousarray(aabb_ordered, np.int32)), _p(codes),
+                                           _p(vals)))
+    return codes[:L], vals[:L]
+
+
+def ref_hierarchy(sorted_codes: np.ndarray):
+    """GenerateHierarchy (BottomUpBuilder.cu:167-215) over L sorted codes: (nodes [2*max(L-1,1)], leaf_indices [L]).
+    Only the child / type / parent words are written; boxes and counts stay zero."""
+    c = np.ascontiguousarray(sorted_codes, np.uint32).copy()
+    L = c.shape[0]
+    nodes = np.zeros(2 * max(L - 1, 1), dtype=NODE)
+    leaf_idx = np.zeros(max(L, 1), np.uint32)
+    _refkernels().ref_hierarchy(_p(c), L, _p(nodes), _p(leaf_idx))
+    return nodes, leaf_idx[:L]
+
+
+def ref_triangles(sorted_indices: np.ndarray, tris: np.ndarray) -> np.ndarray:
+    """GenerateTriangles (BottomUpBuilder.cu:287-312).  The kernel copies an uninitialised local into a single leaf's
+    primitive ids, rotations and pad3, and into every leaf's pad3 (Q1): those bytes are indeterminate, not compared."""
+    t = _tris9(tris)
+    t1 = np.zeros((t.shape[0] + 1, 9), np.float32)     # the kernel reads the triangle after each leaf's first one
+    t1[:t.shape[0]] = t
+    s = np.ascontiguousarray(sorted_indices, np.uint32)
+    L = s.shape[0]
+    out = np.zeros(max(L, 1), TRIANGLE_PAIR)
+    _refkernels().ref_triangles(_p(s), _p(t1), _p(out), L)
+    return out[:L]
+
+
+def ref_aabbs(nodes: np.ndarray, leaf_indices: np.ndarray, sorted_indices: np.ndarray, leaves: np.ndarray) -> np.ndarray:
+    """GenerateAABBs (BottomUpBuilder.cu:217-285), zeroed locks, serial: returns a copy of nodes with boxes and counts."""
+    out = np.ascontiguousarray(nodes).copy()
+    li = np.ascontiguousarray(leaf_indices, np.uint32)
+    _refkernels().ref_aabbs(_p(out), _p(li), _p(np.ascontiguousarray(sorted_indices, np.uint32)),
+                            _p(np.ascontiguousarray(leaves)), li.shape[0])
+    return out
+
+
+def ref_build_lbvh(tris: np.ndarray, pairs: bool = False, aabb_ordered=None) -> dict:
+    """RunBottomUpBuild through the reference's kernels: Morton (plain or pairs) -> stable sort by key (the radix sort's
+    contract; RadixSort.cu itself is not emulated) -> GenerateHierarchy -> GenerateTriangles -> GenerateAABBs.  The
+    scene box is the oracle's (ora_scene_aabb) unless given.  Same dict shape as build_bvh / build_pairs.
+    With pairs=True the leaf order before the sort is the serial arrival order (see the driver)."""
+    t = _tris9(tris)
+    n = t.shape[0]
+    aabb = scene_aabb(t) if aabb_ordered is None else np.ascontiguousarray(aabb_ordered, np.int32)
+    codes, vals = (ref_morton_pairs if pairs else ref_morton)(t, aabb)
+    order = np.argsort(codes, kind="stable")
+    sc, sv = codes[order], vals[order]
+    L = sc.shape[0]
+    nodes, leaf_idx = ref_hierarchy(sc)
+    leaves = ref_triangles(sv, t)
+    if L == 1:
+        # GenerateHierarchy writes nothing for one leaf; GenerateAABBs then reads leaf_indices[0] = 0 (the caller's
+        # zeroed buffer) and stops at once
+        nodes = nodes[:2]
+    nodes = ref_aabbs(nodes, leaf_idx, sv, leaves)
+    out = dict(nodes=nodes, leaves=leaves, codes=sc, indices=sv, leaf_indices=leaf_idx, aabb=aabb, n=n, L=L)
+    return out
+
+
+def ref_trace(leaves, nodes, root, count, camera, w, h, *, render_type=0, attributes=None, materials=None,
+              light=(0, 0, 0), textures=None):
+    """TraceRays (Tracer.cu:471-595) of the reference, run on the CPU over a w x h frame.  Returns (rgba8 [h, w, 4],
+    counters [box_tests, tri_tests]): box_tests is the kernel's own counter, tri_tests the sum of its per-ray
+    TraceStats.tri_tests (read by the driver when the kernel hands its record to atomicAdd).
+    TraceRays reads attributes[primitive_id] and materials[material_id] for every pixel, whatever the render type:
+    without attributes / materials, zeroed attributes for every primitive id of the leaves and one default material
+    stand in (render types 0-2 do not use them)."""
+    lv = np.ascontiguousarray(leaves)
+    if attributes is None:
+        k = 1 if lv.shape[0] == 0 else int(max(lv["primitive_id_0"].max(), lv["primitive_id_1"].max())) + 1
+        attributes = np.zeros(k, np.dtype([("b", "u1", 72)]))
+    at = np.ascontiguousarray(attributes)
+    if materials is None:
+        materials = np.zeros(1, np.dtype([("f", "<f4", 10), ("i", "<i4", 3)]))
+        materials["i"] = -1
+    mt = np.ascontiguousarray(materials)
+    assert at.dtype.itemsize == 72 and mt.dtype.itemsize == 52
+    table, _keep = _texture_table(textures) if textures else (None, None)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    tests = np.zeros(2, np.uint64)
+    lt = np.asarray(light, np.float32)
+    _refkernels().ref_trace(_p(lv), _p(np.ascontiguousarray(nodes)), root, count, _p(np.ascontiguousarray(camera)),
+                            _p(at), at.shape[0], _p(mt), mt.shape[0],
+                            None if table is None else ctypes.cast(table, ctypes.c_void_p), len(textures or ()),
+                            _p(lt), w, h, render_type, _p(rgba), _p(tests))
+    return rgba, tests

@@ -11,10 +11,11 @@
  * correctly rounded '/' and sqrtf -- the same operation order as the reference's device code
  * without FMA contraction and with rsqrtf(x) := 1.0f/sqrtf(x).
  *
- * PINNING STATUS: the reference ships no tests, fixtures or golden vectors
- * and its CUDA kernels cannot be built in this image (no nvcc / CUDA device runtime), so the
- * arithmetic of Morton codes / sort / traversal is "parity unpinned" against reference-held
- * vectors.  What IS pinned: (1) the reference's own structural check -- VerifyHierarchy and
+ * PINNING STATUS: the reference ships no tests, fixtures or golden vectors.
+ * Its LBVH kernels (BottomUpBuilder.cu) and TraceRays (Tracer.cu) are compiled from the reference tree
+ * and run on the CPU (oracle/_ref/libref_kernels.so): Morton codes, the radix
+ * tree, leaf records, boxes and traversal of this oracle are held against them exactly
+ * (tests/test_ref_kernels_cpu.py).  Also pinned: (1) the reference's own structural check -- VerifyHierarchy and
  * CountNodes from Utilities.cpp compiled unmodified into oracle/_ref -- is run on the oracle's
  * (and the GPU's) Node arrays, for the bottom-up, hybrid, pairs and SAH trees alike; Camera.cu
  * (host functions only) and Arguments.cpp are compiled the same way and pin the camera basis every
