@@ -6,7 +6,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 (``BuildInput``, ``BuMemoryRequirements``, ``RunBottomUpBuild``, ``RadixSort``, ``Trace``; reference
 ``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``), plus ray queries over any built
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
-vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame).  torch is used for device
+vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), and instancing (``accel_table``,
+``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
 
@@ -47,6 +48,12 @@ kClosestHit, kAnyHit = 0, 1
 kRaysRowMajor, kRaysTiled = 0, 1
 # refit status flags (rt_refit_plan_layout.status)
 RT_REFIT_BAD_TREE, RT_REFIT_PLAN_MISMATCH, RT_REFIT_PAIR_BROKEN = 1, 2, 4
+# instancing (rt_prepare_instances / rt_intersect_rays_instanced)
+INSTANCE = np.dtype([("object_to_world", "<f4", (3, 4)), ("blas", "<u4"), ("pad", "<u4", 3)])                # 64 B
+INSTANCE_RECORD = np.dtype([("world_to_object", "<f4", (3, 4)), ("blas", "<u4"), ("flags", "<u4"), ("spare", "<u4", 2)])
+ACCEL = np.dtype([("triangles", "<u8"), ("nodes", "<u8"), ("root", "<u4"), ("count", "<u4")])                # 24 B
+assert INSTANCE.itemsize == 64 and INSTANCE_RECORD.itemsize == 64 and ACCEL.itemsize == 24
+RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -114,7 +121,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_calculate_scene_aabb", "rt_generate_morton_codes", "rt_radix_sort_scratch_bytes",
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
-           "rt_build_refit_plan", "rt_refit", "rt_error_string", "rt_version_string"]
+           "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_error_string",
+           "rt_version_string"]
 
 _lib = None
 
@@ -177,6 +185,10 @@ def lib() -> ctypes.CDLL:
     L.rt_build_refit_plan.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
     L.rt_refit.restype = i32
     L.rt_refit.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
+    L.rt_prepare_instances.restype = i32
+    L.rt_prepare_instances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
+    L.rt_intersect_rays_instanced.restype = i32
+    L.rt_intersect_rays_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -464,6 +476,48 @@ def refit_status(plan, num_triangles: int) -> int:
     """The plan's RT_REFIT_* flags (copies the status word back: waits for the work queued before it on the current stream).
     Sticky: BuildRefitPlan clears them, every Refit only adds to them."""
     return int(to_host(plan, np.uint32, 1, refit_plan_layout(num_triangles).status)[0])
+
+
+def accel_table(trees, device="cuda"):
+    """The device BLAS table of instancing: one rt_accel per (triangles, nodes, root, count) of `trees` (e.g. a BuildInput's
+    triangles_out / nodes_out and its trace root), as an ACCEL-array device buffer.  The caller keeps the trees alive."""
+    tab = np.zeros(len(trees), ACCEL)
+    for k, (tris, nodes, root, count) in enumerate(trees):
+        tab[k] = (_ptr(tris), _ptr(nodes), int(root), int(count))
+    return to_device(tab, device)
+
+
+def PrepareInstances(instances, num_instances: int, blas_table, num_blas: int, proxies, records, status, stream=None) -> None:
+    """rt_prepare_instances: `instances` (INSTANCE records, device), the BLAS table (accel_table) -> `proxies` (num_instances
+    TRIANGLE records: the TLAS build input, e.g. a BuildInput's triangles_in), `records` (INSTANCE_RECORD, the query's input)
+    and `status` (a device uint32 the call clears; RT_INSTANCE_* flags, see instance_status).  Asynchronous on `stream`."""
+    _check(lib().rt_prepare_instances(_ptr(instances), int(num_instances), _ptr(blas_table), int(num_blas), _ptr(proxies),
+                                      _ptr(records), _ptr(status), _stream_ptr(stream)), "rt_prepare_instances")
+
+
+def instance_status(status) -> int:
+    """The RT_INSTANCE_* flags of the last PrepareInstances (copies the word back: waits for the work queued before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
+
+
+def IntersectRaysInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                           num_blas: int, rays, hits, instance_ids, *, any_hit: bool = False, num_primitives: int = 0,
+                           counters=None, stream=None) -> None:
+    """rt_intersect_rays_instanced: IntersectRays through a TLAS (built over PrepareInstances's proxies; root / count of its
+    root) and the instances' BLASes.  `instance_ids` (>= 4 N bytes, e.g. int32 [N]) gets the instance of each hit or MISS;
+    hits[i] carries the BLAS's own primitive_id and (u, v) and the world-space t.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits / instance_ids contiguous buffers")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records and instance_ids {n} words")
+    if n == 0:
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                             int(num_blas), _ptr(rays), _ptr(hits), _ptr(instance_ids), n,
+                                             kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
+                                             _stream_ptr(stream)), "rt_intersect_rays_instanced")
 
 
 def version() -> str:

@@ -332,6 +332,50 @@ int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* p
     return hip_rc(launch_refit(*input, root, count, plan, static_cast<hipStream_t>(stream)));
 }
 
+static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                         rt_triangle* proxies, rt_instance_record* records, uint32_t* status, void* stream)
+{
+    if (!status || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances) {
+        if (!instances || !proxies || !records || !blas_table || num_blas == 0) return RT_ERR_INVALID_ARGUMENT;
+        if (misaligned(instances, 16) || misaligned(proxies, 16) || misaligned(records, 16) || misaligned(blas_table, 8))
+            return RT_ERR_INVALID_ARGUMENT;
+    }
+    return hip_rc(launch_prepare_instances(instances, num_instances, blas_table, num_blas, proxies, records, status,
+                                           static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                uint64_t* counters, void* stream)
+{
+    if (!tlas || !rays || !hits || !instance_ids || tlas->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (tlas->count && (!tlas->nodes || !tlas->triangles)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
+        misaligned(blas_table, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    InstanceQuery q;
+    q.tlas = *tlas;
+    q.records = records;
+    q.num_instances = num_instances;
+    q.blas_table = blas_table;
+    q.num_blas = num_blas;
+    q.rays = rays;
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    q.num_rays = num_rays;
+    q.any_hit = mode == RT_RAY_ANY_HIT;
+    q.num_primitives = num_primitives;
+    q.counters = counters;
+    return hip_rc(launch_instance_query(q, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -353,7 +397,9 @@ const char* rt_version_string(void)
            "trace: wave64 8x8 tiles, two-phase schedule, LDS stack 16, XCD chunks of 8 workgroups, pair prefetch from 8M primitives, counters through 16-row slots | "
            "rays: caller rays through the same traversal, 64 consecutive rays per wave, closest / any hit, 16-byte records, camera rays row-major or 8x8-tiled | "
            "refit: top-down plan walk (one wide launch per level + one-workgroup tail, one CAS per run), one thread per leaf slot "
-           "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max";
+           "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max | "
+           "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "
+           "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit";
 }
 
 }  // extern "C"

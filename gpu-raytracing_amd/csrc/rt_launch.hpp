@@ -201,4 +201,24 @@ uint32_t refit_plan_wide_levels(uint32_t n);   // wide walk launches of a plan b
 hipError_t launch_refit_plan(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
 hipError_t launch_refit(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
 
+// instances.hip: rt_prepare_instances / rt_intersect_rays_instanced after their argument checks (the query: num_rays > 0)
+hipError_t launch_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
+                                    uint32_t num_blas, rt_triangle* proxies, rt_instance_record* records, uint32_t* status,
+                                    hipStream_t st);
+struct InstanceQuery {
+    rt_accel tlas;
+    const rt_instance_record* records;
+    uint32_t num_instances;
+    const rt_accel* blas_table;
+    uint32_t num_blas;
+    const rt_ray* rays;
+    rt_hit* hits;
+    uint32_t* instance_ids;
+    uint32_t num_rays;
+    bool any_hit;
+    uint32_t num_primitives;
+    uint64_t* counters;
+};
+hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st);
+
 }  // namespace rt

@@ -318,6 +318,74 @@ int rt_refit_plan_layout_get(uint32_t num_triangles, rt_refit_plan_layout* out);
 int rt_build_refit_plan(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
 int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
 
+/* ---- instancing (no reference counterpart: the reference traces one mesh, main.cu:125-192).  A scene of placed copies of
+ * a few meshes: every mesh has its own built tree (a bottom-level tree, BLAS: any tree rt_trace takes -- LBVH, pairs, hybrid,
+ * SAH, splits, mixed kinds in one table), and a small top-level tree (TLAS) is built over the placed copies.
+ *
+ * rt_instance (caller input, 64 bytes): object_to_world, row-major 3x4: world = M[:, :3] * p + M[:, 3]; blas indexes the
+ * BLAS table (a DEVICE array of rt_accel).
+ * rt_instance_record (64 bytes, written by rt_prepare_instances, read by the query): world_to_object, row-major 3x4 (the
+ * inverse of object_to_world, computed in double and rounded to float), blas, flags (the instance's RT_INSTANCE_* flags;
+ * non-zero: the query never enters the instance), two spare words (0).
+ *
+ * rt_prepare_instances, one launch after a clear of *status, one thread per instance:
+ *   - the object box: the ordered min / max over the non-NONE slots of the BLAS's root run [root, root + count);
+ *   - its 8 corners go through object_to_world in float32, in the order ((m0*x + m1*y) + m2*z) + m3 per row;
+ *   - lo / hi = min / max of the transformed corners, then every bound moves outward by pad = 2^-12 * E, E = the largest
+ *     |lo| or |hi| over the three axes (lo - pad, hi + pad in float32): a box conservative against the rounding of the
+ *     object-space ray (below) for rays that start within a few box magnitudes of the instance;
+ *   - proxies[i] = {v0 = lo, v1 = hi, v2 = lo*0.5f + hi*0.5f}: its box is exactly [lo, hi] and its centroid lies inside it,
+ *     so it is a valid input for every builder (Morton codes, SAH centroids);
+ *   - records[i] as above.
+ * Status flags (OR over the instances, written to *status, a device uint32 the call clears; read it after the stream ran):
+ *   RT_INSTANCE_BAD_BLAS   blas >= num_blas, or the table entry has count 0 or > 7, a null node or leaf pointer, or no
+ *                          non-NONE slot in its root run;
+ *   RT_INSTANCE_SINGULAR   object_to_world has a non-finite entry, its 3x3 part has determinant 0 (in double), or an entry of
+ *                          world_to_object does not fit a float.
+ *   A flagged instance gets a point proxy at the origin (v0 = v1 = v2 = 0) and its flags in its record.
+ *
+ * TLAS build: rt_run_bottom_up_build (plain or hybrid) or rt_run_sah_build over `proxies` (num_triangles = num_instances) with
+ * enable_pairs = enable_splits = 0.  A TLAS leaf's primitive_id_0 is then the instance index.  No other builder is needed.
+ *
+ * rt_intersect_rays_instanced: rays, hits, mode, num_primitives (the scene-size hint: instanced triangles in total), counters,
+ * alignment and the NaN / empty-range rules are rt_intersect_rays's.  Per ray:
+ *   instance_ids[i]  the instance of the hit, or RT_MISS (a DEVICE uint32 array, 4-byte aligned);
+ *   hits[i]          primitive_id, u, v of the BLAS's own triangles (the caller's corners, as rt_intersect_rays); t is the
+ *                    world-space hit distance in units of |dir|.  An affine map preserves t, so tmin / tmax apply unchanged
+ *                    in object space and one tmax is carried across instances.
+ *   The world ray is tested against the TLAS; entering an instance loads its record and its rt_accel and transforms the ray:
+ *   o' = W*(o, 1), d' = W3x3*d, each row ((w0*x + w1*y) + w2*z) [+ w3] in float32, 1/d' by IEEE division.  On leaving the
+ *   instance the world ray is reloaded from rays[i] (never transformed back): the original bits.  An instance is never
+ *   entered when its TLAS leaf's primitive_id_0 >= num_instances, its record's flags are non-zero, its blas >= num_blas, or
+ *   the table entry's count is 0 or > 7.  mode RT_RAY_ANY_HIT ends the ray at its first accepted triangle in any instance.
+ *   Counters: [0] box tests of both levels together, [1] triangle tests, [2] / [3] wave steps, as rt_intersect_rays.
+ *   Stack: ONE 64-entry stack serves both levels (the BLAS's entries sit above the TLAS's); pushes beyond 64 are dropped, as in
+ *   rt_intersect_rays, so a BLAS entered at depth k has 64 - k entries.  Identity instance over a tree: the same hit records and
+ *   triangle tests as rt_intersect_rays on that tree for rays without -0 components (a transformed -0 may come out +0).
+ * Both calls are asynchronous (no host copy, no synchronisation: hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): null pointers (blas_table may be null only when
+ * num_instances = 0), instances / records / proxies / rays / hits not 16-byte aligned, blas_table not 8-, status / instance_ids
+ * not 4-byte aligned, tlas->count > 7, a bad mode, num_instances > 0 with num_blas = 0.  num_instances = 0 (prepare) or num_rays = 0 (query):
+ * nothing runs, except that prepare still clears *status. */
+typedef struct rt_instance {
+    float    object_to_world[12];   /* row-major 3x4 */
+    uint32_t blas;                  /* index into the BLAS table */
+    uint32_t pad[3];
+} rt_instance;
+typedef struct rt_instance_record {
+    float    world_to_object[12];   /* row-major 3x4 */
+    uint32_t blas;
+    uint32_t flags;                 /* RT_INSTANCE_* of the instance; non-zero: never entered */
+    uint32_t spare[2];
+} rt_instance_record;
+enum { RT_INSTANCE_BAD_BLAS = 1, RT_INSTANCE_SINGULAR = 2 };
+int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                         rt_triangle* proxies, rt_instance_record* records, uint32_t* status, void* stream);
+int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                uint64_t* counters, void* stream);
+
 /* static string for a return code */
 const char* rt_error_string(int code);
 
