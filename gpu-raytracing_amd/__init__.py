@@ -6,8 +6,9 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 (``BuildInput``, ``BuMemoryRequirements``, ``RunBottomUpBuild``, ``RadixSort``, ``Trace``; reference
 ``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``), plus ray queries over any built
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
-vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), and instancing (``accel_table``,
-``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees).  torch is used for device
+vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
+``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
+(``ClosestPoints``: the nearest triangle to each point, through any built tree).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
 
@@ -54,6 +55,11 @@ INSTANCE_RECORD = np.dtype([("world_to_object", "<f4", (3, 4)), ("blas", "<u4"),
 ACCEL = np.dtype([("triangles", "<u8"), ("nodes", "<u8"), ("root", "<u4"), ("count", "<u4")])                # 24 B
 assert INSTANCE.itemsize == 64 and INSTANCE_RECORD.itemsize == 64 and ACCEL.itemsize == 24
 RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
+# closest-point queries (rt_closest_points)
+POINT_QUERY = np.dtype([("p", "<f4", 3), ("dist2_max", "<f4")])                                            # 16 B
+POINT_HIT = np.dtype([("dist2", "<f4"), ("primitive_id", "<u4"), ("u", "<f4"), ("v", "<f4")])              # 16 B
+assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 16
+RT_POINT_STACK_OVERFLOW = 1
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -121,8 +127,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_calculate_scene_aabb", "rt_generate_morton_codes", "rt_radix_sort_scratch_bytes",
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
-           "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_error_string",
-           "rt_version_string"]
+           "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
+           "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -189,6 +195,8 @@ def lib() -> ctypes.CDLL:
     L.rt_prepare_instances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     L.rt_intersect_rays_instanced.restype = i32
     L.rt_intersect_rays_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32, vp, vp]
+    L.rt_closest_points.restype = i32
+    L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -518,6 +526,30 @@ def IntersectRaysInstanced(tlas_triangles, tlas_nodes, root: int, count: int, re
                                              int(num_blas), _ptr(rays), _ptr(hits), _ptr(instance_ids), n,
                                              kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
                                              _stream_ptr(stream)), "rt_intersect_rays_instanced")
+
+
+def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, counters=None, status=None, stream=None) -> None:
+    """rt_closest_points: one POINT_HIT record per POINT_QUERY record of `queries` (a contiguous device tensor of 16-byte
+    records (p, dist2_max), e.g. float32 [N, 4]) into `hits` (>= 16 N bytes, e.g. float32 [N, 4]; view it as int32 for
+    primitive_id).  Any tree Trace() takes (`triangles` / `nodes` as for Trace, root / count of its root node).  The record is
+    the lexicographic minimum of (dist2, primitive_id) over the triangles within dist2_max; a miss is {+inf, MISS, 0, 0}.
+    counters: optional int64[4] device tensor ([0] box tests, [1] triangle tests).  status: optional device uint32 the call
+    ORs RT_POINT_STACK_OVERFLOW into (the caller clears it; see point_status).  Asynchronous on `stream`."""
+    if not queries.is_contiguous() or not hits.is_contiguous() or _nbytes(queries) % 16:
+        raise ValueError("queries must be a contiguous device buffer of 16-byte records, hits a contiguous device buffer")
+    n = _nbytes(queries) // 16
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_closest_points(ctypes.byref(a), _ptr(queries), _ptr(hits), n, _ptr(counters), _ptr(status),
+                                   _stream_ptr(stream)), "rt_closest_points")
+
+
+def point_status(status) -> int:
+    """The RT_POINT_* flags ClosestPoints ORed into `status` (copies the word back: waits for the work queued before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
 
 
 def version() -> str:

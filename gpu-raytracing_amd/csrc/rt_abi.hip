@@ -376,6 +376,16 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
     return hip_rc(launch_instance_query(q, static_cast<hipStream_t>(stream)));
 }
 
+int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
+                      uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!as || !queries || !hits || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (misaligned(queries, 16) || misaligned(hits, 16) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_point_query(*as, queries, hits, num_queries, counters, status, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -399,7 +409,9 @@ const char* rt_version_string(void)
            "refit: top-down plan walk (one wide launch per level + one-workgroup tail, one CAS per run), one thread per leaf slot "
            "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max | "
            "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "
-           "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit";
+           "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit | "
+           "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
+           "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id)";
 }
 
 }  // extern "C"

@@ -221,4 +221,8 @@ struct InstanceQuery {
 };
 hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st);
 
+// point_query.hip: rt_closest_points after its argument checks (num_queries > 0)
+hipError_t launch_point_query(const rt_accel& as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
+                              uint64_t* counters, uint32_t* status, hipStream_t st);
+
 }  // namespace rt

@@ -386,6 +386,73 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
                                 uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
                                 uint64_t* counters, void* stream);
 
+/* ---- closest-point queries (no reference counterpart).  For each caller point: which triangle is nearest, where on it, and
+ * how far away -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and
+ * every query misses).
+ *
+ * rt_point_query (16 bytes): p, dist2_max -- a squared search radius, +inf allowed.  A query with a non-finite component of p,
+ * a NaN dist2_max or a negative dist2_max is not traced: its record is a miss and no tests are counted for it.
+ * rt_point_hit (16 bytes): dist2, primitive_id (the caller's triangle index; a split reference reports its original triangle),
+ * u, v (the weights of the caller's corners v1 and v2 at the closest point, from d2 below).  A miss is {+inf, RT_MISS, 0, 0}.
+ *
+ * d2(p, v0, v1, v2), float32, evaluated on the caller's corners in the caller's order (pair leaves: the stored corners are put
+ * back through rt_triangle_pair.rotations first, A with rotations[0], B = (v2, v1, v3) with rotations[1]; r = 1: caller
+ * corners = stored (s1, s2, s0), r = 2: (s2, s0, s1), else as stored).  With a = v0, b = v1, c = v2, every subtraction
+ * componentwise, dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z, guard(n, d) = (d > 0 ? n / d : 0) (IEEE division) and
+ * clamp01(t) = min(max(t, 0), 1) by selects (NaN -> 0):
+ *   1. closest point q, Ericson's ClosestPtPointTriangle (Real-Time Collision Detection 5.1.5), first region that holds:
+ *        ab = b - a, ac = c - a, ap = p - a, d1 = dot(ab, ap), d2 = dot(ac, ap)
+ *        d1 <= 0 && d2 <= 0                      q = a                       (u, v) = (0, 0)
+ *        bp = p - b, d3 = dot(ab, bp), d4 = dot(ac, bp)
+ *        d3 >= 0 && d4 <= d3                     q = b                       (1, 0)
+ *        vc = d1*d4 - d3*d2, t_ab = clamp01(guard(d1, d1 - d3))
+ *        vc <= 0 && d1 >= 0 && d3 <= 0           q = a + t_ab*ab             (t_ab, 0)
+ *        cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp)
+ *        d6 >= 0 && d5 <= d6                     q = c                       (0, 1)
+ *        vb = d5*d2 - d1*d6, t_ac = clamp01(guard(d2, d2 - d6))
+ *        vb <= 0 && d2 >= 0 && d6 <= 0           q = a + t_ac*ac             (0, t_ac)
+ *        va = d3*d6 - d5*d4, e43 = d4 - d3, e56 = d5 - d6, t_bc = clamp01(guard(e43, e43 + e56)), bc = c - b
+ *        va <= 0 && e43 >= 0 && e56 >= 0         q = b + t_bc*bc             (1 - t_bc, t_bc)
+ *        s = (va + vb) + vc, s > 0               fv = vb / s, fw = vc / s, q = (a + ab*fv) + ac*fw     (fv, fw)
+ *        otherwise (a degenerate face)           the nearest of the three edge points a + t_ab*ab, a + t_ac*ac, b + t_bc*bc
+ *                                                by the float dist2 of steps 2-3 (ties: AB, then AC), with their weights;
+ *   2. clamp: q = fminf(fmaxf(q, lo), hi) componentwise, lo / hi = fminf / fmaxf of the three corners (the vertex box);
+ *   3. dist2 = (dx*dx + dy*dy) + dz*dz, d = p - q.  u, v are returned + 0 (a -0 becomes +0).
+ * The clamp is a projection onto a convex set that holds the triangle, so it only moves q toward the true closest point.  It
+ * also makes pruning exact: a slot box that contains the vertex box gives boxdist2 = (gx*gx + gy*gy) + gz*gz, g = max(lo - p,
+ * p - hi, 0) per axis, and since float subtraction, squaring and addition are monotone, dist2 >= boxdist2 holds in float32
+ * exactly, for any input (a NaN from overflow still clamps into the box).
+ *
+ * Result: the lexicographic minimum of (dist2, primitive_id) over every triangle with dist2 <= dist2_max (ties on dist2 go to
+ * the lower id; the search starts from (dist2_max, RT_MISS), so a triangle exactly at the radius is accepted).  A slot or a
+ * popped entry is skipped only when boxdist2 > best (never on equality).  The result does not depend on the visiting order:
+ *   - exact (bit for bit the brute force over the caller's triangles) on every tree whose slot boxes contain the vertex boxes
+ *     below them: LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs, and every refitted tree (refit writes unclipped boxes);
+ *   - spatial-split trees (rt_run_sah_build with enable_splits) clip leaf boxes to grid cells, so a triangle may be pruned
+ *     through a reference whose clipped box is farther than the triangle.  There dist2 is still d2(p, tri[primitive_id]) bit
+ *     for bit, and sqrt(dist2) exceeds the brute-force minimum by at most 2^-20 * M, M = the largest coordinate magnitude of
+ *     p and the scene box.  Refitting a split tree restores exactness.
+ * Range: with coordinate differences beyond about 2^31 Ericson's products (degree 4) overflow; results there stay
+ * deterministic and equal to the restatement above, but are not accurate.
+ *
+ * rt_closest_points: hits[i] for queries[i], i < num_queries; hits[i >= num_queries] are not written.  queries / hits:
+ * 16-byte aligned device arrays.  counters: optional device uint64[4], rt_intersect_rays's layout: [0] += box tests (non-NONE
+ * slots examined), [1] += triangle tests (leaf records visited); [2] / [3] are not touched (no wave phases); one LDS
+ * reduction + 2 device atomics per workgroup of 256 queries.  status: optional device uint32 the call ORs flags into (the
+ * caller clears it).  Stack: 64 pending entries per query; a push beyond them is dropped.  A traversal that dropped a push is
+ * run again from the root with the best record so far (which prunes everything farther), at most twice; a traversal that
+ * drops nothing makes the record exact.  RT_POINT_STACK_OVERFLOW: the last traversal of a query still dropped a push -- its
+ * record is an exact (d2, id) of a real triangle but may not be the nearest.  Asynchronous (no host copy, no synchronisation:
+ * hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / queries / hits, a tree with count > 0
+ * and a null node or leaf pointer, count > 7, queries or hits not 16-byte aligned, status not 4-byte aligned.
+ * num_queries = 0: nothing runs. */
+typedef struct rt_point_query { rt_float3 p; float dist2_max; } rt_point_query;
+typedef struct rt_point_hit { float dist2; uint32_t primitive_id; float u, v; } rt_point_hit;
+enum { RT_POINT_STACK_OVERFLOW = 1 };
+int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
+                      uint64_t* counters, uint32_t* status, void* stream);
+
 /* static string for a return code */
 const char* rt_error_string(int code);
 
