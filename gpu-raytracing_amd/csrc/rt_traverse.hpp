@@ -29,6 +29,31 @@ constexpr int kTraceWaves = RT_TRACE_WAVES;   // waves (8x8 tiles) per workgroup
 #define RT_TRACE_PF_WAVES 5    // waves per SIMD of the pair-prefetch (PF) instantiations
 #endif
 
+// Wave-shared pairs, an EXPERIMENT ARM of the non-PF instantiations (csrc/Makefile librt_amd_exp.so, -DRT_TRACE_UNIFORM_MAX=1|2|4):
+// when the stepping lanes of a box step sit on at most kUniformMax distinct pairs, each pair is fetched ONCE per wave through the
+// scalar path (wave-uniform loads into SGPRs) instead of 4 vector requests per lane: box_step_wave / box_step_shared below.
+// Shipped: 0, every step takes the vector path -- the best arm (1, sticky) is +0.9 % on the 1M LBVH frame and -3 % on the SAH
+// tree, 2 and 4 lose everywhere (profiles/r05_trace_fetch_arms.txt).
+#ifndef RT_TRACE_UNIFORM_MAX
+#define RT_TRACE_UNIFORM_MAX 0
+#endif
+constexpr int kUniformMax = RT_TRACE_UNIFORM_MAX;
+// 1: the 64 rays of a tile share their path from the root down and rarely meet again once they have parted, so the first vote
+// of a traversal whose last step finds more than kUniformMax pairs ends the looking: later steps pay nothing for it.  0: every
+// step looks.
+#ifndef RT_TRACE_UNIFORM_STICKY
+#define RT_TRACE_UNIFORM_STICKY 1
+#endif
+constexpr bool kUniformSticky = RT_TRACE_UNIFORM_STICKY != 0;
+// 1: a scheduling barrier behind the four loads of a pair (box_step)
+#ifndef RT_TRACE_PAIR_BARRIER
+#define RT_TRACE_PAIR_BARRIER 0
+#endif
+// the leaf phase's four 16-byte loads stay four 16-byte requests (0: the compiler narrows them to the components it uses)
+#ifndef RT_TRACE_LEAF_WIDE
+#define RT_TRACE_LEAF_WIDE 1
+#endif
+
 // the wave runs a box step while  stepping * park_den >= parked * park_num  (else one leaf phase)
 constexpr int kParkNum = 8, kParkDen = 1;   // (round-2 sweep under the chunked XCD order, tools/sweep_park.sh: 4..8 equal on the 1080p LBVH frame; 4 is +5 % on the SAH tree but -4 % on the 4K x 16 spp frame)
 
@@ -180,22 +205,13 @@ __device__ __forceinline__ void prefetch_pair(const Params& p, Trav& t)
     }
 }
 
-// One box step of a lane (Tracer.cu:323-352 for one pair): both slots of the current pair are loaded and both slabs
-// computed before the ordered tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.
+// The tests of one box step on a fetched pair (Tracer.cu:323-352 for one pair): both slabs are computed before the ordered
+// tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.  `two`: the pair has a second slot
+// (else a1 / b1 repeat the first).
 template <bool PF, class Params>
-__device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
+__device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0,
+                                            const uint4& a1, const uint4& b1)
 {
-    const uint32_t cnt = t.cur >> 29;
-    const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
-#ifdef RT_EXP_BOX_PAD   // experiment arm (csrc/Makefile librt_amd_exp.so): N extra VALU instructions per box step -- which pipe bounds the kernel?
-#pragma unroll
-    for (int q = 0; q < RT_EXP_BOX_PAD; q++) asm volatile("v_mov_b32 %0, %0" : "+v"(t.box_tests));
-#endif
-    const bool two = cnt > 1;
-    const int o1 = two ? 2 : 0;  // all four loads issue together; a lone slot is simply read twice
-    uint4 a0, b0, a1, b1;
-    if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
-    else { a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1]; }
     float f0, k0;
     slab(a0, b0, r, f0, k0);
     slab(a1, b1, r, t.f1, t.k1);
@@ -213,6 +229,80 @@ __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
         t.second_slot(r.tmin, r.tmax);
         if (t.phase == PH_STEP) { t.advance(); prefetch_pair<PF>(p, t); }
     }
+}
+
+// One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
+template <bool PF, class Params>
+__device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
+{
+    const uint32_t cnt = t.cur >> 29;
+    const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
+#ifdef RT_EXP_BOX_PAD   // experiment arm (csrc/Makefile librt_amd_exp.so): N extra VALU instructions per box step -- which pipe bounds the kernel?
+#pragma unroll
+    for (int q = 0; q < RT_EXP_BOX_PAD; q++) asm volatile("v_mov_b32 %0, %0" : "+v"(t.box_tests));
+#endif
+    const bool two = cnt > 1;
+    const int o1 = two ? 2 : 0;  // all four loads issue together; a lone slot is simply read twice
+    uint4 a0, b0, a1, b1;
+    if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
+    else {
+        a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1];
+#if RT_TRACE_PAIR_BARRIER   // nothing is scheduled across: the first slab's arithmetic cannot slip between the second and third load
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+    box_step_on<PF>(p, r, t, two, a0, b0, a1, b1);
+}
+
+// The same step for the lanes that sit on the pair `c` (packed like Trav::cur), c WAVE-UNIFORM: the pair's 64 bytes are read
+// once per wave through the constant address space -- scalar loads into SGPRs, no vector-memory request -- and every such lane
+// runs the unchanged tests on them.  The tree is read-only for the whole launch, which is what that address space asks.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) u32x4* const_u4_ptr;
+template <class Params>
+__device__ __forceinline__ void box_step_shared(const Params& p, const Ray& r, Trav& t, uint32_t c)
+{
+    // (readfirstlane: every lane here has cur == c, and the compiler knows it -- without it the address is formed from the
+    // lane's own cur again and the loads are vector loads)
+    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+    const const_u4_ptr np = (const_u4_ptr)(uintptr_t)(p.nodes + (c & kIndexMask));
+    const bool two = (c >> 29) > 1;
+    const int o1 = two ? 2 : 0;
+    const u32x4 a0 = np[0], b0 = np[1], a1 = np[o1], b1 = np[o1 + 1];
+    box_step_on<false>(p, r, t, two, make_uint4(a0.x, a0.y, a0.z, a0.w), make_uint4(b0.x, b0.y, b0.z, b0.w),
+                       make_uint4(a1.x, a1.y, a1.z, a1.w), make_uint4(b1.x, b1.y, b1.z, b1.w));
+}
+
+// One box step of the wave, `st` = ballot(phase == PH_STEP) != 0.  Up to kUniformMax distinct pairs are peeled off the stepping
+// lanes (the first stepping lane's cur, the lanes that share it, the next lane left ...); if that covers them all, each pair
+// takes box_step_shared (returns true), otherwise every lane takes box_step.  Any lane in PH_STEP whose cur is c may step on
+// pair c at any time: only the interleaving across lanes differs between the two paths, a lane's own sequence of tests does not.
+template <bool PF, class Params>
+__device__ __forceinline__ bool box_step_wave(const Params& p, const Ray& r, Trav& t, uint64_t st)
+{
+    if constexpr (!PF && kUniformMax > 0) {
+        constexpr int K = kUniformMax > 0 ? kUniformMax : 1;   // (no zero-length arrays in the arm that compiles this out)
+        uint32_t cs[K];
+        uint64_t ms[K];
+        uint64_t rest = st;
+#pragma unroll
+        for (int k = 0; k < kUniformMax; k++) {
+            cs[k] = 0; ms[k] = 0;
+            if (rest) {
+                cs[k] = (uint32_t)__builtin_amdgcn_readlane((int)t.cur, __ffsll((unsigned long long)rest) - 1);
+                ms[k] = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP && t.cur == cs[k]);
+                rest &= ~ms[k];
+            }
+        }
+        if (rest == 0) {
+#pragma unroll
+            for (int k = 0; k < kUniformMax; k++)
+                if (ms[k]) { if (t.phase == PH_STEP && t.cur == cs[k]) box_step_shared(p, r, t, cs[k]); }
+            return true;
+        }
+    }
+    if (t.phase == PH_STEP) box_step<PF>(p, r, t);
+    return false;
 }
 
 // Tracer.cu:308-374, restructured as described in trace_kernel.hip's header.  Returns tri_hit.
@@ -236,6 +326,7 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
     prefetch_pair<PF>(p, t);
     bool tri_hit = false;
     uint32_t nbox = 0, nleaf = 0;
+    bool shared = true;   // wave-uniform; kUniformSticky: the ray's steps look for shared pairs until one step finds too many
 #ifdef RT_EXP_UNIFORM_STATS
     uint32_t ustat[4] = {0, 0, 0, 0};
 #endif
@@ -261,6 +352,15 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 ustat[distinct <= 1 ? 0 : (distinct == 2 ? 1 : (distinct <= 4 ? 2 : 3))]++;
             }
 #endif
+            if constexpr (!PF && kUniformMax > 0) {
+                // second step under the same vote: the detection is redone on the lanes still stepping
+                if (!kUniformSticky || shared) {
+                    shared = box_step_wave<PF>(p, r, t, stepping);
+                    const uint64_t again = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
+                    if (again) shared = box_step_wave<PF>(p, r, t, again);
+                    continue;
+                }
+            }
             if (t.phase == PH_STEP) box_step<PF>(p, r, t);
             // second step under the same vote: halves the per-step loop overhead (ballots, branch, copies)
             if (t.phase == PH_STEP) box_step<PF>(p, r, t);
@@ -272,7 +372,13 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
             t.tri_tests++;
             const uint32_t li = t.leaf & kIndexMask;
             const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + li);
-            const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
+            uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
+#if RT_TRACE_LEAF_WIDE
+            // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (left alone the
+            // compiler narrows them to dwordx3 + overlapping dwordx2 pieces and fetches the primitive ids on a hit: 7+ requests)
+            asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
+                              "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
+#endif
             bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
                                          __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
                                          __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
