@@ -8,7 +8,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
-(``ClosestPoints``: the nearest triangle to each point, through any built tree).  torch is used for device
+(``ClosestPoints``: the nearest triangle to each point, through any built tree), and ray sorting (``SortRays``: a coherence
+order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
 
@@ -55,6 +56,8 @@ INSTANCE_RECORD = np.dtype([("world_to_object", "<f4", (3, 4)), ("blas", "<u4"),
 ACCEL = np.dtype([("triangles", "<u8"), ("nodes", "<u8"), ("root", "<u4"), ("count", "<u4")])                # 24 B
 assert INSTANCE.itemsize == 64 and INSTANCE_RECORD.itemsize == 64 and ACCEL.itemsize == 24
 RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
+# ray sorting (rt_sort_rays): a dead ray's key; every live key is below it
+RAY_KEY_BITS, RAY_KEY_DEAD = 30, 1 << 29
 # closest-point queries (rt_closest_points)
 POINT_QUERY = np.dtype([("p", "<f4", 3), ("dist2_max", "<f4")])                                            # 16 B
 POINT_HIT = np.dtype([("dist2", "<f4"), ("primitive_id", "<u4"), ("u", "<f4"), ("v", "<f4")])              # 16 B
@@ -117,6 +120,12 @@ class _SahScratchLayout(ctypes.Structure):
                 ("num_leaves", ctypes.c_size_t), ("cell_counts", ctypes.c_size_t), ("total", ctypes.c_size_t)]
 
 
+class _RaySortLayout(ctypes.Structure):
+    _fields_ = [("box", ctypes.c_size_t), ("num_live", ctypes.c_size_t), ("keys", ctypes.c_size_t),
+                ("tmp_keys", ctypes.c_size_t), ("tmp_values", ctypes.c_size_t), ("sort", ctypes.c_size_t),
+                ("total", ctypes.c_size_t)]
+
+
 class _RefitPlanLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
                 ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
@@ -128,6 +137,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
+           "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_error_string", "rt_version_string"]
 
 _lib = None
@@ -197,6 +207,14 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32, vp, vp]
     L.rt_closest_points.restype = i32
     L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
+    L.rt_ray_sort_scratch_bytes.restype = ctypes.c_size_t
+    L.rt_ray_sort_scratch_bytes.argtypes = [u32]
+    L.rt_ray_sort_layout_get.restype = i32
+    L.rt_ray_sort_layout_get.argtypes = [u32, ctypes.POINTER(_RaySortLayout)]
+    L.rt_sort_rays.restype = i32
+    L.rt_sort_rays.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp]
+    L.rt_intersect_rays_indexed.restype = i32
+    L.rt_intersect_rays_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, i32, u32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -550,6 +568,62 @@ def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, cou
 def point_status(status) -> int:
     """The RT_POINT_* flags ClosestPoints ORed into `status` (copies the word back: waits for the work queued before it)."""
     return int(to_host(status, np.uint32, 1)[0])
+
+
+def RaySortScratchBytes(num_rays: int) -> int:
+    """rt_ray_sort_scratch_bytes: device bytes of SortRays's scratch (12 bytes per ray + the sort's tables + 256)."""
+    return int(lib().rt_ray_sort_scratch_bytes(num_rays))
+
+
+def ray_sort_layout(num_rays: int) -> _RaySortLayout:
+    out = _RaySortLayout()
+    _check(lib().rt_ray_sort_layout_get(num_rays, ctypes.byref(out)), "rt_ray_sort_layout_get")
+    return out
+
+
+def SortRays(nodes, root: int, count: int, rays, order, scratch, stream=None) -> int:
+    """rt_sort_rays: a coherence order of `rays` (a contiguous device tensor of 32-byte RAY records) into `order` (a device
+    tensor of >= N uint32 / int32 words): ray indices by ascending key -- origin cell in the box of the tree's root run
+    (`nodes`, root / count as for IntersectRays; a TLAS will do), then direction cell; dead rays (the ones IntersectRays does
+    not trace) last.  `scratch`: >= RaySortScratchBytes(N) bytes, 256-byte aligned (device_bytes).  One sort serves any
+    number of IntersectRaysIndexed calls on the same rays.  Asynchronous on `stream`.  Returns N."""
+    if not rays.is_contiguous() or not order.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, order a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(order) < 4 * n or _nbytes(scratch) < RaySortScratchBytes(n):
+        raise ValueError(f"order must hold {n} words and scratch RaySortScratchBytes({n}) bytes")
+    if n == 0:
+        return 0
+    a = _Accel(0, _ptr(nodes), root, count)
+    _check(lib().rt_sort_rays(ctypes.byref(a), _ptr(rays), n, _ptr(order), _ptr(scratch), _stream_ptr(stream)), "rt_sort_rays")
+    return n
+
+
+def ray_sort_live(scratch, num_rays: int) -> int:
+    """The number of live rays of the last SortRays on `scratch`: order[:live] are the rays a query traces (copies the word
+    back: waits for the work queued before it on the current stream)."""
+    return int(to_host(scratch, np.uint32, 1, ray_sort_layout(num_rays).num_live)[0])
+
+
+def IntersectRaysIndexed(triangles, nodes, root: int, count: int, rays, order, hits, *, num_indices: Optional[int] = None,
+                         any_hit: bool = False, num_primitives: int = 0, counters=None, stream=None) -> None:
+    """rt_intersect_rays_indexed: IntersectRays through an index list.  Launch position j (64 consecutive j per wave) traces
+    rays[order[j]] and writes hits[order[j]]; an index >= N (0xFFFFFFFF, say) is skipped and unlisted records are not
+    written.  `order`: a contiguous device tensor of uint32 / int32 words -- SortRays's output, or any list of the rays still
+    alive; num_indices: how many of its words to use (default: all).  Each written record equals IntersectRays's bit for
+    bit.  counters[2:4] (wave steps) measure the order's coherence.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not order.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits / order contiguous device buffers")
+    n = _nbytes(rays) // 32
+    k = _nbytes(order) // 4 if num_indices is None else int(num_indices)
+    if _nbytes(hits) < 16 * n or _nbytes(order) < 4 * k:
+        raise ValueError(f"hits must hold {n} 16-byte records and order {k} words")
+    if k == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_intersect_rays_indexed(ctypes.byref(a), _ptr(rays), n, _ptr(order), k, _ptr(hits),
+                                           kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
+                                           _stream_ptr(stream)), "rt_intersect_rays_indexed")
 
 
 def version() -> str:

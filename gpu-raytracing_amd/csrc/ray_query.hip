@@ -21,6 +21,8 @@
 #include "rt_launch.hpp"
 #include "rt_traverse.hpp"
 
+#include <type_traits>
+
 namespace rt {
 
 struct QueryParams {
@@ -34,9 +36,26 @@ struct QueryParams {
     static constexpr int park_num = kParkNum, park_den = kParkDen;   // (trace_ray reads them as members)
 };
 
-template <bool PF, bool ANY>
+// rt_intersect_rays_indexed: the same query through an index list.  Launch position j takes ray order[j]; everything after
+// the choice of the ray index is the same code.
+struct IndexedQueryParams : QueryParams {
+    const uint32_t* order;
+    uint32_t num_indices;
+};
+
+// launch position j -> ray index (0xFFFFFFFF: no ray -- num_rays is a uint32, so it is never in range)
+template <bool INDEXED, class Params>
+__device__ __forceinline__ uint64_t ray_index(const Params& p, uint64_t j)
+{
+    if constexpr (INDEXED) return j < p.num_indices ? p.order[j] : 0xFFFFFFFFull;
+    else return j;
+}
+
+// One kernel body for both entry points.  INDEXED only changes how the lane's ray index i is obtained: the launch position
+// itself, or order[position] (positions past num_indices and indices >= num_rays: no ray, nothing written).
+template <bool PF, bool ANY, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, PF ? RT_TRACE_PF_WAVES : RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA)
-void ray_query_kernel(QueryParams p)
+void ray_query_kernel(std::conditional_t<INDEXED, IndexedQueryParams, QueryParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
@@ -46,7 +65,7 @@ void ray_query_kernel(QueryParams p)
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    const uint64_t i = ray_index<INDEXED>(p, ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane);
     const bool in_range = i < p.num_rays;
 
     float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, -1.f};
@@ -148,11 +167,39 @@ hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits
     const dim3 grid((uint32_t)(((uint64_t)num_rays + rays_per_block - 1) / rays_per_block)), block(rays_per_block);
     const bool pf = num_primitives >= kPrefetchMinPrims;   // as launch_trace: trees that do not fit the caches
     if (pf) {
-        if (any_hit) ray_query_kernel<true, true><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<true, false><<<grid, block, 0, st>>>(p);
+        if (any_hit) ray_query_kernel<true, true, false><<<grid, block, 0, st>>>(p);
+        else ray_query_kernel<true, false, false><<<grid, block, 0, st>>>(p);
     } else {
-        if (any_hit) ray_query_kernel<false, true><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<false, false><<<grid, block, 0, st>>>(p);
+        if (any_hit) ray_query_kernel<false, true, false><<<grid, block, 0, st>>>(p);
+        else ray_query_kernel<false, false, false><<<grid, block, 0, st>>>(p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_query_indexed(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
+                                    uint32_t num_indices, rt_hit* hits, bool any_hit, uint32_t num_primitives,
+                                    uint64_t* counters, hipStream_t st)
+{
+    IndexedQueryParams p;
+    p.nodes = as.nodes;
+    p.leaves = as.triangles;
+    p.root = as.root;
+    p.count = as.count;
+    p.rays = reinterpret_cast<const float4*>(rays);
+    p.hits = reinterpret_cast<float4*>(hits);
+    p.num_rays = num_rays;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.order = order;
+    p.num_indices = num_indices;
+    const uint32_t rays_per_block = kTraceWaves * 64;
+    const dim3 grid((uint32_t)(((uint64_t)num_indices + rays_per_block - 1) / rays_per_block)), block(rays_per_block);
+    const bool pf = num_primitives >= kPrefetchMinPrims;   // as launch_ray_query
+    if (pf) {
+        if (any_hit) ray_query_kernel<true, true, true><<<grid, block, 0, st>>>(p);
+        else ray_query_kernel<true, false, true><<<grid, block, 0, st>>>(p);
+    } else {
+        if (any_hit) ray_query_kernel<false, true, true><<<grid, block, 0, st>>>(p);
+        else ray_query_kernel<false, false, true><<<grid, block, 0, st>>>(p);
     }
     return hipGetLastError();
 }

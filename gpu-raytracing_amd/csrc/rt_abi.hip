@@ -279,6 +279,47 @@ int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint
                                    static_cast<hipStream_t>(stream)));
 }
 
+static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
+                              uint32_t num_indices, rt_hit* hits, int mode, uint32_t num_primitives, uint64_t* counters,
+                              void* stream)
+{
+    if (!as || !rays || !hits || !order || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(order, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_indices == 0) return RT_OK;
+    return hip_rc(launch_ray_query_indexed(*as, rays, num_rays, order, num_indices, hits, mode == RT_RAY_ANY_HIT,
+                                           num_primitives, counters, static_cast<hipStream_t>(stream)));
+}
+
+size_t rt_ray_sort_scratch_bytes(uint32_t num_rays) { return ray_sort_layout(num_rays).total; }
+
+int rt_ray_sort_layout_get(uint32_t num_rays, rt_ray_sort_layout* out)
+{
+    if (!out) return RT_ERR_INVALID_ARGUMENT;
+    const RaySortLayout L = ray_sort_layout(num_rays);
+    out->box = L.box;
+    out->num_live = L.num_live;
+    out->keys = L.keys;
+    out->tmp_keys = L.tmp_keys;
+    out->tmp_values = L.tmp_values;
+    out->sort = L.sort;
+    out->total = L.total;
+    return RT_OK;
+}
+
+int rt_sort_rays(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t* order, void* scratch, void* stream)
+{
+    if (!as || !rays || !order || !scratch || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && !as->nodes) return RT_ERR_INVALID_ARGUMENT;   // (the root run's boxes are all the call reads)
+    if (misaligned(rays, 16) || misaligned(order, 4) || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays > kSortMaxCount) return RT_ERR_TOO_LARGE;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_sort_rays(*as, rays, num_rays, order, scratch, static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, int layout, rt_ray* rays,
                             void* stream)
 {
@@ -331,8 +372,6 @@ int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* p
     if (rc <= 0) return rc;
     return hip_rc(launch_refit(*input, root, count, plan, static_cast<hipStream_t>(stream)));
 }
-
-static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
                          rt_triangle* proxies, rt_instance_record* records, uint32_t* status, void* stream)
@@ -406,6 +445,8 @@ const char* rt_version_string(void)
            "sah: 4x4x4 grid + level-synchronous binned SAH (fixed launch count, no host round trip), workgroup-per-task stragglers, wave-per-task below 64 items, pairs, splits | "
            "trace: wave64 8x8 tiles, two-phase schedule, LDS stack 16, XCD chunks of 8 workgroups, pair prefetch from 8M primitives, counters through 16-row slots | "
            "rays: caller rays through the same traversal, 64 consecutive rays per wave, closest / any hit, 16-byte records, camera rays row-major or 8x8-tiled | "
+           "raysort: 27-bit keys (7 origin bits per axis in the root box, Morton, above 2 direction bits per axis of d / max|d|), dead rays "
+           "last, the 3x10bit sort with identity values, indexed queries through the ray-query kernel body | "
            "refit: top-down plan walk (one wide launch per level + one-workgroup tail, one CAS per run), one thread per leaf slot "
            "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max | "
            "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "

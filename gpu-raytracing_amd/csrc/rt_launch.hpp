@@ -187,6 +187,25 @@ hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits
 hipError_t launch_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, bool tiled, rt_ray* rays,
                               hipStream_t st);
 
+// ray_query.hip: rt_intersect_rays_indexed after its argument checks (num_indices > 0)
+hipError_t launch_ray_query_indexed(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
+                                    uint32_t num_indices, rt_hit* hits, bool any_hit, uint32_t num_primitives,
+                                    uint64_t* counters, hipStream_t st);
+
+// ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
+struct RaySortLayout {
+    size_t box;         // float lo[4], hi[4] at the start of the 256-byte header
+    size_t num_live;    // uint32 inside the header
+    size_t keys;        // uint32[n]: the sorted keys after the call
+    size_t tmp_keys;    // uint32[n]
+    size_t tmp_values;  // uint32[n]
+    size_t sort;        // SortScratch
+    size_t total;
+};
+RaySortLayout ray_sort_layout(uint32_t num_rays);
+hipError_t launch_sort_rays(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t* order, void* scratch,
+                            hipStream_t st);
+
 // refit.hip: rt_build_refit_plan / rt_refit after their argument checks (n > 0)
 struct RefitLayout {
     size_t status;    // the plan header (256 bytes; word 0 = RT_REFIT_* flags)

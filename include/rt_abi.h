@@ -453,6 +453,64 @@ enum { RT_POINT_STACK_OVERFLOW = 1 };
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- ray sorting and indexed ray queries (no reference counterpart).  rt_intersect_rays gives a wave 64 consecutive rays, so
+ * its speed depends on the caller's ray order.  rt_sort_rays computes a coherence order of a batch, rt_intersect_rays_indexed
+ * traces a batch through an index list -- that order, or any list of rays still alive.
+ *
+ * rt_sort_rays writes into order[0 .. num_rays) the ray indices in ascending key order; ties go to the lower index (the sort
+ * is stable).  One sort serves any number of queries on the same rays (closest, any hit, other tmax windows that keep the
+ * live set).
+ *   Liveness.  A ray is dead exactly when rt_intersect_rays would not trace it: tmin > tmax, or a NaN in tmin, tmax, origin
+ *   or direction.  A dead ray's key is RT_RAY_KEY_DEAD and nothing else: dead rays follow every live ray, in index order.
+ *   The number of live rays lands in the scratch (rt_ray_sort_layout.num_live, a device uint32; read it after the stream ran).
+ *   Box.  lo / hi = the ordered min / max (the floats' monotone integer image, -0 below +0) of min / max over the non-NONE
+ *   slots of the root run [root, root + count); lo = hi = 0 when there is no such slot (an empty tree, count = 0).  Stored in
+ *   the scratch (rt_ray_sort_layout.box: float lo[3], one unused float, float hi[3], one unused float).  Nothing else of
+ *   the tree is read, so `as` may be a TLAS.
+ *   Key of a live ray, float32, every operation rounded on its own (no fused multiply-add), IEEE division:
+ *     cell(q, C) = (q > 0) ? (q >= C - 1 ? C - 1 : trunc(q)) : 0              -- selects; a NaN q gives cell 0
+ *     per axis k: e = hi[k] - lo[k];  oc[k] = cell(((origin[k] - lo[k]) / e) * 128, 128)
+ *     m = |dir.x|; if (|dir.y| > m) m = |dir.y|; if (|dir.z| > m) m = |dir.z|
+ *     per axis k: dc[k] = cell((dir[k] / m) * 2 + 2, 4)
+ *     key = morton3(oc) << 6 | morton3(dc),  morton3(c) = bit j of c[0] at position 3j + 2, of c[1] at 3j + 1, of c[2] at 3j
+ *   27 bits: 7 origin bits per axis above 2 direction bits per axis (the direction's sign is the higher of the two).  The
+ *   recipe is total: an origin outside the box, +-inf included, clamps to a border cell; a degenerate axis (hi == lo: e = 0)
+ *   gives cell 127 above lo, cell 0 at or below it; a zero direction (0 / 0) gives dc = 0; the direction's length does not
+ *   matter (dir / m is exact under scaling by a power of two while no component leaves the normal range).
+ *   Scratch: rt_ray_sort_scratch_bytes(num_rays) bytes, 256-byte aligned, no initialisation needed: a 256-byte header (box,
+ *   num_live), three uint32[num_rays] arrays (keys -- the sorted keys after the call -- and the sort's two temporaries), and
+ *   the sort's tables (rt_radix_sort_scratch_bytes).  `order` is the sort's value array.
+ *   Launches: 2 + the sort's (three 10-bit passes up to 2M rays, else four 8-bit ones), fixed by num_rays.
+ *   Argument errors, returned before any GPU work: RT_ERR_INVALID_ARGUMENT for a null as / rays / order / scratch, rays not
+ *   16-byte, order not 4-byte, scratch not 256-byte aligned, count > 7, or a tree with count > 0 and a null node pointer;
+ *   RT_ERR_TOO_LARGE for num_rays > 0x3FFFFFFF (the sort's limit).  num_rays = 0: nothing runs.
+ *
+ * rt_intersect_rays_indexed: lane j of the launch (j < num_indices, 64 consecutive j per wave) takes i = order[j].  If
+ * i < num_rays it traces rays[i] and writes hits[i], with rt_intersect_rays's semantics in every respect (the same kernel body);
+ * if i >= num_rays (0xFFFFFFFF for instance) it does nothing.  Records whose index is not listed are not written; a
+ * duplicated index writes the same bytes twice.  For any index list each written hits[i] equals rt_intersect_rays's record
+ * bit for bit (a ray's result does not depend on its wave neighbours); when order is a permutation counters[0] and [1]
+ * equal rt_intersect_rays's too, while [2] / [3] (wave steps) depend on the order: they measure its coherence.
+ * Argument errors: rt_intersect_rays's, plus a null order or one not 4-byte aligned.  num_indices = 0: nothing runs.
+ * Both calls are asynchronous (no host copy, no synchronisation: hipGraph-capturable). */
+#define RT_RAY_KEY_BITS 30
+#define RT_RAY_KEY_DEAD (1u << 29)
+typedef struct rt_ray_sort_layout {
+    size_t box;         /* float[8]: lo.xyz, -, hi.xyz, - (the start of the 256-byte header) */
+    size_t num_live;    /* uint32: live rays of the last rt_sort_rays */
+    size_t keys;        /* uint32[num_rays]: the sorted keys after the call (keys[j] is the key of ray order[j]) */
+    size_t tmp_keys;    /* uint32[num_rays] */
+    size_t tmp_values;  /* uint32[num_rays] */
+    size_t sort;        /* rt_radix_sort_scratch_bytes(num_rays) bytes */
+    size_t total;       /* = rt_ray_sort_scratch_bytes(num_rays) */
+} rt_ray_sort_layout;
+size_t rt_ray_sort_scratch_bytes(uint32_t num_rays);
+int rt_ray_sort_layout_get(uint32_t num_rays, rt_ray_sort_layout* out);
+int rt_sort_rays(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t* order, void* scratch, void* stream);
+int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
+                              uint32_t num_indices, rt_hit* hits, int mode, uint32_t num_primitives, uint64_t* counters,
+                              void* stream);
+
 /* static string for a return code */
 const char* rt_error_string(int code);
 

@@ -39,24 +39,12 @@ def timed(fn, iters, warmup):
 
 
 def bounce_rays(rt, prim_rays, hits, tris, seed=1):
-    """origins on the primary hits (offset 1e-3 along the normal facing the ray), uniform hemisphere directions; rays of
-    missed pixels get tmax < tmin (not traced)"""
+    """raygen.bounce_rays on device tensors: (device rays [N, 8], number of live rays)"""
     import torch
-    r = prim_rays.cpu().numpy().view(rt.RAY).reshape(-1)
-    h = hits.cpu().numpy().view(rt.HIT).reshape(-1)
-    ok = h["primitive_id"] != rt.MISS
-    V = tris.reshape(-1, 3, 3)[np.where(ok, h["primitive_id"], 0).astype(np.int64)].astype(np.float32)
-    n = np.cross(V[:, 1] - V[:, 0], V[:, 2] - V[:, 0])
-    n /= np.maximum(np.linalg.norm(n, axis=1), 1e-30)[:, None]
-    n *= -np.sign((n * r["dir"]).sum(axis=1))[:, None]
-    P = r["origin"] + r["dir"] * np.where(ok, h["t"], 0)[:, None]
-    d = np.random.default_rng(seed).normal(size=P.shape).astype(np.float32)
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    d *= np.sign((d * n).sum(axis=1))[:, None]
-    out = np.zeros(r.size, rt.RAY)
-    out["origin"], out["dir"] = P + n * np.float32(1e-3), d
-    out["tmin"], out["tmax"] = np.float32(1e-5), np.where(ok, np.float32(np.inf), np.float32(-1))
-    return rt.to_device(out).view(torch.float32).view(-1, 8), int(ok.sum())
+    raygen = importlib.import_module("gpu-raytracing_amd.raygen")
+    out, live = raygen.bounce_rays(prim_rays.cpu().numpy().view(rt.RAY).reshape(-1), hits.cpu().numpy().view(rt.HIT).reshape(-1),
+                                   tris, seed)
+    return rt.to_device(out).view(torch.float32).view(-1, 8), live
 
 
 def main():
