@@ -138,7 +138,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
-           "rt_error_string", "rt_version_string"]
+           "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -215,6 +215,10 @@ def lib() -> ctypes.CDLL:
     L.rt_sort_rays.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp]
     L.rt_intersect_rays_indexed.restype = i32
     L.rt_intersect_rays_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, i32, u32, vp, vp]
+    L.rt_generate_shadow_rays.restype = i32
+    L.rt_generate_shadow_rays.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_float), vp, vp]
+    L.rt_shade_frame.restype = i32
+    L.rt_shade_frame.argtypes = [ctypes.POINTER(_Scene), vp, u32, vp, vp, vp, u32, u32, u32, i32, i32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -624,6 +628,44 @@ def IntersectRaysIndexed(triangles, nodes, root: int, count: int, rays, order, h
     _check(lib().rt_intersect_rays_indexed(ctypes.byref(a), _ptr(rays), n, _ptr(order), k, _ptr(hits),
                                            kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
                                            _stream_ptr(stream)), "rt_intersect_rays_indexed")
+
+
+def GenerateShadowRays(rays, hits, num_triangles: int, light, shadow_rays, stream=None) -> int:
+    """rt_generate_shadow_rays: for every RAY record of `rays` whose HIT record names a triangle (primitive_id <
+    num_triangles), the ray from the hit point to `light` (tmin 0.001, tmax = the light's distance) at the same index of
+    `shadow_rays`; a dead ray (tmax -1) for a miss.  IntersectRays(..., any_hit=True) on the result gives the shadow records
+    ShadeFrame takes for kTextureLitShadows.  Returns the number of rays."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not shadow_rays.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays / shadow_rays must be contiguous device buffers of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(shadow_rays) < 32 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records, shadow_rays {n} 32-byte records")
+    _check(lib().rt_generate_shadow_rays(_ptr(rays), _ptr(hits), n, int(num_triangles),
+                                         (ctypes.c_float * 3)(*[float(x) for x in light]), _ptr(shadow_rays),
+                                         _stream_ptr(stream)), "rt_generate_shadow_rays")
+    return n
+
+
+def ShadeFrame(triangles_in, num_triangles: int, rays, hits, rgba8, dims, *, render_type: int = kDepth, spp: int = 1,
+               tiled: bool = False, shadow_hits=None, attributes=None, materials=None, num_materials: int = 0,
+               light=(0.0, 0.0, 0.0), textures: Optional[DeviceTextures] = None, stream=None) -> None:
+    """rt_shade_frame: the frame Trace() renders, from stored records -- `rays` as GenerateCameraRays wrote them (same dims,
+    spp and layout), `hits` from IntersectRays / IntersectRaysIndexed on them, `shadow_hits` (kTextureLitShadows only) from
+    an any-hit query on GenerateShadowRays's rays.  `triangles_in`: the caller's 36-byte triangles on the device
+    (BuildInput.triangles_in); no tree is needed.  kBoxtests / kTriangleTests are not available from records (RtError, -2).
+    Byte-equal to Trace() on non-pair trees; asynchronous on `stream`."""
+    w, h = int(dims[0]), int(dims[1])
+    n = CameraRayCount(w, h, int(spp), tiled)
+    if _nbytes(rays) < 32 * n or _nbytes(hits) < 16 * n or _nbytes(rgba8) < 4 * w * h:
+        raise ValueError(f"rays / hits must hold {n} records, rgba8 {4 * w * h} bytes")
+    if shadow_hits is not None and _nbytes(shadow_hits) < 16 * n:
+        raise ValueError(f"shadow_hits must hold {n} 16-byte records")
+    s = _Scene(_ptr(attributes), _ptr(materials), _ptr(textures.table) if textures is not None else 0, 0,
+               (ctypes.c_float * 3)(*[float(x) for x in light]),
+               int(num_triangles), num_materials, textures.count if textures is not None else 0)
+    _check(lib().rt_shade_frame(ctypes.byref(s), _ptr(triangles_in), int(num_triangles), _ptr(rays), _ptr(hits),
+                                _ptr(shadow_hits), w, h, int(spp), kRaysTiled if tiled else kRaysRowMajor, int(render_type),
+                                _ptr(rgba8), _stream_ptr(stream)), "rt_shade_frame")
 
 
 def version() -> str:

@@ -425,6 +425,53 @@ int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_poin
     return hip_rc(launch_point_query(*as, queries, hits, num_queries, counters, status, static_cast<hipStream_t>(stream)));
 }
 
+int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
+                            const float* light, rt_ray* shadow_rays, void* stream)
+{
+    if (!rays || !hits || !light || !shadow_rays) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(shadow_rays, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_shadow_rays(rays, hits, num_rays, num_triangles, light, shadow_rays, static_cast<hipStream_t>(stream)));
+}
+
+int rt_shade_frame(const rt_scene* scene, const rt_triangle* triangles, uint32_t num_triangles, const rt_ray* rays,
+                   const rt_hit* hits, const rt_hit* shadow_hits, uint32_t w, uint32_t h, uint32_t spp, int layout,
+                   int render_type, uint8_t* rgba8, void* stream)
+{
+    if (!scene || !triangles || !rays || !hits || !rgba8) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(shadow_hits, 16) || misaligned(rgba8, 4) ||
+        misaligned(triangles, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (layout != RT_RAYS_ROW_MAJOR && layout != RT_RAYS_TILED) return RT_ERR_INVALID_ARGUMENT;
+    if (spp != 1 && spp != 4 && spp != 16) return RT_ERR_INVALID_ARGUMENT;
+    switch (render_type) {
+    case RT_RENDER_DEPTH: break;
+    case RT_RENDER_BOXTESTS: case RT_RENDER_TRIANGLE_TESTS: return RT_ERR_UNSUPPORTED;   // a hit record carries no test counts
+    case RT_RENDER_MATERIAL_ID: case RT_RENDER_DIFFUSE:
+        if (!scene->attributes || !scene->materials || scene->num_materials == 0) return RT_ERR_INVALID_ARGUMENT;   // as rt_trace
+        break;
+    case RT_RENDER_LODS: case RT_RENDER_TEXTURE: case RT_RENDER_TEXTURE_LIT: case RT_RENDER_TEXTURE_LIT_SHADOWS:
+        if (!scene->attributes || !scene->materials || scene->num_materials == 0) return RT_ERR_INVALID_ARGUMENT;
+        if (scene->num_textures && !scene->textures) return RT_ERR_INVALID_ARGUMENT;
+        if (render_type == RT_RENDER_TEXTURE_LIT_SHADOWS && !shadow_hits) return RT_ERR_INVALID_ARGUMENT;
+        break;
+    default: return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (w == 0 || h == 0) return RT_OK;
+    ShadeLaunch t;
+    t.scene = *scene;
+    t.triangles = triangles;
+    t.num_triangles = num_triangles;
+    t.rays = rays;
+    t.hits = hits;
+    t.shadow_hits = shadow_hits;
+    t.w = w; t.h = h; t.spp = spp;
+    t.tiled = layout == RT_RAYS_TILED;
+    t.render_type = render_type;
+    t.rgba8 = rgba8;
+    return hip_rc(launch_shade_frame(t, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -452,7 +499,9 @@ const char* rt_version_string(void)
            "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "
            "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
-           "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id)";
+           "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
+           "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
+           "instantiations, shadow rays as a ray batch for the any-hit query";
 }
 
 }  // extern "C"

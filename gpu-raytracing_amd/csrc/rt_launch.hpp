@@ -220,6 +220,23 @@ uint32_t refit_plan_wide_levels(uint32_t n);   // wide walk launches of a plan b
 hipError_t launch_refit_plan(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
 hipError_t launch_refit(const rt_build_input& in, uint32_t root, uint32_t count, void* plan, hipStream_t st);
 
+// shade.hip: rt_generate_shadow_rays / rt_shade_frame after their argument checks (num_rays > 0, w * h > 0)
+hipError_t launch_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
+                              const float light[3], rt_ray* shadow_rays, hipStream_t st);
+struct ShadeLaunch {
+    rt_scene scene;                // attributes, materials, textures, light (the camera pointer is not read)
+    const rt_triangle* triangles;  // the caller's triangles
+    uint32_t num_triangles;
+    const rt_ray* rays;
+    const rt_hit* hits;
+    const rt_hit* shadow_hits;     // RT_RENDER_TEXTURE_LIT_SHADOWS only
+    uint32_t w, h, spp;
+    bool tiled;
+    int render_type;
+    uint8_t* rgba8;
+};
+hipError_t launch_shade_frame(const ShadeLaunch& t, hipStream_t st);
+
 // instances.hip: rt_prepare_instances / rt_intersect_rays_instanced after their argument checks (the query: num_rays > 0)
 hipError_t launch_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
                                     uint32_t num_blas, rt_triangle* proxies, rt_instance_record* records, uint32_t* status,

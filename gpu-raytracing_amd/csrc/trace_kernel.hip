@@ -38,6 +38,7 @@
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_math.h"
+#include "rt_shade.hpp"      // the shading helpers (shared with shade.hip)
 #include "rt_traverse.hpp"   // Ray, Hit, Trav, box_step, trace_ray, camera_ray (shared with ray_query.hip)
 
 namespace rt {
@@ -96,150 +97,9 @@ struct TraceParams {
 };
 
 
-__device__ __forceinline__ float clampf(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }
-
-// Tracer.cu:15-41 (float rgb 0..255 before the uchar truncation)
-__device__ __forceinline__ void hsv_to_rgb255(float h, float s, float v, float& R, float& G, float& B)
-{
-    h = clampf(h, 0.f, 1.f) * 360.0f;
-    s = clampf(s, 0.f, 1.f);
-    v = clampf(v, 0.f, 1.f);
-    const float c = s * v;
-    const float x = c * (1 - fabsf(((int)h % 120) / 60.0f - 1));
-    const float m = v - c;
-    float r, g, b;
-    if (h >= 0 && h < 60) { r = c; g = x; b = 0; }
-    else if (h >= 60 && h < 120) { r = x; g = c; b = 0; }
-    else if (h >= 120 && h < 180) { r = 0; g = c; b = x; }
-    else if (h >= 180 && h < 240) { r = 0; g = x; b = c; }
-    else if (h >= 240 && h < 300) { r = x; g = 0; b = c; }
-    else { r = c; g = 0; b = x; }
-    R = (r + m) * 255; G = (g + m) * 255; B = (b + m) * 255;
-}
-
-// ---------------------------------------------------------------------------------------------
-// float -> unsigned char as CUDA converts it (cvt.rzi.u8.f32: NaN -> 0, saturating); bilinear weights at a texture
-// border leave [0, 255]
-__device__ __forceinline__ uint32_t sat_u8(float v) { return !(v > 0.0f) ? 0u : (v >= 255.0f ? 255u : (uint32_t)v); }
-struct F2 { float x, y; };
-struct U8x4 { uint32_t c[4]; };
-__device__ __forceinline__ float fracf1(float v) { return v - floorf(v); }   // helper_math.h:1367
-
-// Sample(Texture&, int2, lod) (Tracer.cu:103-108)
-__device__ __forceinline__ void tex_fetch(const rt_texture& t, int x, int y, int lod, float out[4])
-{
-    const int sx = t.size_x[lod], sy = t.size_y[lod];
-    x = max(0, min(x, sx - 1));
-    y = max(0, min(y, sy - 1));
-    const uint32_t w = t.mips[lod][(size_t)y * sx + x];
-    out[0] = (float)(w & 255u); out[1] = (float)((w >> 8) & 255u); out[2] = (float)((w >> 16) & 255u); out[3] = (float)(w >> 24);
-}
-// BilinearSample (Tracer.cu:122-140)
-__device__ __forceinline__ U8x4 bilinear_sample(const rt_texture& t, F2 uv, int lod)
-{
-    float cx = fracf1(uv.x) * (float)t.size_x[lod] - 0.5f;
-    float cy = fracf1(uv.y) * (float)t.size_y[lod] - 0.5f;
-    cy = (float)t.size_y[lod] - cy;
-    const int ix = (int)cx, iy = (int)cy;
-    const float dx = cx - (float)ix, dy = cy - (float)iy;
-    const float w0 = (1.0f - dx) * dy, w1 = dx * dy, w2 = (1.0f - dx) * (1.0f - dy), w3 = dx * (1.0f - dy);
-    float s0[4], s1[4], s2[4], s3[4];
-    tex_fetch(t, ix, iy, lod, s0);
-    tex_fetch(t, ix + 1, iy, lod, s1);
-    tex_fetch(t, ix, iy - 1, lod, s2);
-    tex_fetch(t, ix + 1, iy - 1, lod, s3);
-    U8x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; c++) o.c[c] = sat_u8(((s0[c] * w0 + s1[c] * w1) + s2[c] * w2) + s3[c] * w3);
-    return o;
-}
-// TrilinearSample (Tracer.cu:142-155)
-__device__ __forceinline__ U8x4 trilinear_sample(const rt_texture& t, F2 uv, float lod)
-{
-    uint32_t min_lod = (uint32_t)floorf(lod), max_lod = min_lod + 1;
-    min_lod = min(min_lod, t.max_lod);
-    max_lod = min(max_lod, t.max_lod);
-    const U8x4 a = bilinear_sample(t, uv, (int)min_lod), b = bilinear_sample(t, uv, (int)max_lod);
-    const float frac = fracf1(lod);
-    U8x4 o;
-#pragma unroll
-    for (int c = 0; c < 4; c++) o.c[c] = sat_u8((float)a.c[c] * (1.0f - frac) + (float)b.c[c] * frac);
-    return o;
-}
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 vscale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float vdot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 vcross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 vnormalize(V3 v) { return vscale(v, 1.0f / sqrtf(vdot(v, v))); }
-
-struct Surface {   // what the textured shaders need about the hit
-    V3 tri[3];
-    float uv[3][2];
-    V3 n[3];
-};
-__device__ __forceinline__ F2 interp_uv(const Surface& s, float bu, float bv)   // InterpolateUVs (Tracer.cu:43-48)
-{
-    const float w0 = 1 - bu - bv;
-    return {(s.uv[0][0] * w0 + s.uv[1][0] * bu) + s.uv[2][0] * bv, (s.uv[0][1] * w0 + s.uv[1][1] * bu) + s.uv[2][1] * bv};
-}
-// ComputeLOD (Tracer.cu:237-254) with RayTriangleGradients (:202-235) inlined
-__device__ __forceinline__ float compute_lod(const Ray& r, const Hit& h, float spread, const Surface& s, const rt_texture& tex)
-{
-    const V3 o = v3(r.ox, r.oy, r.oz), d = v3(r.dx, r.dy, r.dz);
-    const V3 edge1 = vsub(s.tri[1], s.tri[0]), edge2 = vsub(s.tri[2], s.tri[0]);
-    const V3 sv = vsub(o, s.tri[0]);
-    const V3 q = vcross(sv, edge1);
-    const V3 x = vscale(vscale(vnormalize(vcross(d, v3(0, 1, 0))), r.tmax), spread);
-    const V3 y = vscale(vscale(vnormalize(vcross(d, x)), r.tmax), spread);
-    const V3 hit_point = vadd(o, vscale(d, r.tmax));
-    const V3 dirx = vnormalize(vsub(vadd(hit_point, x), o)), diry = vnormalize(vsub(vadd(hit_point, y), o));
-    const V3 h0 = vcross(dirx, edge2);
-    const float f0 = 1.0f / vdot(edge1, h0);
-    const float bu0 = f0 * vdot(sv, h0), bv0 = f0 * vdot(dirx, q);
-    const V3 h1 = vcross(diry, edge2);
-    const float f1 = 1.0f / vdot(edge1, h1);
-    const float bu1 = f1 * vdot(sv, h1), bv1 = f1 * vdot(diry, q);
-    const F2 uvs = interp_uv(s, h.bu, h.bv), ux = interp_uv(s, bu0, bv0), uy = interp_uv(s, bu1, bv1);
-    const float sx = (float)tex.size_x[0], sy = (float)tex.size_y[0];
-    const float dxx = fabsf(ux.x - uvs.x) * sx, dxy = fabsf(ux.y - uvs.y) * sy;
-    const float dyx = fabsf(uy.x - uvs.x) * sx, dyy = fabsf(uy.y - uvs.y) * sy;
-    const float max_change = fmaxf(sqrtf(dxx * dxx + dxy * dxy), sqrtf(dyx * dyx + dyy * dyy));
-    return fmaxf(0.0f, fminf(rt_log2f(max_change), (float)tex.max_lod));   // log2f: rt_math.h (bit-identical to the oracle)
-}
-// TangentMatrix (Tracer.cu:84-101)
-__device__ __forceinline__ void tangent_matrix(const Surface& s, V3 rows[3])
-{
-    const V3 e1 = vsub(s.tri[1], s.tri[0]), e2 = vsub(s.tri[2], s.tri[0]);
-    const float d1x = s.uv[1][0] - s.uv[0][0], d1y = s.uv[1][1] - s.uv[0][1];
-    const float d2x = s.uv[2][0] - s.uv[0][0], d2y = s.uv[2][1] - s.uv[0][1];
-    const float f = 1.0f / (d1x * d2y - d1y * d2x);
-    const V3 normal = vnormalize(vcross(e1, e2));
-    const V3 tangent = vnormalize(vscale(vsub(vscale(e1, d2y), vscale(e2, d1y)), f));
-    const V3 bitangent = vnormalize(vscale(vsub(vscale(e2, d1x), vscale(e1, d2x)), f));
-    rows[0] = v3(tangent.x, bitangent.x, normal.x);
-    rows[1] = v3(tangent.y, bitangent.y, normal.y);
-    rows[2] = v3(tangent.z, bitangent.z, normal.z);
-}
-// Bump2Normal (Tracer.cu:157-185)
-__device__ __forceinline__ V3 bump2normal(const rt_texture& tex, const V3 tbn[3], F2 uv, float lod)
-{
-    const float texel_step = rt_exp2f(lod);   // powf(2.0f, lod): rt_math.h
-    const float stx = texel_step / (float)tex.size_x[0], sty = texel_step / (float)tex.size_y[0];
-    const U8x4 a = trilinear_sample(tex, F2{uv.x - stx * 0.5f, uv.y - sty * 0.5f}, lod);
-    const U8x4 b = trilinear_sample(tex, F2{uv.x + stx * 0.5f, uv.y + 0.0f}, lod);
-    const U8x4 c = trilinear_sample(tex, F2{uv.x + 0.0f, uv.y + sty * 0.5f}, lod);
-    const float gx = (float)b.c[0] - (float)a.c[0], gy = (float)c.c[0] - (float)a.c[0];
-    const float d = 4.0f;
-    V3 n = vnormalize(vcross(v3(1, 0, d * gx / (texel_step * 256.0f)), v3(0, 1, d * gy / (texel_step * 256.0f))));
-    n = v3(vdot(tbn[0], n), vdot(tbn[1], n), vdot(tbn[2], n));
-    return vnormalize(n);
-}
-
-constexpr bool render_is_lit(int r) { return r == RT_RENDER_DIFFUSE || r == RT_RENDER_TEXTURE_LIT || r == RT_RENDER_TEXTURE_LIT_SHADOWS; }
-constexpr bool render_uses_surface(int r) { return r == RT_RENDER_LODS || r == RT_RENDER_TEXTURE || r == RT_RENDER_TEXTURE_LIT || r == RT_RENDER_TEXTURE_LIT_SHADOWS; }
+// (the device shading helpers -- colour conversion, texture sampling, ComputeLOD, TangentMatrix, Bump2Normal -- live in
+// rt_shade.hpp, shared with shade.hip.  shade_sample below keeps its own text of the shaders after the hit: routing it through
+// rt_shade.hpp's shade_unlit / shade_lit changed the instruction order and spill counts of modes 3 and 5-8)
 
 // one sample of one pixel -> float colour 0..255 per channel + alpha (TraceRays body, Tracer.cu:482-593).
 // Every lane of the wave calls this (inactive lanes trace nothing) because trace_ray votes with ballots; the shadow

@@ -113,7 +113,8 @@ typedef struct rt_scene {
 enum {
     RT_OK = 0,
     RT_ERR_INVALID_ARGUMENT = -1,
-    RT_ERR_UNSUPPORTED = -2,       /* (no option of the built paths returns it any more; kept for ABI stability) */
+    RT_ERR_UNSUPPORTED = -2,       /* rt_shade_frame: RT_RENDER_BOXTESTS / RT_RENDER_TRIANGLE_TESTS (a hit record carries no test
+                                    * counts); no option of the build and trace paths returns it */
     RT_ERR_TOO_LARGE = -3,         /* n exceeds the 29-bit child index of Node (Common.cuh:152-159) */
     RT_ERR_BUILD_INCOMPLETE = -4,  /* (kept for ABI stability: rt_run_sah_build is asynchronous since round 4 and reports through the status word) */
     RT_ERR_HIP_BASE = -1000        /* -(hipError_t) + RT_ERR_HIP_BASE */
@@ -510,6 +511,56 @@ int rt_sort_rays(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint
 int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
                               uint32_t num_indices, rt_hit* hits, int mode, uint32_t num_primitives, uint64_t* counters,
                               void* stream);
+
+/* ---- deferred shading (no reference counterpart: the reference shades inside TraceRays, Tracer.cu:471-595).  The ray queries
+ * give (t, primitive_id, u, v) records; these two calls turn records into rt_trace's frames:
+ *   rt_generate_camera_rays -> rt_intersect_rays(closest) -> [rt_generate_shadow_rays -> rt_intersect_rays(any hit)] ->
+ *   rt_shade_frame            (the bracketed pair for RT_RENDER_TEXTURE_LIT_SHADOWS only)
+ *
+ * rt_generate_shadow_rays writes shadow_rays[i] for i < num_rays at the index of its primary ray, so the row-major or tiled
+ * layout carries over.  light: HOST float[3] (rt_scene.light).
+ *   Hit (hits[i].primitive_id < num_triangles, and rays[i] alive: tmin <= tmax, no NaN in origin or direction).  float32, every
+ *   operation rounded on its own (no fused multiply-add), IEEE division and square root:
+ *     hp = origin + dir * t                          per component, t = hits[i].t
+ *     l  = light - hp
+ *     to_light = sqrtf((l.x*l.x + l.y*l.y) + l.z*l.z)
+ *     linv = 1.0f / to_light
+ *     shadow ray: origin = hp, dir = l * linv, tmin = 0.001f, tmax = to_light
+ *   -- the expressions, in the order, that rt_trace's RT_RENDER_TEXTURE_LIT_SHADOWS sample compiles (a + b + c is (a + b) + c).
+ *   Miss, or a dead primary ray: a dead ray, origin 0, dir 0, tmin 0, tmax -1.
+ *   A shadow ray is occluded when rt_intersect_rays(..., RT_RAY_ANY_HIT) returns a hit for it.  rt_trace decides shadow with a
+ *   closest-hit traversal; any hit accepts a triangle exactly where closest hit does, so the boolean is the same.
+ *   One divergence: with the hit point at the light (to_light = 0: a NaN direction) or within 0.001 of it (tmin > tmax) the
+ *   shadow ray is dead for the query, i.e. unshadowed, while rt_trace still runs its traversal there.
+ *
+ * rt_shade_frame: one RGBA8 pixel from the spp records of each pixel -- rt_trace's stratified sample order, its float sums
+ * (sum += sample; sum / (float)spp), its float -> u8 conversion; row 0 first, pitch 4*w.  spp in {1, 4, 16}; layout and the
+ * index of sample s of pixel (x, y) are rt_generate_camera_rays's (tiled: off-frame lanes of edge tiles are not read and write
+ * nothing).  Inputs: scene (attributes, materials, textures, light and the three counts; scene->camera is NOT read), the
+ * caller's triangles[num_triangles] (no tree), rays, hits, and shadow_hits (required for RT_RENDER_TEXTURE_LIT_SHADOWS --
+ * only its primitive_id is read: < num_triangles = occluded -- and ignored otherwise).
+ *   A record is a hit iff primitive_id < num_triangles.  Anything else (RT_MISS, garbage, the record of a dead ray) shades as
+ *   rt_trace's miss, whatever its other fields hold.
+ *   A hit is shaded as rt_trace shades it (Tracer.cu:506-593) from the ray rays[i] with tmax = hits[i].t, barycentrics
+ *   (hits[i].u, hits[i].v), the triangle triangles[primitive_id] and attribute corners 0, 1, 2 in the caller's order
+ *   (rotation 0), spread = 2.0f / w; material and texture indices are range-checked as in rt_trace.  RT_RENDER_DEPTH takes
+ *   max_depth from the ray's own tmax (rt_generate_camera_rays sets it to camera->max_depth).
+ *   Render types: RT_RENDER_DEPTH, MATERIAL_ID, LODS, DIFFUSE, TEXTURE, TEXTURE_LIT, TEXTURE_LIT_SHADOWS.  RT_RENDER_BOXTESTS
+ *   and RT_RENDER_TRIANGLE_TESTS need per-ray test counts, which a record does not carry: RT_ERR_UNSUPPORTED, nothing runs.
+ *   The frame is a function of the records and the caller's data only; it does not depend on which tree produced the hits.
+ *   Every single-triangle leaf stores the caller's corners unrotated (refit notes above), split references included, so on
+ *   every non-pair tree (LBVH, hybrid, SAH, SAH with splits) the pipeline's frame equals rt_trace's BYTE FOR BYTE.  On pair
+ *   trees the records were computed on rotated corners and mapped back: the frame equals rt_trace's up to float32 rounding.
+ * Both calls are asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable).  num_rays = 0 / w*h = 0:
+ * nothing runs.  Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): null pointers (scene, triangles,
+ * rays, hits, rgba8, light, shadow_rays; attributes / materials / textures where rt_trace requires them), rays, hits,
+ * shadow_rays or shadow_hits not 16-byte aligned, rgba8 or triangles not 4-byte aligned, a bad spp, layout or render_type,
+ * RT_RENDER_TEXTURE_LIT_SHADOWS with a null shadow_hits. */
+int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
+                            const float* light, rt_ray* shadow_rays, void* stream);
+int rt_shade_frame(const rt_scene* scene, const rt_triangle* triangles, uint32_t num_triangles, const rt_ray* rays,
+                   const rt_hit* hits, const rt_hit* shadow_hits, uint32_t w, uint32_t h, uint32_t spp, int layout,
+                   int render_type, uint8_t* rgba8, void* stream);
 
 /* static string for a return code */
 const char* rt_error_string(int code);
