@@ -8,7 +8,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
-(``ClosestPoints``: the nearest triangle to each point, through any built tree), and ray sorting (``SortRays``: a coherence
+(``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
+``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -63,6 +64,11 @@ POINT_QUERY = np.dtype([("p", "<f4", 3), ("dist2_max", "<f4")])                 
 POINT_HIT = np.dtype([("dist2", "<f4"), ("primitive_id", "<u4"), ("u", "<f4"), ("v", "<f4")])              # 16 B
 assert POINT_QUERY.itemsize == 16 and POINT_HIT.itemsize == 16
 RT_POINT_STACK_OVERFLOW = 1
+# range queries (rt_range_count / rt_range_collect): sphere queries are POINT_QUERY records, box queries RANGE_BOX records
+RANGE_BOX = np.dtype([("lo", "<f4", 3), ("pad0", "<u4"), ("hi", "<f4", 3), ("pad1", "<u4")])                # 32 B
+assert RANGE_BOX.itemsize == 32
+kRangeSphere, kRangeBox = 0, 1
+RT_RANGE_STACK_OVERFLOW, RT_RANGE_TRUNCATED = 1, 2
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -137,6 +143,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
+           "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
@@ -207,6 +214,12 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32, vp, vp]
     L.rt_closest_points.restype = i32
     L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
+    L.rt_range_scratch_bytes.restype = ctypes.c_size_t
+    L.rt_range_scratch_bytes.argtypes = [u32]
+    L.rt_range_count.restype = i32
+    L.rt_range_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, i32, vp, vp, vp, vp, vp]
+    L.rt_range_collect.restype = i32
+    L.rt_range_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, i32, vp, vp, vp, vp, vp, vp]
     L.rt_ray_sort_scratch_bytes.restype = ctypes.c_size_t
     L.rt_ray_sort_scratch_bytes.argtypes = [u32]
     L.rt_ray_sort_layout_get.restype = i32
@@ -572,6 +585,89 @@ def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, cou
 def point_status(status) -> int:
     """The RT_POINT_* flags ClosestPoints ORed into `status` (copies the word back: waits for the work queued before it)."""
     return int(to_host(status, np.uint32, 1)[0])
+
+
+def RangeScratchBytes(num_queries: int) -> int:
+    """rt_range_scratch_bytes: device bytes of RangeCount's scratch (8 bytes per 256 queries, 256-byte aligned)."""
+    return int(lib().rt_range_scratch_bytes(int(num_queries)))
+
+
+def _range_batch(queries, shape: int) -> int:
+    rec = {kRangeSphere: 16, kRangeBox: 32}.get(int(shape))
+    if rec is None:
+        raise ValueError("shape must be kRangeSphere or kRangeBox")
+    if not queries.is_contiguous() or _nbytes(queries) % rec:
+        raise ValueError(f"queries must be a contiguous device buffer of {rec}-byte records")
+    return _nbytes(queries) // rec
+
+
+def RangeCount(triangles, nodes, root: int, count: int, queries, offsets, *, shape: int = kRangeSphere, scratch=None,
+               counters=None, status=None, stream=None) -> int:
+    """rt_range_count: offsets[0 .. N] (a contiguous device int64 tensor of >= N + 1 words) = the exclusive prefix sum of the
+    number of triangles each query matches; offsets[N] is the total.  `queries`: kRangeSphere -- 16-byte POINT_QUERY records
+    (p, dist2_max), e.g. float32 [N, 4]; kRangeBox -- 32-byte RANGE_BOX records (lo, -, hi, -), e.g. float32 [N, 8].  Any tree
+    Trace() takes.  scratch: >= RangeScratchBytes(N) bytes, 256-byte aligned (device_bytes; taken from torch's allocator when
+    None).  counters: optional int64[4] ([0] box tests, [1] triangle tests).  status: optional device uint32 the call ORs
+    RT_RANGE_* flags into (see range_status).  Asynchronous on `stream`, nothing is read back.  Returns N."""
+    n = _range_batch(queries, shape)
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    if scratch is None:
+        scratch = device_bytes(RangeScratchBytes(n), queries.device)
+    elif _nbytes(scratch) < RangeScratchBytes(n):
+        raise ValueError(f"scratch must hold RangeScratchBytes({n}) bytes")
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
+    _check(lib().rt_range_count(ctypes.byref(a), _ptr(queries) or _ptr(scratch), n, int(shape), _ptr(offsets), _ptr(scratch), _ptr(counters),
+                                _ptr(status), _stream_ptr(stream)), "rt_range_count")
+    return n
+
+
+def RangeCollect(triangles, nodes, root: int, count: int, queries, offsets, ids, *, shape: int = kRangeSphere, counts=None,
+                 counters=None, status=None, stream=None) -> int:
+    """rt_range_collect: query i writes the ids of its first offsets[i+1] - offsets[i] matches at ids[offsets[i]:] (`ids`: a
+    contiguous device int32 / uint32 tensor the offsets stay inside -- the caller's contract; `offsets`: int64 [N + 1] from
+    RangeCount, or i * K for a fixed K per query).  counts: optional device int32 [N], each query's true match count.
+    A query with more matches than room sets RT_RANGE_TRUNCATED in `status`.  Ids come in traversal order (unspecified but
+    deterministic); on non-split trees each matching triangle appears exactly once.  Asynchronous on `stream`.  Returns N."""
+    n = _range_batch(queries, shape)
+    if not offsets.is_contiguous() or not ids.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, ids a contiguous device buffer")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_range_collect(ctypes.byref(a), _ptr(queries), n, int(shape), _ptr(offsets), _ptr(ids), _ptr(counts),
+                                  _ptr(counters), _ptr(status), _stream_ptr(stream)), "rt_range_collect")
+    return n
+
+
+def range_status(status) -> int:
+    """The RT_RANGE_* flags RangeCount / RangeCollect ORed into `status` (copies the word back: waits for the work queued before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
+
+
+def RangeQuery(triangles, nodes, root: int, count: int, queries, *, shape: int = kRangeSphere, counters=None, status=None,
+               stream=None):
+    """Everything each query matches, as CSR: RangeCount, then the total offsets[N] is READ BACK TO THE HOST -- one
+    synchronisation of `stream` per call, the only one -- to allocate the id array, then RangeCollect.  Returns (offsets, ids):
+    torch int64 [N + 1] and int32 [total] device tensors; query i owns ids[offsets[i]:offsets[i+1]].  A caller who cannot
+    afford the synchronisation (a captured graph, a fixed budget per query) uses RangeCount / RangeCollect directly.  With
+    `counters`, the tests of both passes are added (twice one traversal)."""
+    torch = _torch()
+    n = _range_batch(queries, shape)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=queries.device)
+    RangeCount(triangles, nodes, root, count, queries, offsets, shape=shape, counters=counters, status=status, stream=stream)
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            total = int(offsets[n].item())
+    else:
+        total = int(offsets[n].item())
+    ids = torch.empty(max(total, 1), dtype=torch.int32, device=queries.device)[:total]
+    RangeCollect(triangles, nodes, root, count, queries, offsets, ids, shape=shape, counters=counters, status=status,
+                 stream=stream)
+    return offsets, ids
 
 
 def RaySortScratchBytes(num_rays: int) -> int:

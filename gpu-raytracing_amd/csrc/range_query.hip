@@ -1,0 +1,426 @@
+// range_query.hip -- rt_range_count / rt_range_collect: every triangle within a radius of a point (RT_RANGE_SPHERE) or whose
+// vertex box overlaps a box (RT_RANGE_BOX), through any tree rt_intersect_rays takes (semantics: rt_abi.h, range-query block;
+// DESIGN section 13).  The library's first query with a data-dependent output length: the result is CSR -- offsets[0..n] by a
+// 64-bit device scan of the per-query counts, then ids written per query segment.
+//
+// range_query_kernel<SHAPE, COLLECT> keeps the frame of point_query_kernel: one lane per query, 64 consecutive queries per
+// wave, kTraceWaves waves (256 queries) per workgroup, xcd_chunk_block, the query in one (sphere) or two (box) 16-byte
+// loads, a leaf in four 16-byte requests, rt_traverse.hpp's wave-level two phases (box steps while enough lanes hold a box
+// run, then one leaf step), exact per-workgroup counters.  What differs from the point query:
+//   * the region never shrinks, so nothing is ordered and nothing re-culled: a stack entry is the 4-byte entry alone (a box
+//     run child : 29 | count : 3, or a leaf index : 29 | 0), 16 entries in an LDS column per lane (16 KB per workgroup) + 48
+//     private; the first surviving slot of a run is visited next, the others are pushed in slot order;
+//   * a slot is skipped iff its box fails the shape's test (sphere: boxdist2 > dist2_max; box: the closed overlap test), a
+//     triangle matches by the exact predicate of the header; both instantiations of a shape run this one traversal, so the
+//     count and the collect call visit the same leaves in the same order and cannot disagree;
+//   * a push onto a full stack of 64 is dropped and flagged (RT_RANGE_STACK_OVERFLOW): the result is then a subset;
+//   * COLLECT = false: the lane's match count goes through a workgroup scan (two 21-bit limbs through block_excl_scan_u32);
+//     offsets[i] gets the workgroup-local exclusive prefix and the workgroup's total goes to the scratch.  range_scan_kernel
+//     (one workgroup, 64-bit through three limbs) turns the totals into exclusive prefixes and writes offsets[n];
+//     range_add_kernel adds each workgroup's prefix to its 256 offsets.  Three launches, nothing read back;
+//   * COLLECT = true: the lane stores match j < offsets[i+1] - offsets[i] at ids[offsets[i] + j] -- its own segment, in its
+//     own traversal order, plain 4-byte vector stores, no atomics on the output -- and keeps counting beyond the room
+//     (counts[i], RT_RANGE_TRUNCATED).
+// Compiled with -ffp-contract=off and IEEE division: every float operation is the one rt_abi.h writes down.
+#include "rt_device.hpp"
+#include "rt_launch.hpp"
+#include "rt_traverse.hpp"
+
+static_assert(sizeof(rt_range_box) == 32 && offsetof(rt_range_box, hi) == 16, "rt_range_box: two 16-byte halves (lo | hi)");
+static_assert(sizeof(rt_point_query) == 16, "rt_point_query: one 16-byte record");
+
+namespace rt {
+
+namespace {
+
+constexpr int kRgStackLds = 16;        // LDS-resident entries per lane: 16 x 4 B x 256 lanes = 16 KB per workgroup
+constexpr uint32_t kRgBlock = kTraceWaves * 64;   // queries per workgroup = offsets per block sum
+
+struct RangeParams {
+    const rt_node* nodes;
+    const rt_triangle_pair* leaves;
+    uint32_t root, count;
+    const float4* queries;        // sphere: (p, dist2_max); box: (lo, -), (hi, -)
+    uint32_t num_queries;
+    uint64_t* offsets;            // count: out, workgroup-local prefixes; collect: in
+    uint64_t* block_sums;         // count: out, one total per workgroup
+    uint32_t* ids;                // collect
+    uint32_t* counts;             // collect, optional
+    unsigned long long* counters;
+    uint32_t* status;
+};
+
+// exclusive scan of one 64-bit value per thread through block_excl_scan_u32, LIMBS limbs of 21 bits: a limb's block sum stays
+// below 2^31 for NT <= 1024, so the 32-bit scans are exact and the result is exact for values below 2^(21 LIMBS).
+// All NT threads must call it (rt_device.hpp: full waves).
+template <int NT, int LIMBS>
+__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint32_t* ws, uint64_t* total)
+{
+    uint64_t r = 0, t = 0;
+#pragma unroll
+    for (int l = 0; l < LIMBS; l++) {
+        uint32_t tl;
+        const uint32_t e = block_excl_scan_u32<NT>((uint32_t)(v >> (21 * l)) & 0x1FFFFFu, ws, &tl);
+        r += (uint64_t)e << (21 * l);
+        t += (uint64_t)tl << (21 * l);
+    }
+    *total = t;
+    return r;
+}
+
+__device__ __forceinline__ float rg_dot(float ax, float ay, float az, float bx, float by, float bz)
+{
+    return (ax * bx + ay * by) + az * bz;
+}
+// a denominator that is not > 0 (0, negative, NaN) gives weight 0; else the IEEE quotient
+__device__ __forceinline__ float rg_guard(float num, float den) { return den > 0.0f ? num / den : 0.0f; }
+// by selects: NaN -> 0, -0 -> +0
+__device__ __forceinline__ float rg_clamp01(float t)
+{
+    t = t > 0.0f ? t : 0.0f;
+    return t < 1.0f ? t : 1.0f;
+}
+
+struct Tri {
+    float ax, ay, az, bx, by, bz, cx, cy, cz;
+};
+
+// dist2 of p to q after q is clamped into the triangle's vertex box (fmaxf, then fminf)
+__device__ __forceinline__ float rg_clamped(float px, float py, float pz, float qx, float qy, float qz, const Tri& t)
+{
+    const float lox = fminf(fminf(t.ax, t.bx), t.cx), loy = fminf(fminf(t.ay, t.by), t.cy), loz = fminf(fminf(t.az, t.bz), t.cz);
+    const float hix = fmaxf(fmaxf(t.ax, t.bx), t.cx), hiy = fmaxf(fmaxf(t.ay, t.by), t.cy), hiz = fmaxf(fmaxf(t.az, t.bz), t.cz);
+    const float dx = px - fminf(fmaxf(qx, lox), hix);
+    const float dy = py - fminf(fmaxf(qy, loy), hiy);
+    const float dz = pz - fminf(fmaxf(qz, loz), hiz);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// d2(p, a, b, c) of rt_abi.h's closest-point block: Ericson's ClosestPtPointTriangle (RTCD 5.1.5), the clamp into the vertex
+// box, the squared distance -- point_query.hip's routine without the weights, operation for operation.
+__device__ __forceinline__ float range_tri_d2(float px, float py, float pz, const Tri& t)
+{
+    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
+    const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
+    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
+    const float d1 = rg_dot(abx, aby, abz, apx, apy, apz), d2 = rg_dot(acx, acy, acz, apx, apy, apz);
+    if (d1 <= 0.0f && d2 <= 0.0f) return rg_clamped(px, py, pz, t.ax, t.ay, t.az, t);                 // vertex region A
+    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
+    const float d3 = rg_dot(abx, aby, abz, bpx, bpy, bpz), d4 = rg_dot(acx, acy, acz, bpx, bpy, bpz);
+    if (d3 >= 0.0f && d4 <= d3) return rg_clamped(px, py, pz, t.bx, t.by, t.bz, t);                   // vertex region B
+    const float vc = d1 * d4 - d3 * d2;
+    const float t_ab = rg_clamp01(rg_guard(d1, d1 - d3));
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f)                                                       // edge region AB
+        return rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
+    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
+    const float d5 = rg_dot(abx, aby, abz, cpx, cpy, cpz), d6 = rg_dot(acx, acy, acz, cpx, cpy, cpz);
+    if (d6 >= 0.0f && d5 <= d6) return rg_clamped(px, py, pz, t.cx, t.cy, t.cz, t);                   // vertex region C
+    const float vb = d5 * d2 - d1 * d6;
+    const float t_ac = rg_clamp01(rg_guard(d2, d2 - d6));
+    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f)                                                       // edge region AC
+        return rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    const float t_bc = rg_clamp01(rg_guard(e43, e43 + e56));
+    const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
+    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f)                                                     // edge region BC
+        return rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
+    const float s = (va + vb) + vc;
+    if (s > 0.0f) {                                                                                   // face region
+        const float fv = vb / s, fw = vc / s;
+        return rg_clamped(px, py, pz, (t.ax + abx * fv) + acx * fw, (t.ay + aby * fv) + acy * fw, (t.az + abz * fv) + acz * fw, t);
+    }
+    // degenerate face: the nearest of the three edge points
+    float best = rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
+    const float g_ac = rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
+    if (g_ac < best) best = g_ac;
+    const float g_bc = rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
+    if (g_bc < best) best = g_bc;
+    return best;
+}
+
+// the caller's corners of a leaf triangle stored as (s0, s1, s2) with rotation r (RotateAttributes' corner map):
+// r = 1: (c0, c1, c2) = (s1, s2, s0); r = 2: (s2, s0, s1); else as stored
+__device__ __forceinline__ Tri unrotate(float s0x, float s0y, float s0z, float s1x, float s1y, float s1z, float s2x, float s2y,
+                                        float s2z, uint32_t r)
+{
+    Tri t;
+    if (r == 1) t = {s1x, s1y, s1z, s2x, s2y, s2z, s0x, s0y, s0z};
+    else if (r == 2) t = {s2x, s2y, s2z, s0x, s0y, s0z, s1x, s1y, s1z};
+    else t = {s0x, s0y, s0z, s1x, s1y, s1z, s2x, s2y, s2z};
+    return t;
+}
+
+// boxdist2 of a slot: g = max(lo - p, p - hi, 0) per axis, squared and summed in d2's order
+__device__ __forceinline__ float box_d2(const uint4& a, const uint4& b, float px, float py, float pz)
+{
+    const float gx = fmaxf(fmaxf(__uint_as_float(a.x) - px, px - __uint_as_float(b.x)), 0.0f);
+    const float gy = fmaxf(fmaxf(__uint_as_float(a.y) - py, py - __uint_as_float(b.y)), 0.0f);
+    const float gz = fmaxf(fmaxf(__uint_as_float(a.z) - pz, pz - __uint_as_float(b.z)), 0.0f);
+    return (gx * gx + gy * gy) + gz * gz;
+}
+
+// the query region, per shape: keep(slot box) and match(triangle).  SPHERE holds (p, dist2_max), BOX holds (lo, hi).
+template <int SHAPE> struct Region;
+template <> struct Region<RT_RANGE_SPHERE> {
+    float px, py, pz, r;
+    __device__ __forceinline__ bool load(const float4* q, uint64_t i)
+    {
+        const float4 v = q[i];
+        px = v.x; py = v.y; pz = v.z; r = v.w;
+        // not traced: a non-finite p, a NaN or negative dist2_max  (r >= 0 is false for NaN)
+        return __builtin_isfinite(px) & __builtin_isfinite(py) & __builtin_isfinite(pz) & (r >= 0.0f);
+    }
+    __device__ __forceinline__ bool keep(const uint4& a, const uint4& b) const { return !(box_d2(a, b, px, py, pz) > r); }
+    // the caller's corners in the caller's order: (s0, s1, s2) stored with rotation rot
+    __device__ __forceinline__ bool match(float s0x, float s0y, float s0z, float s1x, float s1y, float s1z, float s2x, float s2y,
+                                          float s2z, uint32_t rot) const
+    {
+        return range_tri_d2(px, py, pz, unrotate(s0x, s0y, s0z, s1x, s1y, s1z, s2x, s2y, s2z, rot)) <= r;
+    }
+};
+template <> struct Region<RT_RANGE_BOX> {
+    float lx, ly, lz, hx, hy, hz;
+    __device__ __forceinline__ bool load(const float4* q, uint64_t i)
+    {
+        const float4 l = q[2 * i], h = q[2 * i + 1];
+        lx = l.x; ly = l.y; lz = l.z; hx = h.x; hy = h.y; hz = h.z;
+        // not traced: a NaN component, or lo > hi on an axis  (lo <= hi is false for NaN)
+        return (lx <= hx) & (ly <= hy) & (lz <= hz);
+    }
+    // closed overlap on every axis: tlo <= hi && thi >= lo
+    __device__ __forceinline__ bool over(float tlx, float tly, float tlz, float thx, float thy, float thz) const
+    {
+        return (tlx <= hx) & (tly <= hy) & (tlz <= hz) & (thx >= lx) & (thy >= ly) & (thz >= lz);
+    }
+    __device__ __forceinline__ bool keep(const uint4& a, const uint4& b) const
+    {
+        return over(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(b.x), __uint_as_float(b.y),
+                    __uint_as_float(b.z));
+    }
+    // fminf / fmaxf of the three corners do not depend on their order (a -0 / +0 pick compares equal): no unrotate
+    __device__ __forceinline__ bool match(float s0x, float s0y, float s0z, float s1x, float s1y, float s1z, float s2x, float s2y,
+                                          float s2z, uint32_t) const
+    {
+        return over(fminf(fminf(s0x, s1x), s2x), fminf(fminf(s0y, s1y), s2y), fminf(fminf(s0z, s1z), s2z),
+                    fmaxf(fmaxf(s0x, s1x), s2x), fmaxf(fmaxf(s0y, s1y), s2y), fmaxf(fmaxf(s0z, s1z), s2z));
+    }
+};
+
+typedef uint32_t RgSpill[kStackMax - kRgStackLds];
+
+// the entry a slot refers to: a leaf (index : 29 | 0) or a box run (child : 29 | count : 3)
+__device__ __forceinline__ uint32_t slot_entry(const uint4& a, const uint4& b)
+{
+    return (b.w >> 29) == RT_CHILD_TRI ? (b.w & kIndexMask) : ((b.w & kIndexMask) | (a.w & ~kIndexMask));
+}
+
+template <int SHAPE, bool COLLECT>
+__global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA) void range_query_kernel(RangeParams p)
+{
+    __shared__ uint32_t stack_lds[kTraceWaves][kRgStackLds][64];
+    __shared__ unsigned long long csum[2];
+    __shared__ uint32_t ws[kTraceWaves + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
+    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    const bool in_range = i < p.num_queries;
+    if (p.counters && threadIdx.x < 2) csum[threadIdx.x] = 0ull;   // (kernel argument: the same for every thread)
+
+    Region<SHAPE> rg = {};
+    bool live = false;
+    if (in_range) live = rg.load(p.queries, i) && p.count > 0;
+
+    // collect: the lane's segment [out, out + room)
+    uint32_t* out = nullptr;
+    uint32_t room = 0;
+    if (COLLECT && in_range) {
+        const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
+        const uint64_t d = o1 > o0 ? o1 - o0 : 0ull;
+        room = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
+        out = p.ids + o0;
+    }
+
+    lds_u32* const col = (lds_u32*)&stack_lds[wave][0][lane];
+    RgSpill spill;
+    int sp = 0;
+    bool overflow = false;            // a push was dropped: the result is a subset
+    uint32_t found = 0;               // matches so far (collect: also beyond the room)
+    uint32_t box_tests = 0, tri_tests = 0;
+    uint32_t cur = (p.root & kIndexMask) | (p.count << 29);
+
+    auto next_from_stack = [&]() {
+        if (sp == 0) { live = false; return; }
+        --sp;
+        cur = sp < kRgStackLds ? col[sp * 64] : spill[sp - kRgStackLds];
+    };
+    auto emit = [&](uint32_t id) {
+        if (COLLECT) {
+            if (found < room) out[found] = id;
+        }
+        found++;
+    };
+    auto leaf_step = [&]() {
+        tri_tests++;
+        const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + (cur & kIndexMask));
+        uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
+        // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (rt_traverse.hpp)
+        asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
+                          "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
+        if (rg.match(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
+                     __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
+                     __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z), l2.w & 0xFFFFu))
+            emit(l0.w);
+        if (l1.w == l0.w + 1u) {              // a pair record: B = (v2, v1, v3) with rotations[1]
+            if (rg.match(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
+                         __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
+                         __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z), l2.w >> 16))
+                emit(l1.w);
+        }
+        next_from_stack();
+    };
+    auto box_step = [&]() {
+        const uint32_t first = cur & kIndexMask, cnt = cur >> 29;
+        uint32_t next = kNoNear;
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint4* np = reinterpret_cast<const uint4*>(p.nodes + first + k);
+            const uint4 a = np[0], b = np[1];
+            const uint32_t type = b.w >> 29;
+            if (type == RT_CHILD_NONE) continue;
+            box_tests++;
+            const uint32_t e = slot_entry(a, b);
+            if (!rg.keep(a, b) || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // outside the region, or an empty run
+            if (next == kNoNear) { next = e; continue; }   // the first survivor is visited next, the others wait
+            if (sp < kRgStackLds) col[sp * 64] = e;
+            else if (sp < kStackMax) spill[sp - kRgStackLds] = e;
+            else overflow = true;             // dropped: what lies below it is missing from the result
+            sp = min(sp + 1, kStackMax);
+        }
+        if (next != kNoNear) cur = next;
+        else next_from_stack();
+    };
+
+    while (true) {
+        uint64_t stepping, parked;
+        while (true) {                        // box phase: step while enough lanes hold a box run
+            stepping = __builtin_amdgcn_ballot_w64(live && (cur >> 29) != 0);
+            parked = __builtin_amdgcn_ballot_w64(live && (cur >> 29) == 0);
+            if (stepping == 0 || __popcll(stepping) * kParkDen < __popcll(parked) * kParkNum) break;
+            if (live && (cur >> 29) != 0) box_step();
+        }
+        if ((stepping | parked) == 0) break;
+        if (live && (cur >> 29) == 0) leaf_step();   // leaf phase: every lane that holds a leaf
+    }
+
+    uint32_t flags = overflow ? (uint32_t)RT_RANGE_STACK_OVERFLOW : 0u;
+    if (COLLECT) {
+        if (in_range && p.counts) p.counts[i] = found;
+        if (found > room) flags |= (uint32_t)RT_RANGE_TRUNCATED;
+    } else {
+        // the workgroup's exclusive scan of the counts (a count is below 2^32: two 21-bit limbs); lanes past the batch add 0
+        uint64_t total;
+        const uint64_t ex = block_excl_scan_u64<kTraceWaves * 64, 2>(found, ws, &total);
+        if (in_range) p.offsets[i] = ex;
+        if (threadIdx.x == 0) p.block_sums[vb] = total;
+    }
+    if (p.status) {
+        const bool any_over = __builtin_amdgcn_ballot_w64((flags & RT_RANGE_STACK_OVERFLOW) != 0) != 0;
+        const bool any_trunc = __builtin_amdgcn_ballot_w64((flags & RT_RANGE_TRUNCATED) != 0) != 0;
+        const uint32_t wf = (any_over ? (uint32_t)RT_RANGE_STACK_OVERFLOW : 0u) | (any_trunc ? (uint32_t)RT_RANGE_TRUNCATED : 0u);
+        if (wf && lane == 0) atomicOr(p.status, wf);
+    }
+    if (p.counters) {
+        const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
+        __syncthreads();                      // csum's zeroes
+        if (lane == 0) {
+            atomicAdd(&csum[0], (unsigned long long)bsum);
+            atomicAdd(&csum[1], (unsigned long long)tsum);
+        }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            const unsigned long long v = csum[threadIdx.x];
+            if (v) atomicAdd(&p.counters[threadIdx.x], v);
+        }
+    }
+}
+
+// in-place exclusive scan of the workgroups' totals (one workgroup; a total is below 2^40, three limbs carry 2^63);
+// *total = their sum = offsets[n]
+__global__ __launch_bounds__(1024) void range_scan_kernel(uint64_t* __restrict__ block_sums, uint32_t nblocks,
+                                                          uint64_t* __restrict__ total)
+{
+    __shared__ uint32_t ws[20];
+    uint64_t running = 0;
+    for (uint32_t c = 0; c < nblocks; c += 1024) {
+        const uint32_t i = c + threadIdx.x;
+        const uint64_t v = i < nblocks ? block_sums[i] : 0ull;
+        uint64_t chunk;
+        const uint64_t ex = block_excl_scan_u64<1024, 3>(v, ws, &chunk);
+        if (i < nblocks) block_sums[i] = running + ex;
+        running += chunk;
+    }
+    if (threadIdx.x == 0) *total = running;
+}
+
+// offsets[i] += the prefix of its workgroup
+__global__ __launch_bounds__(256) void range_add_kernel(uint64_t* __restrict__ offsets, const uint64_t* __restrict__ block_sums,
+                                                        uint32_t n)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) offsets[i] += block_sums[i / kRgBlock];
+}
+
+inline uint32_t range_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kRgBlock - 1) / kRgBlock); }
+
+RangeParams range_params(const rt_accel& as, const void* queries, uint32_t num_queries, uint64_t* counters, uint32_t* status)
+{
+    RangeParams p = {};
+    p.nodes = as.nodes;
+    p.leaves = as.triangles;
+    p.root = as.root;
+    p.count = as.count;
+    p.queries = reinterpret_cast<const float4*>(queries);
+    p.num_queries = num_queries;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.status = status;
+    return p;
+}
+
+}  // namespace
+
+size_t range_scratch_bytes(uint32_t num_queries)
+{
+    const size_t blocks = range_blocks(num_queries);
+    return ((blocks ? blocks : 1) * sizeof(uint64_t) + 255) / 256 * 256;
+}
+
+hipError_t launch_range_count(const rt_accel& as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets,
+                              void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st)
+{
+    RangeParams p = range_params(as, queries, num_queries, counters, status);
+    p.offsets = offsets;
+    p.block_sums = static_cast<uint64_t*>(scratch);
+    const uint32_t blocks = range_blocks(num_queries);
+    if (blocks) {
+        if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, false><<<blocks, kRgBlock, 0, st>>>(p);
+        else range_query_kernel<RT_RANGE_BOX, false><<<blocks, kRgBlock, 0, st>>>(p);
+    }
+    range_scan_kernel<<<1, 1024, 0, st>>>(p.block_sums, blocks, offsets + num_queries);
+    if (blocks) range_add_kernel<<<(uint32_t)(((uint64_t)num_queries + 255) / 256), 256, 0, st>>>(offsets, p.block_sums, num_queries);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
+                                uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status, hipStream_t st)
+{
+    RangeParams p = range_params(as, queries, num_queries, counters, status);
+    p.offsets = const_cast<uint64_t*>(offsets);   // (the collect instantiations only read them)
+    p.ids = ids;
+    p.counts = counts;
+    const uint32_t blocks = range_blocks(num_queries);
+    if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, true><<<blocks, kRgBlock, 0, st>>>(p);
+    else range_query_kernel<RT_RANGE_BOX, true><<<blocks, kRgBlock, 0, st>>>(p);
+    return hipGetLastError();
+}
+
+}  // namespace rt

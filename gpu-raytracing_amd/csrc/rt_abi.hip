@@ -425,6 +425,40 @@ int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_poin
     return hip_rc(launch_point_query(*as, queries, hits, num_queries, counters, status, static_cast<hipStream_t>(stream)));
 }
 
+size_t rt_range_scratch_bytes(uint32_t num_queries) { return range_scratch_bytes(num_queries); }
+
+// the checks both range entry points share
+static int range_args(const rt_accel* as, const void* queries, int shape, const uint64_t* offsets, const uint32_t* status)
+{
+    if (!as || !queries || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (shape != RT_RANGE_SPHERE && shape != RT_RANGE_BOX) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(queries, 16) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    return RT_OK;
+}
+
+int rt_range_count(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets, void* scratch,
+                   uint64_t* counters, uint32_t* status, void* stream)
+{
+    const int rc = range_args(as, queries, shape, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    // (num_queries = 0 still launches the scan's one workgroup: offsets[0] = 0)
+    return hip_rc(launch_range_count(*as, queries, num_queries, shape, offsets, scratch, counters, status,
+                                     static_cast<hipStream_t>(stream)));
+}
+
+int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
+                     uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
+{
+    const int rc = range_args(as, queries, shape, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!ids || misaligned(ids, 4) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_range_collect(*as, queries, num_queries, shape, offsets, ids, counts, counters, status,
+                                       static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
                             const float* light, rt_ray* shadow_rays, void* stream)
 {
@@ -500,6 +534,9 @@ const char* rt_version_string(void)
            "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
            "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
+           "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "
+           "(16 in LDS), one traversal compiled for count and collect, CSR output by a 64-bit device scan (workgroup scan in "
+           "the count kernel + one workgroup over the sums + add), ids by plain stores into the query's own segment | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
            "instantiations, shadow rays as a ray batch for the any-hit query";
 }

@@ -261,4 +261,13 @@ hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st);
 hipError_t launch_point_query(const rt_accel& as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                               uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// range_query.hip: rt_range_count / rt_range_collect after their argument checks.  Count runs for num_queries = 0 too (it
+// writes offsets[0] = 0); collect is called with num_queries > 0.  queries: rt_point_query (sphere) or rt_range_box (box).
+size_t range_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned
+hipError_t launch_range_count(const rt_accel& as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets,
+                              void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_t num_queries, int shape,
+                                const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status,
+                                hipStream_t st);
+
 }  // namespace rt

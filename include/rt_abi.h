@@ -454,6 +454,67 @@ enum { RT_POINT_STACK_OVERFLOW = 1 };
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- range queries (no reference counterpart).  For each caller region: WHICH triangles touch it -- the set-valued query,
+ * through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every set is empty).
+ * The output length depends on the data, so the result is compressed sparse rows (CSR): offsets[0 .. n] (uint64) and one id
+ * array; query i owns ids[offsets[i] .. offsets[i+1]).
+ *
+ * shape RT_RANGE_SPHERE: queries is an array of rt_point_query (p, dist2_max; 16 bytes).  Triangle k matches iff
+ *   d2(p, tri[k]) <= dist2_max, with d2 EXACTLY the closest-point block's float32 routine (Ericson, the clamp into the vertex
+ *   box, the squared distance), evaluated on the caller's corners in the caller's order (pair leaves go back through
+ *   rt_triangle_pair.rotations, as there).  A triangle exactly at the radius matches; a NaN d2 (overflow) does not.
+ *   A slot is skipped iff boxdist2 > dist2_max (the closest-point block's boxdist2; never on equality).  Since
+ *   d2 >= boxdist2 holds in float32 for every box that contains the vertex box, skipping loses nothing.
+ *   Not traced (count 0, no tests counted): a non-finite component of p, a NaN dist2_max or a negative dist2_max.  +inf is a
+ *   legal radius: every triangle with a non-NaN d2 matches.
+ * shape RT_RANGE_BOX: queries is an array of rt_range_box (lo, hi; 32 bytes, the pad words are not read).  Triangle k matches
+ *   iff its vertex box overlaps [lo, hi] on every axis with closed comparisons: tlo <= hi && thi >= lo, tlo / thi = fminf /
+ *   fmaxf of the three corners (a NaN coordinate is dropped by fminf / fmaxf; -0 equals +0).  This is the broad-phase candidate
+ *   set: nothing but min, max and comparisons, so nothing rounds.  A slot is skipped iff its box fails the same closed test
+ *   against [lo, hi].
+ *   Not traced: a NaN component of lo or hi, or lo > hi on an axis.
+ *
+ * Result: a SET -- no ordering promise and no tie rule.
+ *   - exact (the brute-force set over the caller's triangles, each id once) on every tree whose slot boxes contain the vertex
+ *     boxes below them: LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs, and every refitted tree;
+ *   - spatial-split trees (rt_run_sah_build with enable_splits): the leaf test is on the whole triangle, so every reported id
+ *     is a true match; but an id appears once per REFERENCE that is reached (duplicates are possible), and in box mode a
+ *     triangle is missed when every one of its clipped references lies outside the query (sphere mode: when every clipped
+ *     reference box is farther than dist2_max).  Refitting a split tree restores exactness up to the duplicates: refit writes
+ *     unclipped boxes, but the references stay.
+ *   Order: the ids of a query come in the traversal order of its lane -- deterministic for a given tree, the same in
+ *   rt_range_count and rt_range_collect (one traversal, compiled twice), otherwise unspecified.
+ *
+ * rt_range_count: offsets[0 .. num_queries] = the exclusive prefix sum of the per-query match counts; offsets[num_queries] is
+ *   the total.  64-bit: no overflow case exists.  scratch: rt_range_scratch_bytes(num_queries) bytes of device memory,
+ *   256-byte aligned, no initialisation needed (one uint64 per 256 queries: the workgroup sums of the scan).  Launches: the
+ *   traversal (which also scans the counts inside each workgroup), one workgroup over the workgroup sums, one add.
+ *   num_queries = 0 still writes offsets[0] = 0.
+ * rt_range_collect: query i writes its first min(matches, offsets[i+1] - offsets[i]) ids at ids + offsets[i] and never writes
+ *   beyond them (offsets[i+1] < offsets[i] counts as no room); ids past the last segment and segments of other queries are not
+ *   touched.  counts (optional, device uint32[num_queries]): the query's true match count, room or not.  A query with more
+ *   matches than room ORs RT_RANGE_TRUNCATED into *status; its segment then holds the first matches in traversal order.
+ *   Two call patterns: (a) everything: rt_range_count, read offsets[num_queries] back, allocate ids, rt_range_collect with the
+ *   same offsets; (b) a fixed K per query: fill offsets[i] = i * K once, one rt_range_collect pass, counts says how many of
+ *   each segment are valid (min(counts[i], K)).  num_queries = 0: nothing runs.
+ * Both calls: counters, optional device uint64[4], rt_closest_points's layout: [0] += box tests (non-NONE slots examined), [1]
+ * += triangle tests (leaf records visited); [2] / [3] are not touched.  The same query set gives the same counters in both
+ * calls.  status: optional device uint32 the calls OR flags into (the caller clears it).  Stack: 64 pending entries per query;
+ * a push beyond them is dropped and sets RT_RANGE_STACK_OVERFLOW: the result is then a subset of the true set, and since both
+ * calls drop the same pushes they still agree with each other.  Asynchronous (no host copy, no synchronisation:
+ * hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / queries / offsets / scratch (count) /
+ * ids (collect), a tree with count > 0 and a null node or leaf pointer, count > 7, an unknown shape, queries not 16-byte,
+ * offsets not 8-byte, ids / counts / status not 4-byte, scratch not 256-byte aligned. */
+typedef struct rt_range_box { rt_float3 lo; uint32_t pad0; rt_float3 hi; uint32_t pad1; } rt_range_box;
+enum { RT_RANGE_SPHERE = 0, RT_RANGE_BOX = 1 };
+enum { RT_RANGE_STACK_OVERFLOW = 1, RT_RANGE_TRUNCATED = 2 };
+size_t rt_range_scratch_bytes(uint32_t num_queries);
+int rt_range_count(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets, void* scratch,
+                   uint64_t* counters, uint32_t* status, void* stream);
+int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
+                     uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- ray sorting and indexed ray queries (no reference counterpart).  rt_intersect_rays gives a wave 64 consecutive rays, so
  * its speed depends on the caller's ray order.  rt_sort_rays computes a coherence order of a batch, rt_intersect_rays_indexed
  * traces a batch through an index list -- that order, or any list of rays still alive.
