@@ -9,7 +9,8 @@ tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
-``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), and ray sorting (``SortRays``: a coherence
+``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
+(``KNearest``: the k nearest triangles to each point, in order), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -69,6 +70,11 @@ RANGE_BOX = np.dtype([("lo", "<f4", 3), ("pad0", "<u4"), ("hi", "<f4", 3), ("pad
 assert RANGE_BOX.itemsize == 32
 kRangeSphere, kRangeBox = 0, 1
 RT_RANGE_STACK_OVERFLOW, RT_RANGE_TRUNCATED = 1, 2
+# k-nearest queries (rt_k_nearest): POINT_QUERY records in, rows of k KNN_HIT records out
+KNN_HIT = np.dtype([("dist2", "<f4"), ("primitive_id", "<u4")])                                              # 8 B
+assert KNN_HIT.itemsize == 8
+RT_KNN_MAX_K = 32
+RT_KNN_STACK_OVERFLOW = 1
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -143,7 +149,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
-           "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect",
+           "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
@@ -220,6 +226,8 @@ def lib() -> ctypes.CDLL:
     L.rt_range_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, i32, vp, vp, vp, vp, vp]
     L.rt_range_collect.restype = i32
     L.rt_range_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, i32, vp, vp, vp, vp, vp, vp]
+    L.rt_k_nearest.restype = i32
+    L.rt_k_nearest.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp]
     L.rt_ray_sort_scratch_bytes.restype = ctypes.c_size_t
     L.rt_ray_sort_scratch_bytes.argtypes = [u32]
     L.rt_ray_sort_layout_get.restype = i32
@@ -668,6 +676,34 @@ def RangeQuery(triangles, nodes, root: int, count: int, queries, *, shape: int =
     RangeCollect(triangles, nodes, root, count, queries, offsets, ids, shape=shape, counters=counters, status=status,
                  stream=stream)
     return offsets, ids
+
+
+def KNearest(triangles, nodes, root: int, count: int, queries, k: int, out, *, counters=None, status=None, stream=None) -> int:
+    """rt_k_nearest: for each POINT_QUERY record of `queries` (a contiguous device tensor of 16-byte records (p, dist2_max),
+    e.g. float32 [N, 4]) a row of k KNN_HIT records (dist2, primitive_id) in `out` (>= 8 k N bytes, e.g. float32 [N, k, 2];
+    view it as int32 for primitive_id): the k nearest triangles within dist2_max in ascending (dist2, primitive_id) order,
+    padded with {+inf, MISS}.  1 <= k <= RT_KNN_MAX_K.  Any tree Trace() takes.  counters: optional int64[4] device tensor
+    ([0] box tests, [1] triangle tests).  status: optional device uint32 the call ORs RT_KNN_STACK_OVERFLOW into (the caller
+    clears it; see knn_status).  Asynchronous on `stream`, nothing is allocated or read back.  Returns N."""
+    k = int(k)
+    if not 1 <= k <= RT_KNN_MAX_K:
+        raise ValueError(f"k must be in 1 .. {RT_KNN_MAX_K}")
+    if not queries.is_contiguous() or not out.is_contiguous() or _nbytes(queries) % 16:
+        raise ValueError("queries must be a contiguous device buffer of 16-byte records, out a contiguous device buffer")
+    n = _nbytes(queries) // 16
+    if _nbytes(out) < 8 * k * n:
+        raise ValueError(f"out must hold {n} rows of {k} 8-byte records")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_k_nearest(ctypes.byref(a), _ptr(queries), n, k, _ptr(out), _ptr(counters), _ptr(status),
+                              _stream_ptr(stream)), "rt_k_nearest")
+    return n
+
+
+def knn_status(status) -> int:
+    """The RT_KNN_* flags KNearest ORed into `status` (copies the word back: waits for the work queued before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
 
 
 def RaySortScratchBytes(num_rays: int) -> int:

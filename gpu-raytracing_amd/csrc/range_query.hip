@@ -21,9 +21,11 @@
 //   * COLLECT = true: the lane stores match j < offsets[i+1] - offsets[i] at ids[offsets[i] + j] -- its own segment, in its
 //     own traversal order, plain 4-byte vector stores, no atomics on the output -- and keeps counting beyond the room
 //     (counts[i], RT_RANGE_TRUNCATED).
+// d2, the corner un-rotation, boxdist2 and slot_entry live in rt_point_math.hpp (shared with knn_query.hip).
 // Compiled with -ffp-contract=off and IEEE division: every float operation is the one rt_abi.h writes down.
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
+#include "rt_point_math.hpp"
 #include "rt_traverse.hpp"
 
 static_assert(sizeof(rt_range_box) == 32 && offsetof(rt_range_box, hi) == 16, "rt_range_box: two 16-byte halves (lo | hi)");
@@ -66,98 +68,6 @@ __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint32_t* ws
     }
     *total = t;
     return r;
-}
-
-__device__ __forceinline__ float rg_dot(float ax, float ay, float az, float bx, float by, float bz)
-{
-    return (ax * bx + ay * by) + az * bz;
-}
-// a denominator that is not > 0 (0, negative, NaN) gives weight 0; else the IEEE quotient
-__device__ __forceinline__ float rg_guard(float num, float den) { return den > 0.0f ? num / den : 0.0f; }
-// by selects: NaN -> 0, -0 -> +0
-__device__ __forceinline__ float rg_clamp01(float t)
-{
-    t = t > 0.0f ? t : 0.0f;
-    return t < 1.0f ? t : 1.0f;
-}
-
-struct Tri {
-    float ax, ay, az, bx, by, bz, cx, cy, cz;
-};
-
-// dist2 of p to q after q is clamped into the triangle's vertex box (fmaxf, then fminf)
-__device__ __forceinline__ float rg_clamped(float px, float py, float pz, float qx, float qy, float qz, const Tri& t)
-{
-    const float lox = fminf(fminf(t.ax, t.bx), t.cx), loy = fminf(fminf(t.ay, t.by), t.cy), loz = fminf(fminf(t.az, t.bz), t.cz);
-    const float hix = fmaxf(fmaxf(t.ax, t.bx), t.cx), hiy = fmaxf(fmaxf(t.ay, t.by), t.cy), hiz = fmaxf(fmaxf(t.az, t.bz), t.cz);
-    const float dx = px - fminf(fmaxf(qx, lox), hix);
-    const float dy = py - fminf(fmaxf(qy, loy), hiy);
-    const float dz = pz - fminf(fmaxf(qz, loz), hiz);
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// d2(p, a, b, c) of rt_abi.h's closest-point block: Ericson's ClosestPtPointTriangle (RTCD 5.1.5), the clamp into the vertex
-// box, the squared distance -- point_query.hip's routine without the weights, operation for operation.
-__device__ __forceinline__ float range_tri_d2(float px, float py, float pz, const Tri& t)
-{
-    const float abx = t.bx - t.ax, aby = t.by - t.ay, abz = t.bz - t.az;
-    const float acx = t.cx - t.ax, acy = t.cy - t.ay, acz = t.cz - t.az;
-    const float apx = px - t.ax, apy = py - t.ay, apz = pz - t.az;
-    const float d1 = rg_dot(abx, aby, abz, apx, apy, apz), d2 = rg_dot(acx, acy, acz, apx, apy, apz);
-    if (d1 <= 0.0f && d2 <= 0.0f) return rg_clamped(px, py, pz, t.ax, t.ay, t.az, t);                 // vertex region A
-    const float bpx = px - t.bx, bpy = py - t.by, bpz = pz - t.bz;
-    const float d3 = rg_dot(abx, aby, abz, bpx, bpy, bpz), d4 = rg_dot(acx, acy, acz, bpx, bpy, bpz);
-    if (d3 >= 0.0f && d4 <= d3) return rg_clamped(px, py, pz, t.bx, t.by, t.bz, t);                   // vertex region B
-    const float vc = d1 * d4 - d3 * d2;
-    const float t_ab = rg_clamp01(rg_guard(d1, d1 - d3));
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f)                                                       // edge region AB
-        return rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
-    const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
-    const float d5 = rg_dot(abx, aby, abz, cpx, cpy, cpz), d6 = rg_dot(acx, acy, acz, cpx, cpy, cpz);
-    if (d6 >= 0.0f && d5 <= d6) return rg_clamped(px, py, pz, t.cx, t.cy, t.cz, t);                   // vertex region C
-    const float vb = d5 * d2 - d1 * d6;
-    const float t_ac = rg_clamp01(rg_guard(d2, d2 - d6));
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f)                                                       // edge region AC
-        return rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
-    const float va = d3 * d6 - d5 * d4;
-    const float e43 = d4 - d3, e56 = d5 - d6;
-    const float t_bc = rg_clamp01(rg_guard(e43, e43 + e56));
-    const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
-    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f)                                                     // edge region BC
-        return rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
-    const float s = (va + vb) + vc;
-    if (s > 0.0f) {                                                                                   // face region
-        const float fv = vb / s, fw = vc / s;
-        return rg_clamped(px, py, pz, (t.ax + abx * fv) + acx * fw, (t.ay + aby * fv) + acy * fw, (t.az + abz * fv) + acz * fw, t);
-    }
-    // degenerate face: the nearest of the three edge points
-    float best = rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
-    const float g_ac = rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
-    if (g_ac < best) best = g_ac;
-    const float g_bc = rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
-    if (g_bc < best) best = g_bc;
-    return best;
-}
-
-// the caller's corners of a leaf triangle stored as (s0, s1, s2) with rotation r (RotateAttributes' corner map):
-// r = 1: (c0, c1, c2) = (s1, s2, s0); r = 2: (s2, s0, s1); else as stored
-__device__ __forceinline__ Tri unrotate(float s0x, float s0y, float s0z, float s1x, float s1y, float s1z, float s2x, float s2y,
-                                        float s2z, uint32_t r)
-{
-    Tri t;
-    if (r == 1) t = {s1x, s1y, s1z, s2x, s2y, s2z, s0x, s0y, s0z};
-    else if (r == 2) t = {s2x, s2y, s2z, s0x, s0y, s0z, s1x, s1y, s1z};
-    else t = {s0x, s0y, s0z, s1x, s1y, s1z, s2x, s2y, s2z};
-    return t;
-}
-
-// boxdist2 of a slot: g = max(lo - p, p - hi, 0) per axis, squared and summed in d2's order
-__device__ __forceinline__ float box_d2(const uint4& a, const uint4& b, float px, float py, float pz)
-{
-    const float gx = fmaxf(fmaxf(__uint_as_float(a.x) - px, px - __uint_as_float(b.x)), 0.0f);
-    const float gy = fmaxf(fmaxf(__uint_as_float(a.y) - py, py - __uint_as_float(b.y)), 0.0f);
-    const float gz = fmaxf(fmaxf(__uint_as_float(a.z) - pz, pz - __uint_as_float(b.z)), 0.0f);
-    return (gx * gx + gy * gy) + gz * gz;
 }
 
 // the query region, per shape: keep(slot box) and match(triangle).  SPHERE holds (p, dist2_max), BOX holds (lo, hi).
@@ -208,12 +118,6 @@ template <> struct Region<RT_RANGE_BOX> {
 };
 
 typedef uint32_t RgSpill[kStackMax - kRgStackLds];
-
-// the entry a slot refers to: a leaf (index : 29 | 0) or a box run (child : 29 | count : 3)
-__device__ __forceinline__ uint32_t slot_entry(const uint4& a, const uint4& b)
-{
-    return (b.w >> 29) == RT_CHILD_TRI ? (b.w & kIndexMask) : ((b.w & kIndexMask) | (a.w & ~kIndexMask));
-}
 
 template <int SHAPE, bool COLLECT>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA) void range_query_kernel(RangeParams p)

@@ -459,6 +459,17 @@ int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queri
                                        static_cast<hipStream_t>(stream)));
 }
 
+int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
+                 uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!as || !queries || !out || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (k == 0 || k > RT_KNN_MAX_K) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (misaligned(queries, 16) || misaligned(out, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_knn_query(*as, queries, num_queries, k, out, counters, status, static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
                             const float* light, rt_ray* shadow_rays, void* stream)
 {
@@ -537,6 +548,9 @@ const char* rt_version_string(void)
            "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "
            "(16 in LDS), one traversal compiled for count and collect, CSR output by a 64-bit device scan (workgroup scan in "
            "the count kernel + one workgroup over the sums + add), ids by plain stores into the query's own segment | "
+           "knn: k-nearest queries (k <= 32), the point query's traversal pruned against the k-th record, a sorted per-lane list "
+           "(registers hold its length, k-th record and bound; find the position, then shift; duplicates dropped), rows of 8-byte "
+           "records | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
            "instantiations, shadow rays as a ray batch for the any-hit query";
 }

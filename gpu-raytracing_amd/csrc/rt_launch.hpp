@@ -270,4 +270,8 @@ hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_
                                 const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status,
                                 hipStream_t st);
 
+// knn_query.hip: rt_k_nearest after its argument checks (num_queries > 0, 1 <= k <= RT_KNN_MAX_K)
+hipError_t launch_knn_query(const rt_accel& as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
+                            uint64_t* counters, uint32_t* status, hipStream_t st);
+
 }  // namespace rt

@@ -515,6 +515,54 @@ int rt_range_count(const rt_accel* as, const void* queries, uint32_t num_queries
 int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
                      uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- k-nearest queries (no reference counterpart).  For each caller point: the K nearest triangles, in order -- through any
+ * tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every row is misses).  The
+ * fixed-length sibling of the sphere range query: row i of the output has exactly k records, so nothing is counted, scanned or
+ * read back.
+ *
+ * Candidate set.  For query i = (p, dist2_max), an rt_point_query: S_i = { (d2(p, tri[t]), t) : d2 <= dist2_max }, with d2
+ * EXACTLY the closest-point block's float32 routine (Ericson, the clamp into the vertex box, the squared distance), evaluated on
+ * the caller's corners in the caller's order (pair leaves go back through rt_triangle_pair.rotations, as there).  A NaN d2
+ * (overflow) is not in S_i; a triangle exactly at the radius is.  +inf is a legal radius.
+ * Output row.  Row i is out[i*k .. i*k + k) (64-bit indexing), rt_knn_hit records of 8 bytes (dist2, primitive_id).  It holds
+ * the m = min(k, |S_i|) smallest elements of S_i in ascending (dist2, primitive_id) order: ties on dist2 go to the lower id.
+ * Entries j >= m are {+inf, RT_MISS}.  Rows at i >= num_queries are not written.  The row holds no u, v: a caller who needs the
+ * weights of neighbour t has t.
+ * Not traced (the whole row is misses, no tests counted): a non-finite component of p, a NaN dist2_max or a negative dist2_max.
+ *
+ * Pruning.  bound = dist2_max while the list holds fewer than k entries, the dist2 of the k-th entry once it is full.  A slot or
+ * a popped entry is skipped iff boxdist2 > bound (the closest-point block's boxdist2; never on equality).  A candidate enters
+ * iff d <= dist2_max, and the list is not full or (d, id) is lexicographically below the k-th entry, and (d, id) is not already
+ * in the list.  The duplicate rule is part of the definition: it makes a restart (below) harmless, which re-visits triangles
+ * already listed, and it makes rows on spatial-split trees hold each id at most once (one id always has one d2).
+ * The k smallest pairs (dist2, id) of a set under a strict total order do not depend on the visiting order, and since
+ * d2 >= boxdist2 holds in float32 for every box that contains the vertex box, a skipped subtree holds no element below the bound
+ * -- for any k.  So:
+ *   - exact (bit for bit the brute force over the caller's triangles, sorted) on every tree whose slot boxes contain the vertex
+ *     boxes below them: LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs, and every refitted tree;
+ *   - spatial-split trees (rt_run_sah_build with enable_splits): every record is d2(p, tri[id]) bit for bit, ids are distinct
+ *     and the order is ascending; rank j's sqrt(dist2) exceeds the brute force's rank j by at most the closest-point block's
+ *     2^-20 * M (the same argument rank by rank: the reference whose clipped box holds the triangle's closest point is pruned
+ *     only against a bound that is at least the final rank-j distance).  Refitting a split tree restores exactness;
+ *   - k = 1: (dist2, primitive_id) of out[i] equals rt_closest_points's record.
+ *
+ * Stack: 64 pending entries per query; a push beyond them is dropped.  A pass that dropped a push is followed by another pass
+ * from the root that keeps the list so far, at most twice (rt_closest_points's rule); a pass that drops nothing makes the row
+ * exact.  RT_KNN_STACK_OVERFLOW: the last pass of a query still dropped a push -- its row then holds real, distinct, sorted
+ * records that may not be the nearest.
+ * counters: optional device uint64[4], rt_closest_points's layout: [0] += box tests (non-NONE slots examined), [1] += triangle
+ * tests (leaf records visited); [2] / [3] are not touched.  status: optional device uint32 the call ORs flags into (the caller
+ * clears it).  Asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable).  num_queries = 0: nothing
+ * runs.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / queries / out, k = 0 or
+ * k > RT_KNN_MAX_K, a tree with count > 0 and a null node or leaf pointer, count > 7, queries not 16-byte aligned, out not
+ * 8-byte aligned, status not 4-byte aligned. */
+#define RT_KNN_MAX_K 32
+typedef struct rt_knn_hit { float dist2; uint32_t primitive_id; } rt_knn_hit;
+enum { RT_KNN_STACK_OVERFLOW = 1 };
+int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
+                 uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- ray sorting and indexed ray queries (no reference counterpart).  rt_intersect_rays gives a wave 64 consecutive rays, so
  * its speed depends on the caller's ray order.  rt_sort_rays computes a coherence order of a batch, rt_intersect_rays_indexed
  * traces a batch through an index list -- that order, or any list of rays still alive.
