@@ -10,7 +10,8 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
-(``KNearest``: the k nearest triangles to each point, in order), and ray sorting (``SortRays``: a coherence
+(``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
+``RayHits``: every triangle a ray crosses inside its window, as CSR), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -20,6 +21,7 @@ The directory name contains a hyphen, so import it with
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -75,6 +77,8 @@ KNN_HIT = np.dtype([("dist2", "<f4"), ("primitive_id", "<u4")])                 
 assert KNN_HIT.itemsize == 8
 RT_KNN_MAX_K = 32
 RT_KNN_STACK_OVERFLOW = 1
+# all-hit ray queries (rt_ray_hits_count / rt_ray_hits_collect): RAY records in, CSR rows of HIT records out
+RT_RAY_HITS_STACK_OVERFLOW, RT_RAY_HITS_TRUNCATED = 1, 2
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -151,6 +155,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
+           "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
 _lib = None
@@ -236,6 +241,12 @@ def lib() -> ctypes.CDLL:
     L.rt_sort_rays.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp]
     L.rt_intersect_rays_indexed.restype = i32
     L.rt_intersect_rays_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, i32, u32, vp, vp]
+    L.rt_ray_hits_scratch_bytes.restype = ctypes.c_size_t
+    L.rt_ray_hits_scratch_bytes.argtypes = [u32]
+    L.rt_ray_hits_count.restype = i32
+    L.rt_ray_hits_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp]
+    L.rt_ray_hits_collect.restype = i32
+    L.rt_ray_hits_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp, vp]
     L.rt_generate_shadow_rays.restype = i32
     L.rt_generate_shadow_rays.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.rt_shade_frame.restype = i32
@@ -676,6 +687,96 @@ def RangeQuery(triangles, nodes, root: int, count: int, queries, *, shape: int =
     RangeCollect(triangles, nodes, root, count, queries, offsets, ids, shape=shape, counters=counters, status=status,
                  stream=stream)
     return offsets, ids
+
+
+def RayHitsScratchBytes(num_rays: int) -> int:
+    """rt_ray_hits_scratch_bytes: device bytes of RayHitsCount's scratch (8 bytes per 256 rays, 256-byte aligned)."""
+    return int(lib().rt_ray_hits_scratch_bytes(int(num_rays)))
+
+
+def _ray_batch(rays) -> int:
+    if not rays.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records")
+    return _nbytes(rays) // 32
+
+
+def RayHitsCount(triangles, nodes, root: int, count: int, rays, offsets, *, scratch=None, counters=None, status=None,
+                 stream=None) -> int:
+    """rt_ray_hits_count: offsets[0 .. N] (a contiguous device int64 tensor of >= N + 1 words) = the exclusive prefix sum of the
+    number of triangles each ray of `rays` (32-byte RAY records, e.g. float32 [N, 8]) crosses inside its [tmin, tmax] window;
+    offsets[N] is the total.  Any tree Trace() takes.  scratch: >= RayHitsScratchBytes(N) bytes, 256-byte aligned
+    (device_bytes; taken from torch's allocator when None).  counters: optional int64[4] ([0] box tests, [1] leaf records
+    visited).  status: optional device uint32 the call ORs RT_RAY_HITS_* flags into (see ray_hits_status).  Asynchronous on
+    `stream`, nothing is read back.  Returns N."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    if scratch is None:
+        scratch = device_bytes(RayHitsScratchBytes(n), rays.device)
+    elif _nbytes(scratch) < RayHitsScratchBytes(n):
+        raise ValueError(f"scratch must hold RayHitsScratchBytes({n}) bytes")
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
+    _check(lib().rt_ray_hits_count(ctypes.byref(a), _ptr(rays) or _ptr(scratch), n, _ptr(offsets), _ptr(scratch), _ptr(counters),
+                                   _ptr(status), _stream_ptr(stream)), "rt_ray_hits_count")
+    return n
+
+
+def RayHitsCollect(triangles, nodes, root: int, count: int, rays, offsets, hits, *, counts=None, counters=None, status=None,
+                   stream=None) -> int:
+    """rt_ray_hits_collect: ray i writes the HIT records of its first offsets[i+1] - offsets[i] crossings at hits[offsets[i]:]
+    (`hits`: a contiguous device buffer of 16-byte records, e.g. float32 [total, 4], that the offsets stay inside -- the
+    caller's contract; `offsets`: int64 [N + 1] from RayHitsCount, or i * K for a fixed K per ray).  counts: optional device
+    int32 [N], each ray's true row length.  A ray with more records than room sets RT_RAY_HITS_TRUNCATED in `status`.
+    Records come in traversal order (unspecified but deterministic; sort by t if an order is needed); on non-split trees each
+    crossed triangle appears exactly once.  Asynchronous on `stream`.  Returns N."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or not hits.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, hits a contiguous device buffer")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_ray_hits_collect(ctypes.byref(a), _ptr(rays), n, _ptr(offsets), _ptr(hits), _ptr(counts), _ptr(counters),
+                                     _ptr(status), _stream_ptr(stream)), "rt_ray_hits_collect")
+    return n
+
+
+def ray_hits_status(status) -> int:
+    """The RT_RAY_HITS_* flags RayHitsCount / RayHitsCollect ORed into `status` (copies the word back: waits for the work queued
+    before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
+
+
+def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False, counters=None, status=None, stream=None):
+    """Every triangle each ray crosses, as CSR: RayHitsCount, then the total offsets[N] is READ BACK TO THE HOST -- one
+    synchronisation of `stream` per call, the only one -- to allocate the record array, then RayHitsCollect.  Returns
+    (offsets, hits): torch int64 [N + 1] and float32 [total, 4] device tensors (t, primitive_id bits, u, v; view column 1 as
+    int32); ray i owns hits[offsets[i]:offsets[i+1]].  sort=True orders every row by ascending (t, primitive_id) on the device
+    (two stable torch sorts over the records: plumbing, not a kernel).  A caller who cannot afford the synchronisation (a
+    captured graph, a fixed budget per ray) uses RayHitsCount / RayHitsCollect directly.  With `counters`, the tests of both
+    passes are added (twice one traversal)."""
+    torch = _torch()
+    n = _ray_batch(rays)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
+    RayHitsCount(triangles, nodes, root, count, rays, offsets, counters=counters, status=status, stream=stream)
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with ctx:
+        total = int(offsets[n].item())
+        hits = torch.empty((max(total, 1), 4), dtype=torch.float32, device=rays.device)[:total]
+        RayHitsCollect(triangles, nodes, root, count, rays, offsets, hits, counters=counters, status=status, stream=stream)
+        if sort and total > 1:
+            # two stable sorts: by primitive_id (unsigned), then by the 64-bit key row << 32 | the monotone integer image of t
+            # (-0 counted as +0), which keeps every record inside its row
+            row = torch.repeat_interleave(torch.arange(n, device=rays.device), offsets[1:] - offsets[:-1], output_size=total)
+            bits = hits.view(torch.int32).to(torch.int64)
+            order = torch.argsort(bits[:, 1] & 0xFFFFFFFF, stable=True)
+            tb = (hits[:, 0] + 0.0).contiguous().view(torch.int32).to(torch.int64)
+            key = (row << 32) | (torch.where(tb >= 0, tb, tb ^ 0x7FFFFFFF) + (1 << 31))
+            order = order[torch.argsort(key[order], stable=True)]
+            hits = hits[order].contiguous()
+    return offsets, hits
 
 
 def KNearest(triangles, nodes, root: int, count: int, queries, k: int, out, *, counters=None, status=None, stream=None) -> int:

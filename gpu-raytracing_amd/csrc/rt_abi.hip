@@ -470,6 +470,38 @@ int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num
     return hip_rc(launch_knn_query(*as, queries, num_queries, k, out, counters, status, static_cast<hipStream_t>(stream)));
 }
 
+size_t rt_ray_hits_scratch_bytes(uint32_t num_rays) { return ray_hits_scratch_bytes(num_rays); }
+
+// the checks both all-hit entry points share
+static int ray_hits_args(const rt_accel* as, const rt_ray* rays, const uint64_t* offsets, const uint32_t* status)
+{
+    if (!as || !rays || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (misaligned(rays, 16) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    return RT_OK;
+}
+
+int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
+                      uint64_t* counters, uint32_t* status, void* stream)
+{
+    const int rc = ray_hits_args(as, rays, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    // (num_rays = 0 still launches the scan's one workgroup: offsets[0] = 0)
+    return hip_rc(launch_ray_hits_count(*as, rays, num_rays, offsets, scratch, counters, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
+                        uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
+{
+    const int rc = ray_hits_args(as, rays, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!hits || misaligned(hits, 16) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_hits_collect(*as, rays, num_rays, offsets, hits, counts, counters, status,
+                                          static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
                             const float* light, rt_ray* shadow_rays, void* stream)
 {
@@ -551,6 +583,10 @@ const char* rt_version_string(void)
            "knn: k-nearest queries (k <= 32), the point query's traversal pruned against the k-th record, a sorted per-lane list "
            "(registers hold its length, k-th record and bound; find the position, then shift; duplicates dropped), rows of 8-byte "
            "records | "
+           "rayhits: all-hit ray queries, every triangle a ray crosses in a fixed [tmin, tmax] window, the range query's frame "
+           "(one lane per ray, unordered traversal, 64-entry stack of 4-byte entries, 16 in LDS) with the tracer's slab and "
+           "Moller-Trumbore tests, CSR output by the 64-bit device scan, 16-byte hit records by plain stores into the ray's "
+           "own segment | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
            "instantiations, shadow rays as a ray batch for the any-hit query";
 }

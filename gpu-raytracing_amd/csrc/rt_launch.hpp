@@ -274,4 +274,12 @@ hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_
 hipError_t launch_knn_query(const rt_accel& as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
                             uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// ray_hits_query.hip: rt_ray_hits_count / rt_ray_hits_collect after their argument checks.  Count runs for num_rays = 0 too
+// (it writes offsets[0] = 0); collect is called with num_rays > 0.
+size_t ray_hits_scratch_bytes(uint32_t num_rays);   // uint64 per workgroup of 256 rays, 256-byte aligned
+hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
+                                 uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets,
+                                   rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status, hipStream_t st);
+
 }  // namespace rt

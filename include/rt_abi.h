@@ -621,6 +621,71 @@ int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t n
                               uint32_t num_indices, rt_hit* hits, int mode, uint32_t num_primitives, uint64_t* counters,
                               void* stream);
 
+/* ---- all-hit ray queries (no reference counterpart).  For each caller ray: WHICH triangles it crosses inside its
+ * [tmin, tmax] window, and how many -- the set-valued ray query (transparency, penetration counts, parity / inside tests, CSG),
+ * through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every row is empty).
+ * The output length depends on the data, so the result is compressed sparse rows (CSR), as for the range queries: offsets[0 .. n]
+ * (uint64) and one rt_hit array; ray i owns hits[offsets[i] .. offsets[i+1]).
+ *
+ * Rays.  An rt_ray, with rt_intersect_rays's liveness rule: a ray with tmin > tmax, or a NaN in origin, direction, tmin or
+ * tmax, is not traced -- its row is empty and no tests are counted for it.  tmax = +inf is allowed.  1/dir is computed once per
+ * ray by IEEE division.
+ * Slot test.  A non-NONE slot is entered iff back >= front && front <= tmax && back >= tmin, front / back from rt_trace's slab
+ * test (float32: t1 = (min - o) * (1/d), t2 = (max - o) * (1/d) per axis, front = the largest fminf(t1, t2), back = the smallest
+ * fmaxf(t1, t2)).  tmin and tmax are the ray's ORIGINAL values for the whole traversal: the window is never updated.
+ * Leaf test.  rt_trace's Moller-Trumbore (same epsilon, same operation order, same acceptance rule: not (|a| < epsilon), not
+ * (u < 0 || u > 1), not (v < 0 || u + v > 1), not (t < tmin || t > tmax)) on the STORED corners of the leaf record: A =
+ * (v0, v1, v2) with primitive_id_0, and B = (v2, v1, v3) with primitive_id_1 when v3 != v2 bit for bit (a single-triangle record
+ * has v3 == v2, see the refit block; every builder gives a leaf slot a count >= 1, so this is the closest-hit traversal's rule
+ * "count > 0 and v3 != v2" on every record the library writes).  Every test uses the original tmax.  Every accepted triangle
+ * emits one rt_hit (t, primitive_id, u, v), (u, v) mapped back to the caller's corners through rt_triangle_pair.rotations
+ * exactly as rt_intersect_rays maps them.
+ *
+ * Result: a SET of records per ray -- no ordering promise.  The row of ray i is the set of accepted triangles in the leaves
+ * reached through entered slots.  With a fixed window whether a slot is entered does not depend on what was visited before it,
+ * so the row is a function of the tree's bytes and the ray alone: any visiting order gives the same set.
+ *   It is NOT promised to equal a brute force over the caller's triangles: the float32 slab test and the float32 triangle test
+ *   are separate computations, and a grazing ray may fail a box whose triangle it would accept.  What does hold, when no push
+ *   was dropped (status 0):
+ *   1. some record of the row has the (t, u, v) bits of rt_intersect_rays's closest-hit record for the same ray and tree: the
+ *      closest hit's triangle was reached through slots that passed with a smaller tmax, so they pass with the original one
+ *      too, and the triangle test is the same arithmetic.  (On split trees and among coincident triangles two records at the
+ *      same t can differ in primitive_id; the closest-hit query reports one of them.)  A closest-hit miss has an empty row and
+ *      the other way round;
+ *   2. hence the minimum t over the row is at most the closest-hit t.
+ *   Spatial-split trees (rt_run_sah_build with enable_splits): a triangle appears once per REFERENCE that is reached, so
+ *   duplicates are possible and the parity of a row means nothing there.  Refit does not remove them: the references stay.
+ *   On the other trees every triangle is in one leaf and appears at most once.
+ *   Order: the records of a ray come in the traversal order of its lane -- deterministic for a given tree, the same in
+ *   rt_ray_hits_count and rt_ray_hits_collect (one traversal, compiled twice), otherwise unspecified.
+ *
+ * rt_ray_hits_count: offsets[0 .. num_rays] = the exclusive prefix sum of the row lengths; offsets[num_rays] is the total.
+ *   64-bit: no overflow case exists.  scratch: rt_ray_hits_scratch_bytes(num_rays) bytes of device memory, 256-byte aligned, no
+ *   initialisation needed (one uint64 per 256 rays: the workgroup sums of the scan).  Launches: the traversal (which also scans
+ *   the counts inside each workgroup), one workgroup over the workgroup sums, one add.  num_rays = 0 still writes
+ *   offsets[0] = 0.
+ * rt_ray_hits_collect: ray i writes its first min(matches, offsets[i+1] - offsets[i]) records at hits + offsets[i] and writes
+ *   nothing else (offsets[i+1] < offsets[i] counts as no room); records past the last segment and segments of other rays are
+ *   not touched.  counts (optional, device uint32[num_rays]): the ray's true row length, room or not.  A ray with more records
+ *   than room ORs RT_RAY_HITS_TRUNCATED into *status; its segment then holds the first records in traversal order.
+ *   Two call patterns: (a) everything: rt_ray_hits_count, read offsets[num_rays] back, allocate hits, rt_ray_hits_collect with
+ *   the same offsets; (b) a fixed K per ray: fill offsets[i] = i * K once, one rt_ray_hits_collect pass, counts says how many
+ *   of each segment are valid (min(counts[i], K)).  num_rays = 0: nothing runs.
+ * Both calls: counters, optional device uint64[4]: [0] += box tests (non-NONE slots examined), [1] += leaf records visited;
+ * [2] / [3] are not touched.  The same rays give the same counters in both calls.  status: optional device uint32 the calls OR
+ * flags into (the caller clears it).  Stack: 64 pending four-byte entries per ray; a push beyond them is dropped and sets
+ * RT_RAY_HITS_STACK_OVERFLOW: the row is then a subset of the full row, and since both calls drop the same pushes they still
+ * agree with each other.  Asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / rays / offsets / scratch (count) / hits
+ * (collect), a tree with count > 0 and a null node or leaf pointer, count > 7, rays or hits not 16-byte, offsets not 8-byte,
+ * counts / status not 4-byte, scratch not 256-byte aligned. */
+enum { RT_RAY_HITS_STACK_OVERFLOW = 1, RT_RAY_HITS_TRUNCATED = 2 };
+size_t rt_ray_hits_scratch_bytes(uint32_t num_rays);
+int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
+                      uint64_t* counters, uint32_t* status, void* stream);
+int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
+                        uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- deferred shading (no reference counterpart: the reference shades inside TraceRays, Tracer.cu:471-595).  The ray queries
  * give (t, primitive_id, u, v) records; these two calls turn records into rt_trace's frames:
  *   rt_generate_camera_rays -> rt_intersect_rays(closest) -> [rt_generate_shadow_rays -> rt_intersect_rays(any hit)] ->
