@@ -11,7 +11,9 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
-``RayHits``: every triangle a ray crosses inside its window, as CSR), and ray sorting (``SortRays``: a coherence
+``RayHits``: every triangle a ray crosses inside its window, as CSR), triangle-overlap queries (``TriOverlapsCount``,
+``TriOverlapsCollect``, ``TriOverlaps``: every triangle a query triangle cuts, as CSR; ``self_pairs`` for the
+self-intersections of the mesh the tree was built over), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -79,6 +81,9 @@ RT_KNN_MAX_K = 32
 RT_KNN_STACK_OVERFLOW = 1
 # all-hit ray queries (rt_ray_hits_count / rt_ray_hits_collect): RAY records in, CSR rows of HIT records out
 RT_RAY_HITS_STACK_OVERFLOW, RT_RAY_HITS_TRUNCATED = 1, 2
+# triangle-overlap queries (rt_tri_overlaps_count / rt_tri_overlaps_collect): TRIANGLE records in, CSR rows of ids out
+kTriSelf = 1
+RT_TRI_STACK_OVERFLOW, RT_TRI_TRUNCATED = 1, 2
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -156,6 +161,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
+           "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
 _lib = None
@@ -247,6 +253,12 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp]
     L.rt_ray_hits_collect.restype = i32
     L.rt_ray_hits_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp, vp]
+    L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
+    L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
+    L.rt_tri_overlaps_count.restype = i32
+    L.rt_tri_overlaps_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp, vp]
+    L.rt_tri_overlaps_collect.restype = i32
+    L.rt_tri_overlaps_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp, vp, vp]
     L.rt_generate_shadow_rays.restype = i32
     L.rt_generate_shadow_rays.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.rt_shade_frame.restype = i32
@@ -777,6 +789,90 @@ def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False
             order = order[torch.argsort(key[order], stable=True)]
             hits = hits[order].contiguous()
     return offsets, hits
+
+
+def TriOverlapsScratchBytes(num_queries: int) -> int:
+    """rt_tri_overlaps_scratch_bytes: device bytes of TriOverlapsCount's scratch (8 bytes per 256 queries, 256-byte aligned)."""
+    return int(lib().rt_tri_overlaps_scratch_bytes(int(num_queries)))
+
+
+def _tri_batch(queries) -> int:
+    if not queries.is_contiguous() or _nbytes(queries) % 36:
+        raise ValueError("queries must be a contiguous device buffer of 36-byte TRIANGLE records")
+    return _nbytes(queries) // 36
+
+
+def TriOverlapsCount(triangles, nodes, root: int, count: int, queries, offsets, *, self_pairs: bool = False, scratch=None,
+                     counters=None, status=None, stream=None) -> int:
+    """rt_tri_overlaps_count: offsets[0 .. N] (a contiguous device int64 tensor of >= N + 1 words) = the exclusive prefix sum of
+    the number of triangles each query triangle of `queries` (36-byte TRIANGLE records, e.g. float32 [N, 9]) cuts; offsets[N]
+    is the total.  Any tree Trace() takes.  self_pairs (kTriSelf): `queries` are the triangles the tree was built over, query i
+    is triangle i, and row i holds only j > i without a corner shared with i -- every intersecting pair once.  scratch:
+    >= TriOverlapsScratchBytes(N) bytes, 256-byte aligned (device_bytes; taken from torch's allocator when None).  counters:
+    optional int64[4] ([0] box tests, [1] leaf records visited).  status: optional device uint32 the call ORs RT_TRI_* flags
+    into (see tri_overlap_status).  Asynchronous on `stream`, nothing is read back.  Returns N."""
+    n = _tri_batch(queries)
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    if scratch is None:
+        scratch = device_bytes(TriOverlapsScratchBytes(n), queries.device)
+    elif _nbytes(scratch) < TriOverlapsScratchBytes(n):
+        raise ValueError(f"scratch must hold TriOverlapsScratchBytes({n}) bytes")
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
+    _check(lib().rt_tri_overlaps_count(ctypes.byref(a), _ptr(queries) or _ptr(scratch), n, kTriSelf if self_pairs else 0,
+                                       _ptr(offsets), _ptr(scratch), _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           "rt_tri_overlaps_count")
+    return n
+
+
+def TriOverlapsCollect(triangles, nodes, root: int, count: int, queries, offsets, ids, *, self_pairs: bool = False, counts=None,
+                       counters=None, status=None, stream=None) -> int:
+    """rt_tri_overlaps_collect: query i writes the ids of its first offsets[i+1] - offsets[i] matches at ids[offsets[i]:]
+    (`ids`: a contiguous device int32 / uint32 tensor the offsets stay inside -- the caller's contract; `offsets`: int64
+    [N + 1] from TriOverlapsCount, or i * K for a fixed K per query).  counts: optional device int32 [N], each query's true
+    match count.  A query with more matches than room sets RT_TRI_TRUNCATED in `status`.  Ids come in traversal order
+    (unspecified but deterministic); on non-split trees each matching triangle appears exactly once.  Asynchronous on
+    `stream`.  Returns N."""
+    n = _tri_batch(queries)
+    if not offsets.is_contiguous() or not ids.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, ids a contiguous device buffer")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_tri_overlaps_collect(ctypes.byref(a), _ptr(queries), n, kTriSelf if self_pairs else 0, _ptr(offsets),
+                                         _ptr(ids), _ptr(counts), _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           "rt_tri_overlaps_collect")
+    return n
+
+
+def tri_overlap_status(status) -> int:
+    """The RT_TRI_* flags TriOverlapsCount / TriOverlapsCollect ORed into `status` (copies the word back: waits for the work
+    queued before it)."""
+    return int(to_host(status, np.uint32, 1)[0])
+
+
+def TriOverlaps(triangles, nodes, root: int, count: int, queries, *, self_pairs: bool = False, counters=None, status=None,
+                stream=None):
+    """Everything each query triangle cuts, as CSR: TriOverlapsCount, then the total offsets[N] is READ BACK TO THE HOST -- one
+    synchronisation of `stream` per call, the only one -- to allocate the id array, then TriOverlapsCollect.  Returns
+    (offsets, ids): torch int64 [N + 1] and int32 [total] device tensors; query i owns ids[offsets[i]:offsets[i+1]].  A
+    caller who cannot afford the synchronisation (a captured graph, a fixed budget per query) uses TriOverlapsCount /
+    TriOverlapsCollect directly.  With `counters`, the tests of both passes are added (twice one traversal)."""
+    torch = _torch()
+    n = _tri_batch(queries)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=queries.device)
+    TriOverlapsCount(triangles, nodes, root, count, queries, offsets, self_pairs=self_pairs, counters=counters, status=status,
+                     stream=stream)
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with ctx:
+        total = int(offsets[n].item())
+    ids = torch.empty(max(total, 1), dtype=torch.int32, device=queries.device)[:total]
+    TriOverlapsCollect(triangles, nodes, root, count, queries, offsets, ids, self_pairs=self_pairs, counters=counters,
+                       status=status, stream=stream)
+    return offsets, ids
 
 
 def KNearest(triangles, nodes, root: int, count: int, queries, k: int, out, *, counters=None, status=None, stream=None) -> int:

@@ -502,6 +502,42 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
                                           static_cast<hipStream_t>(stream)));
 }
 
+size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
+
+// the checks both triangle-overlap entry points share
+static int tri_overlaps_args(const rt_accel* as, const rt_triangle* queries, uint32_t flags, const uint64_t* offsets,
+                             const uint32_t* status)
+{
+    if (!as || !queries || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (flags & ~(uint32_t)RT_TRI_SELF) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(queries, 4) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    return RT_OK;
+}
+
+int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
+                          uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
+{
+    const int rc = tri_overlaps_args(as, queries, flags, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    // (num_queries = 0 still launches the scan's one workgroup: offsets[0] = 0)
+    return hip_rc(launch_tri_overlaps_count(*as, queries, num_queries, (flags & RT_TRI_SELF) != 0, offsets, scratch, counters,
+                                            status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_tri_overlaps_collect(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
+                            const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status,
+                            void* stream)
+{
+    const int rc = tri_overlaps_args(as, queries, flags, offsets, status);
+    if (rc != RT_OK) return rc;
+    if (!ids || misaligned(ids, 4) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_tri_overlaps_collect(*as, queries, num_queries, (flags & RT_TRI_SELF) != 0, offsets, ids, counts,
+                                              counters, status, static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
                             const float* light, rt_ray* shadow_rays, void* stream)
 {
@@ -587,6 +623,9 @@ const char* rt_version_string(void)
            "(one lane per ray, unordered traversal, 64-entry stack of 4-byte entries, 16 in LDS) with the tracer's slab and "
            "Moller-Trumbore tests, CSR output by the 64-bit device scan, 16-byte hit records by plain stores into the ray's "
            "own segment | "
+           "trioverlap: triangle-overlap queries, every triangle a caller triangle cuts (vertex boxes + seventeen separating "
+           "axes in three rolled loops, first separating axis leaves), optional self mode (j > i, no shared corner), the "
+           "range query's frame and CSR output | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
            "instantiations, shadow rays as a ray batch for the any-hit query";
 }

@@ -686,6 +686,82 @@ int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
 int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
                         uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
+ * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
+ * any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every set is empty).
+ * Everything that is not the predicate is the range-query block's, WORD FOR WORD, with rt_tri_overlaps_count /
+ * rt_tri_overlaps_collect / RT_TRI_* read for rt_range_count / rt_range_collect / RT_RANGE_*: the CSR contract (offsets[0 .. n]
+ * uint64 and one id array, query i owns ids[offsets[i] .. offsets[i+1])); count's offsets, scratch
+ * (rt_tri_overlaps_scratch_bytes = rt_range_scratch_bytes: one uint64 per 256 queries, 256-byte aligned, no initialisation) and
+ * three launches; collect's segments, `counts` and RT_TRI_TRUNCATED; both call patterns ((a) everything: count, read
+ * offsets[num_queries] back, allocate ids, collect with the same offsets; (b) a fixed K per query: offsets[i] = i * K, one
+ * collect pass, min(counts[i], K) of each segment are valid); the 64-entry stack (a dropped push sets RT_TRI_STACK_OVERFLOW,
+ * the result is then a subset, and both calls drop the same pushes); the counters ([0] += non-NONE slots examined, [1] += leaf
+ * records visited, [2] / [3] not touched, the same in both calls); num_queries = 0 (count still writes offsets[0] = 0, collect
+ * does nothing); the traversal order of the ids; no allocation, no host copy, no synchronisation (hipGraph-capturable).
+ *
+ * queries: an array of rt_triangle (36 bytes, 4-byte aligned), P = (p0, p1, p2).
+ * Not traced (count 0, no tests counted): a query with a non-finite component among its nine.  Degenerate query triangles (a
+ * point, a segment) ARE traced.
+ *
+ * The predicate cuts(P, Q).  Q = (q0, q1, q2): a caller triangle, its corners in the caller's order (pair leaves go back through
+ * rt_triangle_pair.rotations, exactly as the sphere range query un-rotates them).  float32, every operation rounded on its own
+ * (no fused multiply-add):
+ *     cross(a, b) = (a.y*b.z - a.z*b.y,  a.z*b.x - a.x*b.z,  a.x*b.y - a.y*b.x)
+ *     dot(a, b)   = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *     a - b       componentwise
+ * cuts is true iff both hold:
+ *   1. Vertex boxes.  The two triangles' vertex boxes overlap on every axis with closed comparisons: RT_RANGE_BOX's triangle
+ *      test with [lo, hi] = the query's fminf / fmaxf box (tlo <= hi && thi >= lo; a NaN coordinate of Q is dropped by fminf /
+ *      fmaxf; -0 equals +0).
+ *   2. No separating axis among seventeen.  All corners relative to p0:
+ *        P' = (0, p1 - p0, p2 - p0)                 Q' = (q0 - p0, q1 - p0, q2 - p0)
+ *        e0 = p1 - p0, e1 = p2 - p1, e2 = p0 - p2   f0 = q1 - q0, f1 = q2 - q1, f2 = q0 - q2
+ *        nP = cross(e0, e1)                         nQ = cross(f0, f1)
+ *      Axes, in this order: nP; nQ; cross(e_i, f_j) for i = 0..2 (outer), j = 0..2 (inner); cross(nP, e_i) for i = 0..2;
+ *      cross(nQ, f_j) for j = 0..2.
+ *      On an axis a: sP_k = dot(a, P'_k), sQ_k = dot(a, Q'_k), k = 0..2 (sP_0 = dot(a, 0) is computed like the others);
+ *      minP = fminf(fminf(sP_0, sP_1), sP_2), maxP = fmaxf(fmaxf(sP_0, sP_1), sP_2), and minQ / maxQ alike.
+ *      The axis SEPARATES iff minP > maxQ || minQ > maxP.  Strict: touching does not separate.  A NaN makes both comparisons
+ *      false: a NaN does not separate.
+ *   The six in-plane axes make coplanar and coincident triangles come out right, where the nine edge crosses vanish.  A zero
+ *   axis never separates (degenerate triangles).  Overflow gives inf or NaN and hence a match.  Accuracy: the projections are
+ *   products of degree 4 in the coordinate differences, so differences beyond about 2^31 overflow float32; the result there is
+ *   still deterministic and equal to this text, but it is not an accurate intersection test (as the closest-point block says of
+ *   its own overflow).  The answer does not depend on the order the axes are evaluated in (a
+ *   conjunction); the kernel leaves at the first separating axis.
+ *
+ * Slot test.  A non-NONE slot is skipped iff its box fails the closed overlap test against the query's vertex box (the
+ * RT_RANGE_BOX slot test).  Condition 1 is part of the predicate and uses nothing but min, max and comparisons, so skipping loses
+ * nothing.
+ * Result: a SET -- no ordering promise and no tie rule.
+ *   - exact (the brute-force set { k : cuts(P, tri[k]) } over the caller's triangles, each id once) on every tree whose slot
+ *     boxes contain the vertex boxes below them: LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs, and every refitted tree;
+ *   - spatial-split trees (rt_run_sah_build with enable_splits): the leaf test is on the whole triangle, so every reported id
+ *     is a true match; but an id appears once per REFERENCE that is reached (duplicates are possible), and a triangle is missed
+ *     when every one of its clipped references lies outside the query's vertex box.  Refitting a split tree restores exactness
+ *     up to the duplicates: refit writes unclipped boxes, but the references stay.
+ *
+ * flags: 0 or RT_TRI_SELF.  RT_TRI_SELF: the caller passes the triangles the tree was built over (after a refit: the moved
+ * ones), and query i IS triangle i.  Candidate j is reported iff cuts holds and
+ *   - j > i, and
+ *   - no corner of j equals a corner of i: nine corner comparisons, two corners being equal when all three components are float
+ *     == (as the pairing test compares corners: -0 == +0, a NaN equals nothing).
+ * Every intersecting pair without a shared corner therefore appears once, in row min(i, j).  Without the flag nothing is
+ * excluded: a query identical to a scene triangle matches that triangle.
+ *
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / queries / offsets / scratch (count) /
+ * ids (collect), a tree with count > 0 and a null node or leaf pointer, count > 7, a flag bit other than RT_TRI_SELF, queries
+ * not 4-byte, offsets not 8-byte, ids / counts / status not 4-byte, scratch not 256-byte aligned. */
+enum { RT_TRI_SELF = 1 };
+enum { RT_TRI_STACK_OVERFLOW = 1, RT_TRI_TRUNCATED = 2 };
+size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries);
+int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
+                          uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream);
+int rt_tri_overlaps_collect(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
+                            const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters,
+                            uint32_t* status, void* stream);
+
 /* ---- deferred shading (no reference counterpart: the reference shades inside TraceRays, Tracer.cu:471-595).  The ray queries
  * give (t, primitive_id, u, v) records; these two calls turn records into rt_trace's frames:
  *   rt_generate_camera_rays -> rt_intersect_rays(closest) -> [rt_generate_shadow_rays -> rt_intersect_rays(any hit)] ->
