@@ -569,9 +569,13 @@ def PrepareInstances(instances, num_instances: int, blas_table, num_blas: int, p
                                       _ptr(records), _ptr(status), _stream_ptr(stream)), "rt_prepare_instances")
 
 
+def _status_word(status) -> int:
+    return int(to_host(status, np.uint32, 1)[0])
+
+
 def instance_status(status) -> int:
     """The RT_INSTANCE_* flags of the last PrepareInstances (copies the word back: waits for the work queued before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
 
 
 def IntersectRaysInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
@@ -615,7 +619,46 @@ def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, cou
 
 def point_status(status) -> int:
     """The RT_POINT_* flags ClosestPoints ORed into `status` (copies the word back: waits for the work queued before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
+
+
+def _csr_count(entry, scratch_bytes, tree, queries, n: int, extra, offsets, *, scratch, counters, status, stream) -> int:
+    """The count call of a CSR query family: the offsets / scratch checks, then the call.  entry: the library's rt_*_count;
+    scratch_bytes: the family's public *ScratchBytes; tree: (triangles, nodes, root, count); extra: the family's own arguments
+    between the batch size and the offsets."""
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    if scratch is None:
+        scratch = device_bytes(scratch_bytes(n), queries.device)
+    elif _nbytes(scratch) < scratch_bytes(n):
+        raise ValueError(f"scratch must hold {scratch_bytes.__name__}({n}) bytes")
+    triangles, nodes, root, count = tree
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
+    _check(entry(ctypes.byref(a), _ptr(queries) or _ptr(scratch), n, *extra, _ptr(offsets), _ptr(scratch), _ptr(counters),
+                 _ptr(status), _stream_ptr(stream)), entry.__name__)
+    return n
+
+
+def _csr_collect(entry, tree, queries, n: int, extra, offsets, rows, rows_name: str, *, counts, counters, status, stream) -> int:
+    """The collect call of a CSR query family: the offsets / rows / counts checks, then the call.  entry: the library's
+    rt_*_collect; tree, extra: as for _csr_count; rows: the output (`rows_name` in the error message)."""
+    if not offsets.is_contiguous() or not rows.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, {rows_name} a contiguous device buffer")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    if n == 0:
+        return 0
+    triangles, nodes, root, count = tree
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(entry(ctypes.byref(a), _ptr(queries), n, *extra, _ptr(offsets), _ptr(rows), _ptr(counts), _ptr(counters), _ptr(status),
+                 _stream_ptr(stream)), entry.__name__)
+    return n
+
+
+def _on_stream(stream):
+    """The context in which torch's own work (an .item() read-back, an allocation, a sort) goes to `stream`."""
+    return _torch().cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
 
 def RangeScratchBytes(num_queries: int) -> int:
@@ -641,17 +684,8 @@ def RangeCount(triangles, nodes, root: int, count: int, queries, offsets, *, sha
     None).  counters: optional int64[4] ([0] box tests, [1] triangle tests).  status: optional device uint32 the call ORs
     RT_RANGE_* flags into (see range_status).  Asynchronous on `stream`, nothing is read back.  Returns N."""
     n = _range_batch(queries, shape)
-    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
-    if scratch is None:
-        scratch = device_bytes(RangeScratchBytes(n), queries.device)
-    elif _nbytes(scratch) < RangeScratchBytes(n):
-        raise ValueError(f"scratch must hold RangeScratchBytes({n}) bytes")
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
-    _check(lib().rt_range_count(ctypes.byref(a), _ptr(queries) or _ptr(scratch), n, int(shape), _ptr(offsets), _ptr(scratch), _ptr(counters),
-                                _ptr(status), _stream_ptr(stream)), "rt_range_count")
-    return n
+    return _csr_count(lib().rt_range_count, RangeScratchBytes, (triangles, nodes, root, count), queries, n, (int(shape),), offsets,
+                      scratch=scratch, counters=counters, status=status, stream=stream)
 
 
 def RangeCollect(triangles, nodes, root: int, count: int, queries, offsets, ids, *, shape: int = kRangeSphere, counts=None,
@@ -662,21 +696,13 @@ def RangeCollect(triangles, nodes, root: int, count: int, queries, offsets, ids,
     A query with more matches than room sets RT_RANGE_TRUNCATED in `status`.  Ids come in traversal order (unspecified but
     deterministic); on non-split trees each matching triangle appears exactly once.  Asynchronous on `stream`.  Returns N."""
     n = _range_batch(queries, shape)
-    if not offsets.is_contiguous() or not ids.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, ids a contiguous device buffer")
-    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
-        raise ValueError(f"counts must hold {n} words")
-    if n == 0:
-        return 0
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    _check(lib().rt_range_collect(ctypes.byref(a), _ptr(queries), n, int(shape), _ptr(offsets), _ptr(ids), _ptr(counts),
-                                  _ptr(counters), _ptr(status), _stream_ptr(stream)), "rt_range_collect")
-    return n
+    return _csr_collect(lib().rt_range_collect, (triangles, nodes, root, count), queries, n, (int(shape),), offsets, ids, "ids",
+                        counts=counts, counters=counters, status=status, stream=stream)
 
 
 def range_status(status) -> int:
     """The RT_RANGE_* flags RangeCount / RangeCollect ORed into `status` (copies the word back: waits for the work queued before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
 
 
 def RangeQuery(triangles, nodes, root: int, count: int, queries, *, shape: int = kRangeSphere, counters=None, status=None,
@@ -690,10 +716,7 @@ def RangeQuery(triangles, nodes, root: int, count: int, queries, *, shape: int =
     n = _range_batch(queries, shape)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=queries.device)
     RangeCount(triangles, nodes, root, count, queries, offsets, shape=shape, counters=counters, status=status, stream=stream)
-    if stream is not None:
-        with torch.cuda.stream(stream):
-            total = int(offsets[n].item())
-    else:
+    with _on_stream(stream):
         total = int(offsets[n].item())
     ids = torch.empty(max(total, 1), dtype=torch.int32, device=queries.device)[:total]
     RangeCollect(triangles, nodes, root, count, queries, offsets, ids, shape=shape, counters=counters, status=status,
@@ -720,18 +743,8 @@ def RayHitsCount(triangles, nodes, root: int, count: int, rays, offsets, *, scra
     (device_bytes; taken from torch's allocator when None).  counters: optional int64[4] ([0] box tests, [1] leaf records
     visited).  status: optional device uint32 the call ORs RT_RAY_HITS_* flags into (see ray_hits_status).  Asynchronous on
     `stream`, nothing is read back.  Returns N."""
-    n = _ray_batch(rays)
-    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
-    if scratch is None:
-        scratch = device_bytes(RayHitsScratchBytes(n), rays.device)
-    elif _nbytes(scratch) < RayHitsScratchBytes(n):
-        raise ValueError(f"scratch must hold RayHitsScratchBytes({n}) bytes")
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
-    _check(lib().rt_ray_hits_count(ctypes.byref(a), _ptr(rays) or _ptr(scratch), n, _ptr(offsets), _ptr(scratch), _ptr(counters),
-                                   _ptr(status), _stream_ptr(stream)), "rt_ray_hits_count")
-    return n
+    return _csr_count(lib().rt_ray_hits_count, RayHitsScratchBytes, (triangles, nodes, root, count), rays, _ray_batch(rays), (),
+                      offsets, scratch=scratch, counters=counters, status=status, stream=stream)
 
 
 def RayHitsCollect(triangles, nodes, root: int, count: int, rays, offsets, hits, *, counts=None, counters=None, status=None,
@@ -742,23 +755,14 @@ def RayHitsCollect(triangles, nodes, root: int, count: int, rays, offsets, hits,
     int32 [N], each ray's true row length.  A ray with more records than room sets RT_RAY_HITS_TRUNCATED in `status`.
     Records come in traversal order (unspecified but deterministic; sort by t if an order is needed); on non-split trees each
     crossed triangle appears exactly once.  Asynchronous on `stream`.  Returns N."""
-    n = _ray_batch(rays)
-    if not offsets.is_contiguous() or not hits.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, hits a contiguous device buffer")
-    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
-        raise ValueError(f"counts must hold {n} words")
-    if n == 0:
-        return 0
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    _check(lib().rt_ray_hits_collect(ctypes.byref(a), _ptr(rays), n, _ptr(offsets), _ptr(hits), _ptr(counts), _ptr(counters),
-                                     _ptr(status), _stream_ptr(stream)), "rt_ray_hits_collect")
-    return n
+    return _csr_collect(lib().rt_ray_hits_collect, (triangles, nodes, root, count), rays, _ray_batch(rays), (), offsets, hits,
+                        "hits", counts=counts, counters=counters, status=status, stream=stream)
 
 
 def ray_hits_status(status) -> int:
     """The RT_RAY_HITS_* flags RayHitsCount / RayHitsCollect ORed into `status` (copies the word back: waits for the work queued
     before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
 
 
 def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False, counters=None, status=None, stream=None):
@@ -773,8 +777,7 @@ def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False
     n = _ray_batch(rays)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
     RayHitsCount(triangles, nodes, root, count, rays, offsets, counters=counters, status=status, stream=stream)
-    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-    with ctx:
+    with _on_stream(stream):
         total = int(offsets[n].item())
         hits = torch.empty((max(total, 1), 4), dtype=torch.float32, device=rays.device)[:total]
         RayHitsCollect(triangles, nodes, root, count, rays, offsets, hits, counters=counters, status=status, stream=stream)
@@ -811,19 +814,9 @@ def TriOverlapsCount(triangles, nodes, root: int, count: int, queries, offsets, 
     >= TriOverlapsScratchBytes(N) bytes, 256-byte aligned (device_bytes; taken from torch's allocator when None).  counters:
     optional int64[4] ([0] box tests, [1] leaf records visited).  status: optional device uint32 the call ORs RT_TRI_* flags
     into (see tri_overlap_status).  Asynchronous on `stream`, nothing is read back.  Returns N."""
-    n = _tri_batch(queries)
-    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
-    if scratch is None:
-        scratch = device_bytes(TriOverlapsScratchBytes(n), queries.device)
-    elif _nbytes(scratch) < TriOverlapsScratchBytes(n):
-        raise ValueError(f"scratch must hold TriOverlapsScratchBytes({n}) bytes")
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    # (an empty torch tensor has no storage; the call still wants a pointer and, with n = 0, reads nothing through it)
-    _check(lib().rt_tri_overlaps_count(ctypes.byref(a), _ptr(queries) or _ptr(scratch), n, kTriSelf if self_pairs else 0,
-                                       _ptr(offsets), _ptr(scratch), _ptr(counters), _ptr(status), _stream_ptr(stream)),
-           "rt_tri_overlaps_count")
-    return n
+    return _csr_count(lib().rt_tri_overlaps_count, TriOverlapsScratchBytes, (triangles, nodes, root, count), queries,
+                      _tri_batch(queries), (kTriSelf if self_pairs else 0,), offsets, scratch=scratch, counters=counters,
+                      status=status, stream=stream)
 
 
 def TriOverlapsCollect(triangles, nodes, root: int, count: int, queries, offsets, ids, *, self_pairs: bool = False, counts=None,
@@ -834,24 +827,15 @@ def TriOverlapsCollect(triangles, nodes, root: int, count: int, queries, offsets
     match count.  A query with more matches than room sets RT_TRI_TRUNCATED in `status`.  Ids come in traversal order
     (unspecified but deterministic); on non-split trees each matching triangle appears exactly once.  Asynchronous on
     `stream`.  Returns N."""
-    n = _tri_batch(queries)
-    if not offsets.is_contiguous() or not ids.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
-        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, ids a contiguous device buffer")
-    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
-        raise ValueError(f"counts must hold {n} words")
-    if n == 0:
-        return 0
-    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
-    _check(lib().rt_tri_overlaps_collect(ctypes.byref(a), _ptr(queries), n, kTriSelf if self_pairs else 0, _ptr(offsets),
-                                         _ptr(ids), _ptr(counts), _ptr(counters), _ptr(status), _stream_ptr(stream)),
-           "rt_tri_overlaps_collect")
-    return n
+    return _csr_collect(lib().rt_tri_overlaps_collect, (triangles, nodes, root, count), queries, _tri_batch(queries),
+                        (kTriSelf if self_pairs else 0,), offsets, ids, "ids", counts=counts, counters=counters, status=status,
+                        stream=stream)
 
 
 def tri_overlap_status(status) -> int:
     """The RT_TRI_* flags TriOverlapsCount / TriOverlapsCollect ORed into `status` (copies the word back: waits for the work
     queued before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
 
 
 def TriOverlaps(triangles, nodes, root: int, count: int, queries, *, self_pairs: bool = False, counters=None, status=None,
@@ -866,8 +850,7 @@ def TriOverlaps(triangles, nodes, root: int, count: int, queries, *, self_pairs:
     offsets = torch.empty(n + 1, dtype=torch.int64, device=queries.device)
     TriOverlapsCount(triangles, nodes, root, count, queries, offsets, self_pairs=self_pairs, counters=counters, status=status,
                      stream=stream)
-    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-    with ctx:
+    with _on_stream(stream):
         total = int(offsets[n].item())
     ids = torch.empty(max(total, 1), dtype=torch.int32, device=queries.device)[:total]
     TriOverlapsCollect(triangles, nodes, root, count, queries, offsets, ids, self_pairs=self_pairs, counters=counters,
@@ -900,7 +883,7 @@ def KNearest(triangles, nodes, root: int, count: int, queries, k: int, out, *, c
 
 def knn_status(status) -> int:
     """The RT_KNN_* flags KNearest ORed into `status` (copies the word back: waits for the work queued before it)."""
-    return int(to_host(status, np.uint32, 1)[0])
+    return _status_word(status)
 
 
 def RaySortScratchBytes(num_rays: int) -> int:

@@ -14,15 +14,18 @@
 //     triangle matches by the exact predicate of the header; both instantiations of a shape run this one traversal, so the
 //     count and the collect call visit the same leaves in the same order and cannot disagree;
 //   * a push onto a full stack of 64 is dropped and flagged (RT_RANGE_STACK_OVERFLOW): the result is then a subset;
-//   * COLLECT = false: the lane's match count goes through a workgroup scan (two 21-bit limbs through block_excl_scan_u32);
-//     offsets[i] gets the workgroup-local exclusive prefix and the workgroup's total goes to the scratch.  range_scan_kernel
-//     (one workgroup, 64-bit through three limbs) turns the totals into exclusive prefixes and writes offsets[n];
-//     range_add_kernel adds each workgroup's prefix to its 256 offsets.  Three launches, nothing read back;
+//   * COLLECT = false: the lane's match count goes through a workgroup scan (rt_csr.hpp: two 21-bit limbs); offsets[i] gets
+//     the workgroup-local exclusive prefix and the workgroup's total goes to the scratch.  launch_csr_offsets (csr_scan.hip)
+//     turns the totals into exclusive prefixes, writes offsets[n] and adds each workgroup's prefix to its 256 offsets.  Three
+//     launches, nothing read back;
 //   * COLLECT = true: the lane stores match j < offsets[i+1] - offsets[i] at ids[offsets[i] + j] -- its own segment, in its
 //     own traversal order, plain 4-byte vector stores, no atomics on the output -- and keeps counting beyond the room
 //     (counts[i], RT_RANGE_TRUNCATED).
-// d2, the corner un-rotation, boxdist2 and slot_entry live in rt_point_math.hpp (shared with knn_query.hip).
+// d2, the corner un-rotation, boxdist2 and slot_entry live in rt_point_math.hpp (shared with knn_query.hip); the workgroup
+// geometry, the limb scan and the segment prologue in rt_csr.hpp (shared with ray_hits_query.hip and tri_overlap_query.hip),
+// as does the epilogue csr_finish (shared with tri_overlap_query.hip).
 // Compiled with -ffp-contract=off and IEEE division: every float operation is the one rt_abi.h writes down.
+#include "rt_csr.hpp"
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_point_math.hpp"
@@ -34,9 +37,6 @@ static_assert(sizeof(rt_point_query) == 16, "rt_point_query: one 16-byte record"
 namespace rt {
 
 namespace {
-
-constexpr int kRgStackLds = 16;        // LDS-resident entries per lane: 16 x 4 B x 256 lanes = 16 KB per workgroup
-constexpr uint32_t kRgBlock = kTraceWaves * 64;   // queries per workgroup = offsets per block sum
 
 struct RangeParams {
     const rt_node* nodes;
@@ -51,24 +51,6 @@ struct RangeParams {
     unsigned long long* counters;
     uint32_t* status;
 };
-
-// exclusive scan of one 64-bit value per thread through block_excl_scan_u32, LIMBS limbs of 21 bits: a limb's block sum stays
-// below 2^31 for NT <= 1024, so the 32-bit scans are exact and the result is exact for values below 2^(21 LIMBS).
-// All NT threads must call it (rt_device.hpp: full waves).
-template <int NT, int LIMBS>
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint32_t* ws, uint64_t* total)
-{
-    uint64_t r = 0, t = 0;
-#pragma unroll
-    for (int l = 0; l < LIMBS; l++) {
-        uint32_t tl;
-        const uint32_t e = block_excl_scan_u32<NT>((uint32_t)(v >> (21 * l)) & 0x1FFFFFu, ws, &tl);
-        r += (uint64_t)e << (21 * l);
-        t += (uint64_t)tl << (21 * l);
-    }
-    *total = t;
-    return r;
-}
 
 // the query region, per shape: keep(slot box) and match(triangle).  SPHERE holds (p, dist2_max), BOX holds (lo, hi).
 template <int SHAPE> struct Region;
@@ -117,12 +99,12 @@ template <> struct Region<RT_RANGE_BOX> {
     }
 };
 
-typedef uint32_t RgSpill[kStackMax - kRgStackLds];
+typedef uint32_t RgSpill[kStackMax - kCsrStackLds];
 
 template <int SHAPE, bool COLLECT>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA) void range_query_kernel(RangeParams p)
 {
-    __shared__ uint32_t stack_lds[kTraceWaves][kRgStackLds][64];
+    __shared__ uint32_t stack_lds[kTraceWaves][kCsrStackLds][64];
     __shared__ unsigned long long csum[2];
     __shared__ uint32_t ws[kTraceWaves + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -138,12 +120,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     // collect: the lane's segment [out, out + room)
     uint32_t* out = nullptr;
     uint32_t room = 0;
-    if (COLLECT && in_range) {
-        const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
-        const uint64_t d = o1 > o0 ? o1 - o0 : 0ull;
-        room = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
-        out = p.ids + o0;
-    }
+    if (COLLECT && in_range) out = csr_segment(p.offsets, p.ids, i, room);
 
     lds_u32* const col = (lds_u32*)&stack_lds[wave][0][lane];
     RgSpill spill;
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     auto next_from_stack = [&]() {
         if (sp == 0) { live = false; return; }
         --sp;
-        cur = sp < kRgStackLds ? col[sp * 64] : spill[sp - kRgStackLds];
+        cur = sp < kCsrStackLds ? col[sp * 64] : spill[sp - kCsrStackLds];
     };
     auto emit = [&](uint32_t id) {
         if (COLLECT) {
@@ -195,8 +172,8 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
             const uint32_t e = slot_entry(a, b);
             if (!rg.keep(a, b) || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // outside the region, or an empty run
             if (next == kNoNear) { next = e; continue; }   // the first survivor is visited next, the others wait
-            if (sp < kRgStackLds) col[sp * 64] = e;
-            else if (sp < kStackMax) spill[sp - kRgStackLds] = e;
+            if (sp < kCsrStackLds) col[sp * 64] = e;
+            else if (sp < kStackMax) spill[sp - kCsrStackLds] = e;
             else overflow = true;             // dropped: what lies below it is missing from the result
             sp = min(sp + 1, kStackMax);
         }
@@ -216,65 +193,10 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
         if (live && (cur >> 29) == 0) leaf_step();   // leaf phase: every lane that holds a leaf
     }
 
-    uint32_t flags = overflow ? (uint32_t)RT_RANGE_STACK_OVERFLOW : 0u;
-    if (COLLECT) {
-        if (in_range && p.counts) p.counts[i] = found;
-        if (found > room) flags |= (uint32_t)RT_RANGE_TRUNCATED;
-    } else {
-        // the workgroup's exclusive scan of the counts (a count is below 2^32: two 21-bit limbs); lanes past the batch add 0
-        uint64_t total;
-        const uint64_t ex = block_excl_scan_u64<kTraceWaves * 64, 2>(found, ws, &total);
-        if (in_range) p.offsets[i] = ex;
-        if (threadIdx.x == 0) p.block_sums[vb] = total;
-    }
-    if (p.status) {
-        const bool any_over = __builtin_amdgcn_ballot_w64((flags & RT_RANGE_STACK_OVERFLOW) != 0) != 0;
-        const bool any_trunc = __builtin_amdgcn_ballot_w64((flags & RT_RANGE_TRUNCATED) != 0) != 0;
-        const uint32_t wf = (any_over ? (uint32_t)RT_RANGE_STACK_OVERFLOW : 0u) | (any_trunc ? (uint32_t)RT_RANGE_TRUNCATED : 0u);
-        if (wf && lane == 0) atomicOr(p.status, wf);
-    }
-    if (p.counters) {
-        const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
-        __syncthreads();                      // csum's zeroes
-        if (lane == 0) {
-            atomicAdd(&csum[0], (unsigned long long)bsum);
-            atomicAdd(&csum[1], (unsigned long long)tsum);
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const unsigned long long v = csum[threadIdx.x];
-            if (v) atomicAdd(&p.counters[threadIdx.x], v);
-        }
-    }
+    csr_finish<COLLECT, RT_RANGE_STACK_OVERFLOW, RT_RANGE_TRUNCATED>(
+        in_range, i, vb, lane, overflow, found, room, box_tests, tri_tests, p.offsets, p.block_sums, p.counts, p.status,
+        p.counters, ws, csum);
 }
-
-// in-place exclusive scan of the workgroups' totals (one workgroup; a total is below 2^40, three limbs carry 2^63);
-// *total = their sum = offsets[n]
-__global__ __launch_bounds__(1024) void range_scan_kernel(uint64_t* __restrict__ block_sums, uint32_t nblocks,
-                                                          uint64_t* __restrict__ total)
-{
-    __shared__ uint32_t ws[20];
-    uint64_t running = 0;
-    for (uint32_t c = 0; c < nblocks; c += 1024) {
-        const uint32_t i = c + threadIdx.x;
-        const uint64_t v = i < nblocks ? block_sums[i] : 0ull;
-        uint64_t chunk;
-        const uint64_t ex = block_excl_scan_u64<1024, 3>(v, ws, &chunk);
-        if (i < nblocks) block_sums[i] = running + ex;
-        running += chunk;
-    }
-    if (threadIdx.x == 0) *total = running;
-}
-
-// offsets[i] += the prefix of its workgroup
-__global__ __launch_bounds__(256) void range_add_kernel(uint64_t* __restrict__ offsets, const uint64_t* __restrict__ block_sums,
-                                                        uint32_t n)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < n) offsets[i] += block_sums[i / kRgBlock];
-}
-
-inline uint32_t range_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kRgBlock - 1) / kRgBlock); }
 
 RangeParams range_params(const rt_accel& as, const void* queries, uint32_t num_queries, uint64_t* counters, uint32_t* status)
 {
@@ -292,11 +214,7 @@ RangeParams range_params(const rt_accel& as, const void* queries, uint32_t num_q
 
 }  // namespace
 
-size_t range_scratch_bytes(uint32_t num_queries)
-{
-    const size_t blocks = range_blocks(num_queries);
-    return ((blocks ? blocks : 1) * sizeof(uint64_t) + 255) / 256 * 256;
-}
+size_t range_scratch_bytes(uint32_t num_queries) { return csr_scratch_bytes(num_queries); }
 
 hipError_t launch_range_count(const rt_accel& as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets,
                               void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st)
@@ -304,14 +222,12 @@ hipError_t launch_range_count(const rt_accel& as, const void* queries, uint32_t 
     RangeParams p = range_params(as, queries, num_queries, counters, status);
     p.offsets = offsets;
     p.block_sums = static_cast<uint64_t*>(scratch);
-    const uint32_t blocks = range_blocks(num_queries);
+    const uint32_t blocks = csr_blocks(num_queries);
     if (blocks) {
-        if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, false><<<blocks, kRgBlock, 0, st>>>(p);
-        else range_query_kernel<RT_RANGE_BOX, false><<<blocks, kRgBlock, 0, st>>>(p);
+        if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, false><<<blocks, kCsrBlock, 0, st>>>(p);
+        else range_query_kernel<RT_RANGE_BOX, false><<<blocks, kCsrBlock, 0, st>>>(p);
     }
-    range_scan_kernel<<<1, 1024, 0, st>>>(p.block_sums, blocks, offsets + num_queries);
-    if (blocks) range_add_kernel<<<(uint32_t)(((uint64_t)num_queries + 255) / 256), 256, 0, st>>>(offsets, p.block_sums, num_queries);
-    return hipGetLastError();
+    return launch_csr_offsets(offsets, p.block_sums, num_queries, st);
 }
 
 hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
@@ -321,9 +237,9 @@ hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_
     p.offsets = const_cast<uint64_t*>(offsets);   // (the collect instantiations only read them)
     p.ids = ids;
     p.counts = counts;
-    const uint32_t blocks = range_blocks(num_queries);
-    if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, true><<<blocks, kRgBlock, 0, st>>>(p);
-    else range_query_kernel<RT_RANGE_BOX, true><<<blocks, kRgBlock, 0, st>>>(p);
+    const uint32_t blocks = csr_blocks(num_queries);
+    if (shape == RT_RANGE_SPHERE) range_query_kernel<RT_RANGE_SPHERE, true><<<blocks, kCsrBlock, 0, st>>>(p);
+    else range_query_kernel<RT_RANGE_BOX, true><<<blocks, kCsrBlock, 0, st>>>(p);
     return hipGetLastError();
 }
 

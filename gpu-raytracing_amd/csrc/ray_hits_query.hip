@@ -19,18 +19,18 @@
 //     single-triangle record has v3 == v2 (rt_abi.h, refit block) and every builder gives a leaf slot a count >= 1, which makes
 //     this trace_ray's rule (count > 0 && v3 != v2) on every record the library writes;
 //   * a push onto a full stack of 64 is dropped and flagged (RT_RAY_HITS_STACK_OVERFLOW): the row is then a subset;
-//   * COLLECT = false: the lane's count goes through a workgroup scan (two 21-bit limbs through block_excl_scan_u32);
-//     offsets[i] gets the workgroup-local exclusive prefix and the workgroup's total goes to the scratch.  hits_scan_kernel
-//     (one workgroup, 64-bit through three limbs) turns the totals into exclusive prefixes and writes offsets[n];
-//     hits_add_kernel adds each workgroup's prefix to its 256 offsets.  Three launches, nothing read back.  (The scan is
-//     range_query.hip's, restated here so that file and its kernels stay as they are.)
+//   * COLLECT = false: the lane's count goes through a workgroup scan (rt_csr.hpp: two 21-bit limbs); offsets[i] gets the
+//     workgroup-local exclusive prefix and the workgroup's total goes to the scratch; launch_csr_offsets (csr_scan.hip) does
+//     the rest, as for the range queries.  Three launches, nothing read back.
 //   * COLLECT = true: the lane stores record j < offsets[i+1] - offsets[i] at hits[offsets[i] + j] -- its own segment, in its
 //     own traversal order, one 16-byte vector store, no atomics on the output -- and keeps counting beyond the room
 //     (counts[i], RT_RAY_HITS_TRUNCATED).  (u, v) go back to the caller's corners as in ray_query_kernel.
 // Compiled with -ffp-contract=off and IEEE division: every accepted record is bit for bit the one rt_intersect_rays would
 // report for that triangle.
+#include "rt_csr.hpp"
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
+#include "rt_point_math.hpp"
 #include "rt_traverse.hpp"
 
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 16, "rt_ray: two 16-byte halves; rt_hit: one 16-byte record");
@@ -38,9 +38,6 @@ static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 16, "rt_ray: two 16-byte
 namespace rt {
 
 namespace {
-
-constexpr int kRhStackLds = 16;        // LDS-resident entries per lane: 16 x 4 B x 256 lanes = 16 KB per workgroup
-constexpr uint32_t kRhBlock = kTraceWaves * 64;   // rays per workgroup = offsets per block sum
 
 struct RayHitsParams {
     const rt_node* nodes;
@@ -56,36 +53,12 @@ struct RayHitsParams {
     uint32_t* status;
 };
 
-// exclusive scan of one 64-bit value per thread through block_excl_scan_u32, LIMBS limbs of 21 bits: a limb's block sum stays
-// below 2^31 for NT <= 1024, so the 32-bit scans are exact and the result is exact for values below 2^(21 LIMBS).
-// All NT threads must call it (rt_device.hpp: full waves).
-template <int NT, int LIMBS>
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint32_t* ws, uint64_t* total)
-{
-    uint64_t r = 0, t = 0;
-#pragma unroll
-    for (int l = 0; l < LIMBS; l++) {
-        uint32_t tl;
-        const uint32_t e = block_excl_scan_u32<NT>((uint32_t)(v >> (21 * l)) & 0x1FFFFFu, ws, &tl);
-        r += (uint64_t)e << (21 * l);
-        t += (uint64_t)tl << (21 * l);
-    }
-    *total = t;
-    return r;
-}
-
-// the entry a slot refers to: a leaf (index : 29 | 0) or a box run (child : 29 | count : 3)
-__device__ __forceinline__ uint32_t hits_slot_entry(const uint4& a, const uint4& b)
-{
-    return (b.w >> 29) == RT_CHILD_TRI ? (b.w & kIndexMask) : ((b.w & kIndexMask) | (a.w & ~kIndexMask));
-}
-
-typedef uint32_t RhSpill[kStackMax - kRhStackLds];
+typedef uint32_t RhSpill[kStackMax - kCsrStackLds];
 
 template <bool COLLECT>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA) void ray_hits_kernel(RayHitsParams p)
 {
-    __shared__ uint32_t stack_lds[kTraceWaves][kRhStackLds][64];
+    __shared__ uint32_t stack_lds[kTraceWaves][kCsrStackLds][64];
     __shared__ unsigned long long csum[2];
     __shared__ uint32_t ws[kTraceWaves + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,12 +83,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     // collect: the lane's segment [out, out + room)
     float4* out = nullptr;
     uint32_t room = 0;
-    if (COLLECT && in_range) {
-        const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
-        const uint64_t d = o1 > o0 ? o1 - o0 : 0ull;
-        room = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
-        out = p.hits + o0;
-    }
+    if (COLLECT && in_range) out = csr_segment(p.offsets, p.hits, i, room);
 
     lds_u32* const col = (lds_u32*)&stack_lds[wave][0][lane];
     RhSpill spill;
@@ -128,7 +96,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     auto next_from_stack = [&]() {
         if (sp == 0) { live = false; return; }
         --sp;
-        cur = sp < kRhStackLds ? col[sp * 64] : spill[sp - kRhStackLds];
+        cur = sp < kCsrStackLds ? col[sp * 64] : spill[sp - kCsrStackLds];
     };
     // one triangle (leaf corners c0, c1, c2, rotation rot) against the original window; an accepted one emits its record
     auto test = [&](float c0x, float c0y, float c0z, float c1x, float c1y, float c1z, float c2x, float c2y, float c2z,
@@ -177,14 +145,14 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
             const uint32_t type = b.w >> 29;
             if (type == RT_CHILD_NONE) continue;
             box_tests++;
-            const uint32_t e = hits_slot_entry(a, b);
+            const uint32_t e = slot_entry(a, b);
             float front, back;
             slab(a, b, r, front, back);
             const bool in = (back >= front) & (front <= tmax0) & (back >= r.tmin);
             if (!in || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // missed by the ray, or an empty run
             if (next == kNoNear) { next = e; continue; }   // the first survivor is visited next, the others wait
-            if (sp < kRhStackLds) col[sp * 64] = e;
-            else if (sp < kStackMax) spill[sp - kRhStackLds] = e;
+            if (sp < kCsrStackLds) col[sp * 64] = e;
+            else if (sp < kStackMax) spill[sp - kCsrStackLds] = e;
             else overflow = true;             // dropped: what lies below it is missing from the row
             sp = min(sp + 1, kStackMax);
         }
@@ -237,34 +205,6 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     }
 }
 
-// in-place exclusive scan of the workgroups' totals (one workgroup; a total is below 2^40, three limbs carry 2^63);
-// *total = their sum = offsets[n]
-__global__ __launch_bounds__(1024) void hits_scan_kernel(uint64_t* __restrict__ block_sums, uint32_t nblocks,
-                                                         uint64_t* __restrict__ total)
-{
-    __shared__ uint32_t ws[20];
-    uint64_t running = 0;
-    for (uint32_t c = 0; c < nblocks; c += 1024) {
-        const uint32_t i = c + threadIdx.x;
-        const uint64_t v = i < nblocks ? block_sums[i] : 0ull;
-        uint64_t chunk;
-        const uint64_t ex = block_excl_scan_u64<1024, 3>(v, ws, &chunk);
-        if (i < nblocks) block_sums[i] = running + ex;
-        running += chunk;
-    }
-    if (threadIdx.x == 0) *total = running;
-}
-
-// offsets[i] += the prefix of its workgroup
-__global__ __launch_bounds__(256) void hits_add_kernel(uint64_t* __restrict__ offsets, const uint64_t* __restrict__ block_sums,
-                                                       uint32_t n)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < n) offsets[i] += block_sums[i / kRhBlock];
-}
-
-inline uint32_t hits_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kRhBlock - 1) / kRhBlock); }
-
 RayHitsParams hits_params(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint64_t* counters, uint32_t* status)
 {
     RayHitsParams p = {};
@@ -281,11 +221,7 @@ RayHitsParams hits_params(const rt_accel& as, const rt_ray* rays, uint32_t num_r
 
 }  // namespace
 
-size_t ray_hits_scratch_bytes(uint32_t num_rays)
-{
-    const size_t blocks = hits_blocks(num_rays);
-    return ((blocks ? blocks : 1) * sizeof(uint64_t) + 255) / 256 * 256;
-}
+size_t ray_hits_scratch_bytes(uint32_t num_rays) { return csr_scratch_bytes(num_rays); }
 
 hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
                                  uint64_t* counters, uint32_t* status, hipStream_t st)
@@ -293,11 +229,9 @@ hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_
     RayHitsParams p = hits_params(as, rays, num_rays, counters, status);
     p.offsets = offsets;
     p.block_sums = static_cast<uint64_t*>(scratch);
-    const uint32_t blocks = hits_blocks(num_rays);
-    if (blocks) ray_hits_kernel<false><<<blocks, kRhBlock, 0, st>>>(p);
-    hits_scan_kernel<<<1, 1024, 0, st>>>(p.block_sums, blocks, offsets + num_rays);
-    if (blocks) hits_add_kernel<<<(uint32_t)(((uint64_t)num_rays + 255) / 256), 256, 0, st>>>(offsets, p.block_sums, num_rays);
-    return hipGetLastError();
+    const uint32_t blocks = csr_blocks(num_rays);
+    if (blocks) ray_hits_kernel<false><<<blocks, kCsrBlock, 0, st>>>(p);
+    return launch_csr_offsets(offsets, p.block_sums, num_rays, st);
 }
 
 hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets,
@@ -307,7 +241,7 @@ hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint3
     p.offsets = const_cast<uint64_t*>(offsets);   // (the collect instantiation only reads them)
     p.hits = reinterpret_cast<float4*>(hits);
     p.counts = counts;
-    ray_hits_kernel<true><<<hits_blocks(num_rays), kRhBlock, 0, st>>>(p);
+    ray_hits_kernel<true><<<csr_blocks(num_rays), kCsrBlock, 0, st>>>(p);
     return hipGetLastError();
 }
 

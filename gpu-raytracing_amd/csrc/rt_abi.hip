@@ -267,11 +267,15 @@ int rt_trace_strips(const rt_accel* as, const rt_scene* scene, uint64_t* counter
                         strip_stride, stream);
 }
 
+static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// a tree a query can walk: count = 0 is an empty tree, nothing is read through it
+static inline bool tree_args(const rt_accel* as) { return as && as->count <= 7 && (!as->count || (as->nodes && as->triangles)); }
+
 int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
                       uint32_t num_primitives, uint64_t* counters, void* stream)
 {
-    if (!as || !rays || !hits || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (!tree_args(as) || !rays || !hits) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (reinterpret_cast<uintptr_t>(hits) & 15u)) return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
@@ -279,14 +283,11 @@ int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint
                                    static_cast<hipStream_t>(stream)));
 }
 
-static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
                               uint32_t num_indices, rt_hit* hits, int mode, uint32_t num_primitives, uint64_t* counters,
                               void* stream)
 {
-    if (!as || !rays || !hits || !order || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;
+    if (!tree_args(as) || !rays || !hits || !order) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(order, 4)) return RT_ERR_INVALID_ARGUMENT;
     if (num_indices == 0) return RT_OK;
@@ -391,8 +392,7 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
                                 uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
                                 uint64_t* counters, void* stream)
 {
-    if (!tlas || !rays || !hits || !instance_ids || tlas->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (tlas->count && (!tlas->nodes || !tlas->triangles)) return RT_ERR_INVALID_ARGUMENT;
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
@@ -418,8 +418,7 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream)
 {
-    if (!as || !queries || !hits || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
+    if (!tree_args(as) || !queries || !hits) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(queries, 16) || misaligned(hits, 16) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
     if (num_queries == 0) return RT_OK;
     return hip_rc(launch_point_query(*as, queries, hits, num_queries, counters, status, static_cast<hipStream_t>(stream)));
@@ -427,22 +426,27 @@ int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_poin
 
 size_t rt_range_scratch_bytes(uint32_t num_queries) { return range_scratch_bytes(num_queries); }
 
-// the checks both range entry points share
-static int range_args(const rt_accel* as, const void* queries, int shape, const uint64_t* offsets, const uint32_t* status)
+// the checks the CSR entry points share (every failure is RT_ERR_INVALID_ARGUMENT, so their order cannot be observed).
+// extra_ok: the family's own test (the range shape, the overlap flags); query_align: of its query records
+static bool csr_args(const rt_accel* as, const void* queries, uintptr_t query_align, bool extra_ok, const uint64_t* offsets,
+                     const uint32_t* status)
 {
-    if (!as || !queries || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
-    if (shape != RT_RANGE_SPHERE && shape != RT_RANGE_BOX) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(queries, 16) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
-    return RT_OK;
+    return tree_args(as) && queries && offsets && extra_ok && !misaligned(queries, query_align) && !misaligned(offsets, 8) &&
+           !misaligned(status, 4);
+}
+// ... the count side: the scratch of rt_*_scratch_bytes
+static bool csr_count_args(const void* scratch) { return scratch && !misaligned(scratch, 256); }
+// ... the collect side: rows of row_align bytes, the optional true counts
+static bool csr_collect_args(const void* rows, uintptr_t row_align, const uint32_t* counts)
+{
+    return rows && !misaligned(rows, row_align) && !misaligned(counts, 4);
 }
 
 int rt_range_count(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, uint64_t* offsets, void* scratch,
                    uint64_t* counters, uint32_t* status, void* stream)
 {
-    const int rc = range_args(as, queries, shape, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    const bool shape_ok = shape == RT_RANGE_SPHERE || shape == RT_RANGE_BOX;
+    if (!csr_args(as, queries, 16, shape_ok, offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
     // (num_queries = 0 still launches the scan's one workgroup: offsets[0] = 0)
     return hip_rc(launch_range_count(*as, queries, num_queries, shape, offsets, scratch, counters, status,
                                      static_cast<hipStream_t>(stream)));
@@ -451,9 +455,8 @@ int rt_range_count(const rt_accel* as, const void* queries, uint32_t num_queries
 int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queries, int shape, const uint64_t* offsets,
                      uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
 {
-    const int rc = range_args(as, queries, shape, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!ids || misaligned(ids, 4) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    const bool shape_ok = shape == RT_RANGE_SPHERE || shape == RT_RANGE_BOX;
+    if (!csr_args(as, queries, 16, shape_ok, offsets, status) || !csr_collect_args(ids, 4, counts)) return RT_ERR_INVALID_ARGUMENT;
     if (num_queries == 0) return RT_OK;
     return hip_rc(launch_range_collect(*as, queries, num_queries, shape, offsets, ids, counts, counters, status,
                                        static_cast<hipStream_t>(stream)));
@@ -462,9 +465,8 @@ int rt_range_collect(const rt_accel* as, const void* queries, uint32_t num_queri
 int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
                  uint64_t* counters, uint32_t* status, void* stream)
 {
-    if (!as || !queries || !out || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
+    if (!tree_args(as) || !queries || !out) return RT_ERR_INVALID_ARGUMENT;
     if (k == 0 || k > RT_KNN_MAX_K) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
     if (misaligned(queries, 16) || misaligned(out, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
     if (num_queries == 0) return RT_OK;
     return hip_rc(launch_knn_query(*as, queries, num_queries, k, out, counters, status, static_cast<hipStream_t>(stream)));
@@ -472,21 +474,10 @@ int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num
 
 size_t rt_ray_hits_scratch_bytes(uint32_t num_rays) { return ray_hits_scratch_bytes(num_rays); }
 
-// the checks both all-hit entry points share
-static int ray_hits_args(const rt_accel* as, const rt_ray* rays, const uint64_t* offsets, const uint32_t* status)
-{
-    if (!as || !rays || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
-    if (misaligned(rays, 16) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
-    return RT_OK;
-}
-
 int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
                       uint64_t* counters, uint32_t* status, void* stream)
 {
-    const int rc = ray_hits_args(as, rays, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    if (!csr_args(as, rays, 16, true, offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
     // (num_rays = 0 still launches the scan's one workgroup: offsets[0] = 0)
     return hip_rc(launch_ray_hits_count(*as, rays, num_rays, offsets, scratch, counters, status, static_cast<hipStream_t>(stream)));
 }
@@ -494,9 +485,7 @@ int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
 int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
                         uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
 {
-    const int rc = ray_hits_args(as, rays, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!hits || misaligned(hits, 16) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (!csr_args(as, rays, 16, true, offsets, status) || !csr_collect_args(hits, 16, counts)) return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
     return hip_rc(launch_ray_hits_collect(*as, rays, num_rays, offsets, hits, counts, counters, status,
                                           static_cast<hipStream_t>(stream)));
@@ -504,23 +493,11 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
 
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
 
-// the checks both triangle-overlap entry points share
-static int tri_overlaps_args(const rt_accel* as, const rt_triangle* queries, uint32_t flags, const uint64_t* offsets,
-                             const uint32_t* status)
-{
-    if (!as || !queries || !offsets || as->count > 7) return RT_ERR_INVALID_ARGUMENT;
-    if (as->count && (!as->nodes || !as->triangles)) return RT_ERR_INVALID_ARGUMENT;   // (count = 0: an empty tree, nothing read)
-    if (flags & ~(uint32_t)RT_TRI_SELF) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(queries, 4) || misaligned(offsets, 8) || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
-    return RT_OK;
-}
-
 int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
                           uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
 {
-    const int rc = tri_overlaps_args(as, queries, flags, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!scratch || misaligned(scratch, 256)) return RT_ERR_INVALID_ARGUMENT;
+    const bool flags_ok = !(flags & ~(uint32_t)RT_TRI_SELF);
+    if (!csr_args(as, queries, 4, flags_ok, offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
     // (num_queries = 0 still launches the scan's one workgroup: offsets[0] = 0)
     return hip_rc(launch_tri_overlaps_count(*as, queries, num_queries, (flags & RT_TRI_SELF) != 0, offsets, scratch, counters,
                                             status, static_cast<hipStream_t>(stream)));
@@ -530,9 +507,8 @@ int rt_tri_overlaps_collect(const rt_accel* as, const rt_triangle* queries, uint
                             const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters, uint32_t* status,
                             void* stream)
 {
-    const int rc = tri_overlaps_args(as, queries, flags, offsets, status);
-    if (rc != RT_OK) return rc;
-    if (!ids || misaligned(ids, 4) || misaligned(counts, 4)) return RT_ERR_INVALID_ARGUMENT;
+    const bool flags_ok = !(flags & ~(uint32_t)RT_TRI_SELF);
+    if (!csr_args(as, queries, 4, flags_ok, offsets, status) || !csr_collect_args(ids, 4, counts)) return RT_ERR_INVALID_ARGUMENT;
     if (num_queries == 0) return RT_OK;
     return hip_rc(launch_tri_overlaps_collect(*as, queries, num_queries, (flags & RT_TRI_SELF) != 0, offsets, ids, counts,
                                               counters, status, static_cast<hipStream_t>(stream)));

@@ -261,6 +261,11 @@ hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st);
 hipError_t launch_point_query(const rt_accel& as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                               uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// csr_scan.hip: the tail of every CSR count call.  offsets[0..n) hold workgroup-local exclusive prefixes and block_sums one
+// total per workgroup of 256 queries (rt_csr.hpp); afterwards offsets[0..n] are the exclusive prefixes of the whole batch.
+// Runs for n = 0 too (offsets[0] = 0).
+hipError_t launch_csr_offsets(uint64_t* offsets, uint64_t* block_sums, uint32_t n, hipStream_t st);
+
 // range_query.hip: rt_range_count / rt_range_collect after their argument checks.  Count runs for num_queries = 0 too (it
 // writes offsets[0] = 0); collect is called with num_queries > 0.  queries: rt_point_query (sphere) or rt_range_box (box).
 size_t range_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned

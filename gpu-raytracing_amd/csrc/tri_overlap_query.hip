@@ -17,9 +17,11 @@
 //     axes run in three rolled loops (the two normals, the nine edge crosses, the six in-plane axes) over one projection
 //     routine: the axis operands are picked by selects, so the code stays a fraction of seventeen unrolled copies;
 //   * SELF = true: the query index is the triangle's id; the lane also keeps p1 and p2 for the corner comparisons.
-// The three-launch 64-bit scan is restated here (tri_scan_kernel, tri_add_kernel), as in ray_hits_query.hip.
-// The corner un-rotation and slot_entry live in rt_point_math.hpp.
+// The workgroup geometry, the limb scan, the segment prologue, the epilogue (csr_finish) and the scan over the workgroups'
+// totals are rt_csr.hpp's and csr_scan.hip's (launch_csr_offsets); the corner un-rotation and slot_entry live in
+// rt_point_math.hpp.
 // Compiled with -ffp-contract=off and IEEE division: every float operation is the one rt_abi.h writes down.
+#include "rt_csr.hpp"
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_point_math.hpp"
@@ -38,9 +40,6 @@ namespace rt {
 
 namespace {
 
-constexpr int kToStackLds = 16;        // LDS-resident entries per lane: 16 x 4 B x 256 lanes = 16 KB per workgroup
-constexpr uint32_t kToBlock = kTraceWaves * 64;   // queries per workgroup = offsets per block sum
-
 struct TriOverlapParams {
     const rt_node* nodes;
     const rt_triangle_pair* leaves;
@@ -54,24 +53,6 @@ struct TriOverlapParams {
     unsigned long long* counters;
     uint32_t* status;
 };
-
-// exclusive scan of one 64-bit value per thread through block_excl_scan_u32, LIMBS limbs of 21 bits: a limb's block sum stays
-// below 2^31 for NT <= 1024, so the 32-bit scans are exact and the result is exact for values below 2^(21 LIMBS).
-// All NT threads must call it (rt_device.hpp: full waves).
-template <int NT, int LIMBS>
-__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint32_t* ws, uint64_t* total)
-{
-    uint64_t r = 0, t = 0;
-#pragma unroll
-    for (int l = 0; l < LIMBS; l++) {
-        uint32_t tl;
-        const uint32_t e = block_excl_scan_u32<NT>((uint32_t)(v >> (21 * l)) & 0x1FFFFFu, ws, &tl);
-        r += (uint64_t)e << (21 * l);
-        t += (uint64_t)tl << (21 * l);
-    }
-    *total = t;
-    return r;
-}
 
 struct V3 {
     float x, y, z;
@@ -153,12 +134,12 @@ __device__ __forceinline__ bool no_separating_axis(const QueryTri& q, const Tri&
     return true;
 }
 
-typedef uint32_t ToSpill[kStackMax - kToStackLds];
+typedef uint32_t ToSpill[kStackMax - kCsrStackLds];
 
 template <bool SELF, bool COLLECT>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_TRI_MIN_WAVES) void tri_overlap_kernel(TriOverlapParams p)
 {
-    __shared__ uint32_t stack_lds[kTraceWaves][kToStackLds][64];
+    __shared__ uint32_t stack_lds[kTraceWaves][kCsrStackLds][64];
     __shared__ unsigned long long csum[2];
     __shared__ uint32_t ws[kTraceWaves + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -191,12 +172,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRI_MIN_WAVES) void tri_overla
     // collect: the lane's segment [out, out + room)
     uint32_t* out = nullptr;
     uint32_t room = 0;
-    if (COLLECT && in_range) {
-        const uint64_t o0 = p.offsets[i], o1 = p.offsets[i + 1];
-        const uint64_t d = o1 > o0 ? o1 - o0 : 0ull;
-        room = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d;
-        out = p.ids + o0;
-    }
+    if (COLLECT && in_range) out = csr_segment(p.offsets, p.ids, i, room);
 
     lds_u32* const col = (lds_u32*)&stack_lds[wave][0][lane];
     ToSpill spill;
@@ -209,7 +185,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRI_MIN_WAVES) void tri_overla
     auto next_from_stack = [&]() {
         if (sp == 0) { live = false; return; }
         --sp;
-        cur = sp < kToStackLds ? col[sp * 64] : spill[sp - kToStackLds];
+        cur = sp < kCsrStackLds ? col[sp * 64] : spill[sp - kCsrStackLds];
     };
     auto emit = [&](uint32_t id) {
         if (COLLECT) {
@@ -268,8 +244,8 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRI_MIN_WAVES) void tri_overla
             const uint32_t e = slot_entry(a, b);
             if (!q.keep(a, b) || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // outside the query's box, or an empty run
             if (next == kNoNear) { next = e; continue; }   // the first survivor is visited next, the others wait
-            if (sp < kToStackLds) col[sp * 64] = e;
-            else if (sp < kStackMax) spill[sp - kToStackLds] = e;
+            if (sp < kCsrStackLds) col[sp * 64] = e;
+            else if (sp < kStackMax) spill[sp - kCsrStackLds] = e;
             else overflow = true;             // dropped: what lies below it is missing from the result
             sp = min(sp + 1, kStackMax);
         }
@@ -289,65 +265,10 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRI_MIN_WAVES) void tri_overla
         if (live && (cur >> 29) == 0) leaf_step();   // leaf phase: every lane that holds a leaf
     }
 
-    uint32_t flags = overflow ? (uint32_t)RT_TRI_STACK_OVERFLOW : 0u;
-    if (COLLECT) {
-        if (in_range && p.counts) p.counts[i] = found;
-        if (found > room) flags |= (uint32_t)RT_TRI_TRUNCATED;
-    } else {
-        // the workgroup's exclusive scan of the counts (a count is below 2^32: two 21-bit limbs); lanes past the batch add 0
-        uint64_t total;
-        const uint64_t ex = block_excl_scan_u64<kTraceWaves * 64, 2>(found, ws, &total);
-        if (in_range) p.offsets[i] = ex;
-        if (threadIdx.x == 0) p.block_sums[vb] = total;
-    }
-    if (p.status) {
-        const bool any_over = __builtin_amdgcn_ballot_w64((flags & RT_TRI_STACK_OVERFLOW) != 0) != 0;
-        const bool any_trunc = __builtin_amdgcn_ballot_w64((flags & RT_TRI_TRUNCATED) != 0) != 0;
-        const uint32_t wf = (any_over ? (uint32_t)RT_TRI_STACK_OVERFLOW : 0u) | (any_trunc ? (uint32_t)RT_TRI_TRUNCATED : 0u);
-        if (wf && lane == 0) atomicOr(p.status, wf);
-    }
-    if (p.counters) {
-        const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
-        __syncthreads();                      // csum's zeroes
-        if (lane == 0) {
-            atomicAdd(&csum[0], (unsigned long long)bsum);
-            atomicAdd(&csum[1], (unsigned long long)tsum);
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const unsigned long long v = csum[threadIdx.x];
-            if (v) atomicAdd(&p.counters[threadIdx.x], v);
-        }
-    }
+    csr_finish<COLLECT, RT_TRI_STACK_OVERFLOW, RT_TRI_TRUNCATED>(
+        in_range, i, vb, lane, overflow, found, room, box_tests, tri_tests, p.offsets, p.block_sums, p.counts, p.status,
+        p.counters, ws, csum);
 }
-
-// in-place exclusive scan of the workgroups' totals (one workgroup; a total is below 2^40, three limbs carry 2^63);
-// *total = their sum = offsets[n]
-__global__ __launch_bounds__(1024) void tri_scan_kernel(uint64_t* __restrict__ block_sums, uint32_t nblocks,
-                                                        uint64_t* __restrict__ total)
-{
-    __shared__ uint32_t ws[20];
-    uint64_t running = 0;
-    for (uint32_t c = 0; c < nblocks; c += 1024) {
-        const uint32_t i = c + threadIdx.x;
-        const uint64_t v = i < nblocks ? block_sums[i] : 0ull;
-        uint64_t chunk;
-        const uint64_t ex = block_excl_scan_u64<1024, 3>(v, ws, &chunk);
-        if (i < nblocks) block_sums[i] = running + ex;
-        running += chunk;
-    }
-    if (threadIdx.x == 0) *total = running;
-}
-
-// offsets[i] += the prefix of its workgroup
-__global__ __launch_bounds__(256) void tri_add_kernel(uint64_t* __restrict__ offsets, const uint64_t* __restrict__ block_sums,
-                                                      uint32_t n)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < n) offsets[i] += block_sums[i / kToBlock];
-}
-
-inline uint32_t tri_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kToBlock - 1) / kToBlock); }
 
 TriOverlapParams tri_params(const rt_accel& as, const rt_triangle* queries, uint32_t num_queries, uint64_t* counters,
                             uint32_t* status)
@@ -366,11 +287,7 @@ TriOverlapParams tri_params(const rt_accel& as, const rt_triangle* queries, uint
 
 }  // namespace
 
-size_t tri_overlaps_scratch_bytes(uint32_t num_queries)
-{
-    const size_t blocks = tri_blocks(num_queries);
-    return ((blocks ? blocks : 1) * sizeof(uint64_t) + 255) / 256 * 256;
-}
+size_t tri_overlaps_scratch_bytes(uint32_t num_queries) { return csr_scratch_bytes(num_queries); }
 
 hipError_t launch_tri_overlaps_count(const rt_accel& as, const rt_triangle* queries, uint32_t num_queries, bool self,
                                      uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st)
@@ -378,14 +295,12 @@ hipError_t launch_tri_overlaps_count(const rt_accel& as, const rt_triangle* quer
     TriOverlapParams p = tri_params(as, queries, num_queries, counters, status);
     p.offsets = offsets;
     p.block_sums = static_cast<uint64_t*>(scratch);
-    const uint32_t blocks = tri_blocks(num_queries);
+    const uint32_t blocks = csr_blocks(num_queries);
     if (blocks) {
-        if (self) tri_overlap_kernel<true, false><<<blocks, kToBlock, 0, st>>>(p);
-        else tri_overlap_kernel<false, false><<<blocks, kToBlock, 0, st>>>(p);
+        if (self) tri_overlap_kernel<true, false><<<blocks, kCsrBlock, 0, st>>>(p);
+        else tri_overlap_kernel<false, false><<<blocks, kCsrBlock, 0, st>>>(p);
     }
-    tri_scan_kernel<<<1, 1024, 0, st>>>(p.block_sums, blocks, offsets + num_queries);
-    if (blocks) tri_add_kernel<<<(uint32_t)(((uint64_t)num_queries + 255) / 256), 256, 0, st>>>(offsets, p.block_sums, num_queries);
-    return hipGetLastError();
+    return launch_csr_offsets(offsets, p.block_sums, num_queries, st);
 }
 
 hipError_t launch_tri_overlaps_collect(const rt_accel& as, const rt_triangle* queries, uint32_t num_queries, bool self,
@@ -396,9 +311,9 @@ hipError_t launch_tri_overlaps_collect(const rt_accel& as, const rt_triangle* qu
     p.offsets = const_cast<uint64_t*>(offsets);   // (the collect instantiations only read them)
     p.ids = ids;
     p.counts = counts;
-    const uint32_t blocks = tri_blocks(num_queries);
-    if (self) tri_overlap_kernel<true, true><<<blocks, kToBlock, 0, st>>>(p);
-    else tri_overlap_kernel<false, true><<<blocks, kToBlock, 0, st>>>(p);
+    const uint32_t blocks = csr_blocks(num_queries);
+    if (self) tri_overlap_kernel<true, true><<<blocks, kCsrBlock, 0, st>>>(p);
+    else tri_overlap_kernel<false, true><<<blocks, kCsrBlock, 0, st>>>(p);
     return hipGetLastError();
 }
 

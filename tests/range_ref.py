@@ -68,3 +68,18 @@ def box(lo, hi, tris):
 
 def offsets(counts):
     return np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))]).astype(np.int64)
+
+
+# ------------------------------------------------------------------ inputs of the CSR scan tests (range and all-hit ray queries)
+SCAN_CHUNK_N = (256 * 1024, 256 * 1024 + 1, 256 * 1025 + 37)   # 1024, 1025 and 1026 workgroups of 256 queries
+
+
+def scan_tiny_tris():
+    """four triangles in the planes z = 1, 2, 3, 4; (0.2, 0.2, z) is well inside each"""
+    return np.array([[[-1, -1, z], [3, -1, z], [-1, 3, z]] for z in (1, 2, 3, 4)], F)
+
+
+def scan_reach_pattern(n):
+    """a fixed pattern of reaches 0.5, 1.5 .. 4.5 from (0.2, 0.2, 0): 0 .. 4 of scan_tiny_tris() lie within; no period divides 256"""
+    i = np.arange(n, dtype=np.int64)
+    return ((i * 7 + i // 256) % 5).astype(F) + F(0.5)

@@ -14,7 +14,8 @@
 7. deep fractal trees and wide collapsed trees: exact with status 0; a hand-built comb with 80 pending entries sets
    RT_RANGE_STACK_OVERFLOW and returns a subset;
 8. cross-check: ClosestPoints hits iff the sphere count is > 0 and its id is a member;
-9. build + count + collect captured in one HIP graph replay the eager results."""
+9. build + count + collect captured in one HIP graph replay the eager results;
+10. the shared 64-bit scan (csr_scan.hip) past one chunk of 1024 workgroups and past its lowest 21-bit limb."""
 import numpy as np
 import pytest
 
@@ -447,3 +448,43 @@ def test_range_query_convenience(rt, trees):
         o, i = off.cpu().numpy(), ids.cpu().numpy().view(np.uint32)
         assert (o == rr.offsets(counts)).all()
         assert all((np.sort(i[o[k]:o[k + 1]]) == lists[k]).all() for k in range(len(lists)))
+
+
+# ------------------------------------------------------------------ 10. the scan past one chunk and past one limb
+@pytest.fixture(scope="module")
+def tiny(rt):
+    return _gpu_tree(rt, rr.scan_tiny_tris(), "bottom_up")
+
+
+@pytest.fixture(scope="module")
+def chunk_counts():
+    """brute-force counts of the largest chunk-loop batch, computed once; a smaller batch is its prefix"""
+    reach = rr.scan_reach_pattern(max(rr.SCAN_CHUNK_N))
+    counts = rr.sphere_matrix(np.tile(F([0.2, 0.2, 0.0]), (len(reach), 1)), reach * reach, rr.scan_tiny_tris()).sum(axis=1)
+    assert set(np.unique(counts)) == {0, 1, 2, 3, 4}
+    return counts
+
+
+@pytest.mark.parametrize("n", rr.SCAN_CHUNK_N)
+def test_count_scan_chunk_loop(rt, tiny, chunk_counts, n):
+    """more than 1024 workgroups: the one-workgroup scan over the block sums runs its chunk loop (RangeCount only)"""
+    inp, root, count = tiny
+    reach = rr.scan_reach_pattern(n)
+    q = _queries(np.tile(F([0.2, 0.2, 0.0]), (n, 1)), reach * reach)
+    offsets, _, status, _ = _count(rt, inp.triangles_out, inp.nodes_out, root, count, q)
+    exp = np.concatenate([[0], np.cumsum(chunk_counts[:n], dtype=np.int64)])
+    assert status == 0
+    assert offsets[n] == chunk_counts[:n].sum()
+    assert (offsets == exp).all(), f"first wrong offset at query {int(np.argmax(offsets != exp))}"
+
+
+def test_count_scan_limb_carry(rt, scenes):
+    """every query matches all 16400 triangles: the prefix passes 2^21 inside a workgroup (at lane 128) and in the block
+    totals, so both scans carry out of their lowest 21-bit limb (RangeCount only)"""
+    ntri, n = 16400, 512
+    inp, root, count = _gpu_tree(rt, scenes.soup(ntri, 11), "bottom_up")
+    pts = np.random.default_rng(5).uniform(-1.0, 2.0, (n, 3)).astype(F)
+    offsets, _, status, _ = _count(rt, inp.triangles_out, inp.nodes_out, root, count, _queries(pts, F(1e30)))
+    assert status == 0
+    assert 128 * ntri >= 1 << 21 > 127 * ntri
+    assert (offsets == ntri * np.arange(n + 1, dtype=np.int64)).all()

@@ -533,3 +533,21 @@ def test_ray_hits_convenience_sorted(world, tree):
         key = list(zip(row["t"].tolist(), row["primitive_id"].tolist()))
         assert key == sorted(key), f"ray {k}: not ascending in (t, primitive_id): {key}"
     assert max(len(x) for x in rows) >= 3
+
+
+# ------------------------------------------------------------------ the shared scan through a second caller
+def test_count_scan_chunk_loop(rt):
+    """1025 workgroups of rays: the scan over the block sums runs its chunk loop for RayHitsCount as for RangeCount
+    (range_ref.py: the same four triangles, the same pattern).  A ray from (0.2, 0.2, 0) along +z with window
+    [0, tmax] crosses the planes z = 1 .. 4 that lie below tmax = 0.5, 1.5 .. 4.5."""
+    import range_ref as rr
+    n = rr.SCAN_CHUNK_N[1]
+    inp, root, count = _gpu_tree(rt, rr.scan_tiny_tris(), "bottom_up")
+    rays = np.zeros(n, rh.RAY)
+    rays["origin"], rays["dir"], rays["tmax"] = F([0.2, 0.2, 0.0]), F([0.0, 0.0, 1.0]), rr.scan_reach_pattern(n)
+    counts = (F([1, 2, 3, 4])[None, :] <= rays["tmax"][:, None]).sum(axis=1)
+    assert set(np.unique(counts)) == {0, 1, 2, 3, 4}
+    offsets, _, status, _ = _count(rt, inp.triangles_out, inp.nodes_out, root, count, _dev_rays(rt, rays))
+    exp = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    assert status == 0
+    assert (offsets == exp).all(), f"first wrong offset at ray {int(np.argmax(offsets != exp))}"
