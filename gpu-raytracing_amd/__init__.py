@@ -13,7 +13,9 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
 ``RayHits``: every triangle a ray crosses inside its window, as CSR), triangle-overlap queries (``TriOverlapsCount``,
 ``TriOverlapsCollect``, ``TriOverlaps``: every triangle a query triangle cuts, as CSR; ``self_pairs`` for the
-self-intersections of the mesh the tree was built over), and ray sorting (``SortRays``: a coherence
+self-intersections of the mesh the tree was built over), signed distance and occupancy (``SignedDistance``, ``Occupancy``:
+how far the nearest triangle is and whether a point is inside a closed mesh, in one launch; ``GenerateGridPoints`` for the
+lattice such queries usually run on), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -84,6 +86,14 @@ RT_RAY_HITS_STACK_OVERFLOW, RT_RAY_HITS_TRUNCATED = 1, 2
 # triangle-overlap queries (rt_tri_overlaps_count / rt_tri_overlaps_collect): TRIANGLE records in, CSR rows of ids out
 kTriSelf = 1
 RT_TRI_STACK_OVERFLOW, RT_TRI_TRUNCATED = 1, 2
+# signed distance and occupancy (rt_signed_distance / rt_occupancy): POINT_QUERY records in, SDF_HIT records or bytes out
+SDF_HIT = np.dtype([("sdist", "<f4"), ("primitive_id", "<u4")])                                              # 8 B
+assert SDF_HIT.itemsize == 8
+RT_SDF_MAX_VOTES = 3
+RT_SDF_STACK_OVERFLOW = 1
+SDF_DEFAULT_DIRS = np.array([[0.577, 0.211, 0.789], [-0.683, 0.619, 0.387], [0.259, -0.857, 0.446]], np.float32)
+SDF_DEFAULT_DIRS.setflags(write=False)
+kGridRowMajor, kGridBricks = 0, 1
 
 INDEX_MASK = 0x1FFFFFFF
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
@@ -162,6 +172,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
+           "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
 
 _lib = None
@@ -259,6 +270,13 @@ def lib() -> ctypes.CDLL:
     L.rt_tri_overlaps_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp, vp]
     L.rt_tri_overlaps_collect.restype = i32
     L.rt_tri_overlaps_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp, vp, vp]
+    fp = ctypes.POINTER(ctypes.c_float)
+    L.rt_signed_distance.restype = i32
+    L.rt_signed_distance.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, fp, vp, vp, vp, vp]
+    L.rt_occupancy.restype = i32
+    L.rt_occupancy.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, fp, vp, vp, vp, vp]
+    L.rt_generate_grid_points.restype = i32
+    L.rt_generate_grid_points.argtypes = [fp, fp, ctypes.POINTER(u32), ctypes.c_float, i32, vp, vp]
     L.rt_generate_shadow_rays.restype = i32
     L.rt_generate_shadow_rays.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.rt_shade_frame.restype = i32
@@ -884,6 +902,89 @@ def KNearest(triangles, nodes, root: int, count: int, queries, k: int, out, *, c
 def knn_status(status) -> int:
     """The RT_KNN_* flags KNearest ORed into `status` (copies the word back: waits for the work queued before it)."""
     return _status_word(status)
+
+
+def _sdf_call(entry, triangles, nodes, root: int, count: int, queries, result, record: int, votes, dirs, counters, status,
+              stream) -> int:
+    votes = int(votes)
+    if votes not in (1, RT_SDF_MAX_VOTES):
+        raise ValueError(f"votes must be 1 or {RT_SDF_MAX_VOTES}")
+    if not queries.is_contiguous() or not result.is_contiguous() or _nbytes(queries) % 16:
+        raise ValueError("queries must be a contiguous device buffer of 16-byte records, the output a contiguous device buffer")
+    n = _nbytes(queries) // 16
+    if _nbytes(result) < record * n:
+        raise ValueError(f"the output must hold {n} records of {record} byte(s)")
+    d = None
+    if dirs is not None:
+        host = np.ascontiguousarray(dirs, np.float32).reshape(-1)
+        if host.size < 3 * votes:
+            raise ValueError(f"dirs must hold {votes} directions of 3 floats")
+        d = (ctypes.c_float * (3 * votes))(*host[:3 * votes].tolist())
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(entry(ctypes.byref(a), _ptr(queries), n, votes, d, _ptr(result), _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           entry.__name__)
+    return n
+
+
+def SignedDistance(triangles, nodes, root: int, count: int, queries, out, *, votes: int = 3, dirs=None, counters=None,
+                   status=None, stream=None) -> int:
+    """rt_signed_distance: for each POINT_QUERY record of `queries` (a contiguous device tensor of 16-byte records
+    (p, dist2_max), e.g. float32 [N, 4]) one SDF_HIT record (sdist, primitive_id) in `out` (>= 8 N bytes, e.g. float32 [N, 2];
+    view it as int32 for primitive_id).  (sdist**2, primitive_id) is ClosestPoints's nearest triangle within dist2_max
+    (|sdist| = sqrt(dist2); {inf, MISS} beyond the radius), negative when the point is inside: `votes` rays (1 or 3; the third
+    only where the first two disagree) along `dirs` (host float32 [votes, 3]; None = SDF_DEFAULT_DIRS) are counted as by
+    RayHitsCount and the majority of odd counts decides.  The sign means something only for a closed mesh on a tree without
+    spatial splits.  counters: optional int64[4] ([0] box tests, [1] leaf records, over every traversal that ran).  status:
+    optional device uint32 the call ORs RT_SDF_STACK_OVERFLOW into (see sdf_status).  Asynchronous on `stream`, nothing is
+    allocated or read back.  Returns N."""
+    return _sdf_call(lib().rt_signed_distance, triangles, nodes, root, count, queries, out, 8, votes, dirs, counters, status,
+                     stream)
+
+
+def Occupancy(triangles, nodes, root: int, count: int, queries, inside, *, votes: int = 3, dirs=None, counters=None,
+              status=None, stream=None) -> int:
+    """rt_occupancy: the inside / outside bit of SignedDistance alone: inside[i] = 1 or 0 for queries[i] (`inside`: a contiguous
+    device buffer of >= N bytes, e.g. uint8 [N]).  dist2_max only decides whether the query is traced (NaN or negative: not
+    traced, outside).  Other arguments as for SignedDistance.  Returns N."""
+    return _sdf_call(lib().rt_occupancy, triangles, nodes, root, count, queries, inside, 1, votes, dirs, counters, status, stream)
+
+
+def sdf_status(status) -> int:
+    """The RT_SDF_* flags SignedDistance / Occupancy ORed into `status` (copies the word back: waits for the work queued before
+    it)."""
+    return _status_word(status)
+
+
+def GridPointCount(dims, bricks: bool = False) -> int:
+    """Number of records GenerateGridPoints writes: dims[0]*dims[1]*dims[2] row-major, ceil(dims/4) bricks of 64 per axis
+    product in the brick layout (0 when a dimension is 0)."""
+    dx, dy, dz = (int(v) for v in dims)
+    if min(dx, dy, dz) <= 0:
+        return 0
+    return ((dx + 3) // 4) * ((dy + 3) // 4) * ((dz + 3) // 4) * 64 if bricks else dx * dy * dz
+
+
+def GenerateGridPoints(origin, spacing, dims, queries, *, dist2_max: float = float("inf"), bricks: bool = False,
+                       stream=None) -> int:
+    """rt_generate_grid_points: the POINT_QUERY records of a lattice, point (i, j, k) = origin + (i, j, k) * spacing in float32
+    (one multiply, one add), every one with `dist2_max`, into `queries` (a contiguous device tensor of at least
+    GridPointCount(dims, bricks) * 16 bytes, e.g. float32 [N, 4]).  Row-major: index (k*dims[1] + j)*dims[0] + i.  Bricks:
+    4x4x4 bricks in row-major brick order, 64 records each, lane = 3-D Morton code of the offset in the brick (one wave of
+    SignedDistance / Occupancy gets one brick); off-lattice lanes of edge bricks get {0, 0, 0, -1}, a query that is not traced.
+    origin, spacing, dims: host triples.  Asynchronous on `stream`.  Returns the number of records written."""
+    n = GridPointCount(dims, bricks)
+    if not queries.is_contiguous() or _nbytes(queries) < 16 * n:
+        raise ValueError(f"queries must be a contiguous device buffer of >= {16 * n} bytes")
+    if n == 0:
+        return 0
+    o = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    sp = (ctypes.c_float * 3)(*[float(v) for v in spacing])
+    d = (ctypes.c_uint32 * 3)(*[int(v) for v in dims])
+    _check(lib().rt_generate_grid_points(o, sp, d, float(dist2_max), kGridBricks if bricks else kGridRowMajor,
+                                         _ptr(queries), _stream_ptr(stream)), "rt_generate_grid_points")
+    return n
 
 
 def RaySortScratchBytes(num_rays: int) -> int:

@@ -37,6 +37,8 @@ namespace {
 
 constexpr int kPtStackLds = 16;   // LDS-resident entries per lane: 16 x 8 B x 256 lanes = 32 KB per workgroup
 constexpr int kPtRestarts = 2;    // passes from the root after a pass that dropped a push (each starts from the best so far)
+// (sdf_query.hip restates this traversal -- kSdfStackLds, kSdfRestarts, the 8-byte entries of RT_POINT_DIST_STACK = 1 -- and
+// promises rt_closest_points's record bit for bit, dropped pushes included: change the two files together)
 
 struct PointParams {
     const rt_node* nodes;

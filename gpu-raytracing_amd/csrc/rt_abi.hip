@@ -514,6 +514,51 @@ int rt_tri_overlaps_collect(const rt_accel* as, const rt_triangle* queries, uint
                                               counters, status, static_cast<hipStream_t>(stream)));
 }
 
+// rt_signed_distance / rt_occupancy: the default vote directions of rt_abi.h
+static const float kSdfDefaultDirs[3 * RT_SDF_MAX_VOTES] = {0.577f, 0.211f, 0.789f, -0.683f, 0.619f, 0.387f, 0.259f, -0.857f, 0.446f};
+
+static bool sdf_args(const rt_accel* as, const rt_point_query* queries, uint32_t votes, const void* result, uintptr_t result_align,
+                     const uint32_t* status)
+{
+    return tree_args(as) && queries && result && (votes == 1 || votes == RT_SDF_MAX_VOTES) && !misaligned(queries, 16) &&
+           !misaligned(result, result_align) && !misaligned(status, 4);
+}
+
+int rt_signed_distance(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                       const float* dirs, rt_sdf_hit* out, uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!sdf_args(as, queries, votes, out, 8, status)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_signed_distance(*as, queries, num_queries, votes, dirs ? dirs : kSdfDefaultDirs, out, counters, status,
+                                         static_cast<hipStream_t>(stream)));
+}
+
+int rt_occupancy(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                 const float* dirs, uint8_t* inside, uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!sdf_args(as, queries, votes, inside, 1, status)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_queries == 0) return RT_OK;
+    return hip_rc(launch_occupancy(*as, queries, num_queries, votes, dirs ? dirs : kSdfDefaultDirs, inside, counters, status,
+                                   static_cast<hipStream_t>(stream)));
+}
+
+int rt_generate_grid_points(const float origin[3], const float spacing[3], const uint32_t dims[3], float dist2_max,
+                            int layout, rt_point_query* queries, void* stream)
+{
+    if (!origin || !spacing || !dims || !queries || misaligned(queries, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (layout != RT_GRID_ROW_MAJOR && layout != RT_GRID_BRICKS) return RT_ERR_INVALID_ARGUMENT;
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0) return RT_OK;
+    // the record count, checked factor by factor: every partial product is below 2^64
+    const bool bricks = layout == RT_GRID_BRICKS;
+    uint64_t n = bricks ? 64u : 1u;
+    for (int a = 0; a < 3; a++) {
+        n *= bricks ? ((uint64_t)dims[a] + 3u) / 4u : (uint64_t)dims[a];
+        if (n > 0xFFFFFFFFull) return RT_ERR_TOO_LARGE;
+    }
+    return hip_rc(launch_grid_points(origin, spacing, dims, dist2_max, bricks, (uint32_t)n, queries,
+                                     static_cast<hipStream_t>(stream)));
+}
+
 int rt_generate_shadow_rays(const rt_ray* rays, const rt_hit* hits, uint32_t num_rays, uint32_t num_triangles,
                             const float* light, rt_ray* shadow_rays, void* stream)
 {
@@ -602,6 +647,10 @@ const char* rt_version_string(void)
            "trioverlap: triangle-overlap queries, every triangle a caller triangle cuts (vertex boxes + seventeen separating "
            "axes in three rolled loops, first separating axis leaves), optional self mode (j > i, no shared corner), the "
            "range query's frame and CSR output | "
+           "sdf: signed distance and occupancy in one launch, one lane per query, the point query's distance-ordered traversal "
+           "(weight-free d2) then 1 or 3 parity votes by the all-hit traversal (fixed window, a counter instead of a row) on one "
+           "64-entry stack (16 in LDS), third vote only where the first two disagree, 8-byte records or one byte, grid points "
+           "row-major or in 4x4x4 Morton bricks | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
            "instantiations, shadow rays as a ray batch for the any-hit query";
 }

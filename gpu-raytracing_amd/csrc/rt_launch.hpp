@@ -296,4 +296,13 @@ hipError_t launch_tri_overlaps_collect(const rt_accel& as, const rt_triangle* qu
                                        const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters,
                                        uint32_t* status, hipStream_t st);
 
+// sdf_query.hip: rt_signed_distance / rt_occupancy after their argument checks (num_queries > 0, votes 1 or 3, dirs: host
+// float[3 * votes], never null here), rt_generate_grid_points after its checks (num_points > 0 records to write)
+hipError_t launch_signed_distance(const rt_accel& as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                                  const float* dirs, rt_sdf_hit* out, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_occupancy(const rt_accel& as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                            const float* dirs, uint8_t* inside, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_grid_points(const float origin[3], const float spacing[3], const uint32_t dims[3], float dist2_max, bool bricks,
+                              uint32_t num_points, rt_point_query* queries, hipStream_t st);
+
 }  // namespace rt

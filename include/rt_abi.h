@@ -762,6 +762,97 @@ int rt_tri_overlaps_collect(const rt_accel* as, const rt_triangle* queries, uint
                             const uint64_t* offsets, uint32_t* ids, uint32_t* counts, uint64_t* counters,
                             uint32_t* status, void* stream);
 
+/* ---- signed distance and occupancy (no reference counterpart).  For each caller point: how far is the nearest triangle, and is
+ * the point INSIDE the closed mesh the tree was built over -- the two calls mesh-query libraries offer next to closest points
+ * (SDF volumes for marching cubes, collision margins, voxelisation, point-in-solid tests), through any tree rt_intersect_rays
+ * takes (runs of 1..7 slots; an empty tree, count = 0, is accepted: every query is a miss and outside).  One launch per call;
+ * both halves of the result are defined by blocks above, so the result equals a composition of rt_closest_points and
+ * rt_ray_hits_count bit for bit.
+ *
+ * Queries: rt_point_query records (p, dist2_max), with rt_closest_points's liveness rule: a query with a non-finite component
+ * of p, a NaN dist2_max or a negative dist2_max is not traced by either call -- its output is {+inf, RT_MISS} / inside = 0 and no
+ * tests are counted for it.  rt_occupancy uses dist2_max for this rule and for nothing else.
+ *
+ * Distance half (rt_signed_distance).  (dist2, primitive_id) is EXACTLY the pair rt_closest_points reports for the query: the
+ * lexicographic minimum of (d2, id) over the triangles with d2 <= dist2_max, d2 the closest-point block's float32 routine
+ * (Ericson, the clamp into the vertex box, the squared distance) on the caller's corners in the caller's order, the search
+ * started from (dist2_max, RT_MISS), a slot or a popped entry skipped iff boxdist2 > best (never on equality), the same visiting
+ * order (nearest surviving slot first, ties to the lower slot), the same restarts (below).  Hence the same exactness statement:
+ * bit for bit the brute force on LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs and every refitted tree; on spatial-split
+ * trees dist2 is d2(p, tri[primitive_id]) bit for bit and sqrt(dist2) exceeds the brute-force minimum by at most 2^-20 * M.
+ *   |sdist| = sqrtf(dist2), the correctly rounded float32 square root.  No query triangle within the radius: primitive_id =
+ *   RT_MISS and |sdist| = +inf; the sign is computed all the same (a point deep inside with a small radius gives -inf).
+ *   No weights are reported: a caller who wants the closest point itself calls rt_closest_points.
+ *
+ * Sign half (both calls).  Vote j < votes casts the ray (origin = p, tmin = 0, dir = D[j], tmax = +inf) and takes its crossing
+ * count c_j = the length of the row the all-hit block defines for that ray: the same slot test (back >= front && front <= tmax
+ * && back >= tmin on rt_trace's slab test, 1/dir computed once per vote by IEEE division), the same leaf test (rt_trace's
+ * Moller-Trumbore on the stored corners, A = (v0, v1, v2), and B = (v2, v1, v3) iff v3 != v2 bit for bit), the window fixed for the
+ * whole traversal.  As there, c_j is a function of the tree's bytes and the ray alone.
+ *   inside = (number of j with c_j odd) * 2 > votes
+ *   sdist  = inside ? -|sdist| : |sdist|, except that dist2 == 0 always gives +0 (a point on the surface has no side).
+ * votes is 1 or 3 (RT_SDF_MAX_VOTES).  With votes = 3 a query whose first two votes agree does NOT cast the third: the majority
+ * is already decided, so the result is the same -- but the counters below see two traversals for it, not three.
+ * dirs: a HOST pointer to 3 * votes floats (D[j] = dirs[3j .. 3j+2]), copied into the kernel arguments at call time, or null for
+ * the default directions
+ *   D0 = ( 0.577f,  0.211f, 0.789f)
+ *   D1 = (-0.683f,  0.619f, 0.387f)
+ *   D2 = ( 0.259f, -0.857f, 0.446f)
+ * -- not normalised (nothing here needs it), not axis-aligned, no two components of equal magnitude, so none of them runs along
+ * the edges or diagonals of an axis-aligned lattice or box.  A caller direction with a zero or non-finite component is accepted
+ * exactly as rt_ray_hits_count accepts it (1/0 = inf in the slab test); a NaN component makes that vote's ray dead: c_j = 0, even.
+ *
+ * What the sign means -- and where it means nothing:
+ *   - only for a CLOSED mesh: there, every ray from a point crosses the surface an odd number of times iff the point is inside.
+ *     For an open mesh the votes are still the parities defined above, but "inside" has no meaning;
+ *   - only on trees where each triangle sits in one leaf: LBVH, pairs, hybrid, hybrid + pairs, SAH, SAH + pairs and their refits.
+ *     On spatial-split trees (rt_run_sah_build with enable_splits) a triangle is counted once per reached REFERENCE, so the
+ *     parity and the sign mean nothing there, and refit does not repair it (the references stay).  The distance half keeps the
+ *     closest-point block's statement for split trees.  rt_accel carries no flag that says "split tree", so the library CANNOT
+ *     refuse one: the caller must not ask a split tree for a sign;
+ *   - Moller-Trumbore here is not watertight: a ray through a shared edge or corner can be counted zero or two times instead of
+ *     once.  That is what the vote is for: three directions rarely graze edges for the same point.  With votes = 1 the caller
+ *     gets the raw parity of one ray.
+ *
+ * Stack: 64 pending entries per query in either half, as in the blocks they come from; a push beyond them is dropped.  A
+ * distance pass that dropped a push is run again from the root with the best so far, at most twice (rt_closest_points's rule).
+ * RT_SDF_STACK_OVERFLOW is ORed into *status when the last distance pass of a query still dropped a push (its record is an
+ * exact (d2, id) of a real triangle but may not be the nearest), or when any parity traversal of a query dropped a push (its
+ * count is then a lower bound, so its parity -- and the sign -- is unknown).
+ * counters: optional device uint64[4]: [0] += non-NONE slots examined, [1] += leaf records visited, both summed over every
+ * traversal that actually ran (every distance pass, every vote that was cast); [2] / [3] are not touched.  One LDS reduction +
+ * 2 device atomics per workgroup of 256 queries.  status: optional device uint32 the calls OR flags into (the caller clears it).
+ * rt_signed_distance: out[i] for queries[i], i < num_queries, one 8-byte record; rt_occupancy: inside[i] = 0 or 1, one byte;
+ * nothing is written at i >= num_queries.  Asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable;
+ * dirs is read on the host during the call).  num_queries = 0 with valid arguments: nothing runs.
+ * Argument errors, returned before any GPU work and before the empty-batch return (RT_ERR_INVALID_ARGUMENT): a null as / queries /
+ * out / inside, a tree with count > 0 and a null node or leaf pointer, count > 7, votes not 1 or 3, queries not 16-byte
+ * aligned, out not 8-byte aligned, status not 4-byte aligned.
+ *
+ * rt_generate_grid_points: the lattice counterpart of rt_generate_camera_rays.  Point (i, j, k), i < dims[0], j < dims[1],
+ * k < dims[2], is p = (origin[0] + (float)i * spacing[0], origin[1] + (float)j * spacing[1], origin[2] + (float)k * spacing[2])
+ * -- float32, one multiplication and then one addition per component, each rounded on its own (no fused multiply-add) -- with
+ * the given dist2_max.  origin, spacing, dims: HOST pointers read during the call.  Layouts:
+ *   RT_GRID_ROW_MAJOR  dims[0]*dims[1]*dims[2] records; point (i, j, k) at index (k*dims[1] + j)*dims[0] + i
+ *   RT_GRID_BRICKS     nbx*nby*nbz*64 records, nb = ceil(dims / 4) per axis; brick (bx, by, bz) has number (bz*nby + by)*nbx + bx
+ *                      and holds its 64 points at brick*64 + lane, point (4*bx + lx, 4*by + ly, 4*bz + lz) with lane the 3-D
+ *                      Morton code of the offset: lx = lane bits 0, 3, ly = bits 1, 4, lz = bits 2, 5 -- one wave of either
+ *                      query gets one 4 x 4 x 4 brick.  Off-lattice lanes of edge bricks get {0, 0, 0, -1}: a negative radius,
+ *                      so the query is not traced.
+ * queries: 16-byte aligned device array of that many records.  Asynchronous, hipGraph-capturable.  A lattice with a zero
+ * dimension: nothing runs.  Errors, before any GPU work: a null origin / spacing / dims / queries, queries not 16-byte aligned
+ * or a bad layout (RT_ERR_INVALID_ARGUMENT); a record count that does not fit 32 bits (RT_ERR_TOO_LARGE). */
+typedef struct rt_sdf_hit { float sdist; uint32_t primitive_id; } rt_sdf_hit;
+#define RT_SDF_MAX_VOTES 3
+enum { RT_SDF_STACK_OVERFLOW = 1 };
+int rt_signed_distance(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                       const float* dirs, rt_sdf_hit* out, uint64_t* counters, uint32_t* status, void* stream);
+int rt_occupancy(const rt_accel* as, const rt_point_query* queries, uint32_t num_queries, uint32_t votes,
+                 const float* dirs, uint8_t* inside, uint64_t* counters, uint32_t* status, void* stream);
+enum { RT_GRID_ROW_MAJOR = 0, RT_GRID_BRICKS = 1 };
+int rt_generate_grid_points(const float origin[3], const float spacing[3], const uint32_t dims[3], float dist2_max,
+                            int layout, rt_point_query* queries, void* stream);
+
 /* ---- deferred shading (no reference counterpart: the reference shades inside TraceRays, Tracer.cu:471-595).  The ray queries
  * give (t, primitive_id, u, v) records; these two calls turn records into rt_trace's frames:
  *   rt_generate_camera_rays -> rt_intersect_rays(closest) -> [rt_generate_shadow_rays -> rt_intersect_rays(any hit)] ->
