@@ -83,6 +83,9 @@ RT_KNN_MAX_K = 32
 RT_KNN_STACK_OVERFLOW = 1
 # all-hit ray queries (rt_ray_hits_count / rt_ray_hits_collect): RAY records in, CSR rows of HIT records out
 RT_RAY_HITS_STACK_OVERFLOW, RT_RAY_HITS_TRUNCATED = 1, 2
+# first-K ray queries (rt_ray_first_hits): RAY records in, rows of k HIT records out
+RT_RAY_FIRST_MAX_K = 32
+RT_RAY_FIRST_STACK_OVERFLOW = 1
 # triangle-overlap queries (rt_tri_overlaps_count / rt_tri_overlaps_collect): TRIANGLE records in, CSR rows of ids out
 kTriSelf = 1
 RT_TRI_STACK_OVERFLOW, RT_TRI_TRUNCATED = 1, 2
@@ -171,6 +174,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
+           "rt_ray_first_hits",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
@@ -264,6 +268,8 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_count.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp]
     L.rt_ray_hits_collect.restype = i32
     L.rt_ray_hits_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp, vp]
+    L.rt_ray_first_hits.restype = i32
+    L.rt_ray_first_hits.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -771,7 +777,7 @@ def RayHitsCollect(triangles, nodes, root: int, count: int, rays, offsets, hits,
     (`hits`: a contiguous device buffer of 16-byte records, e.g. float32 [total, 4], that the offsets stay inside -- the
     caller's contract; `offsets`: int64 [N + 1] from RayHitsCount, or i * K for a fixed K per ray).  counts: optional device
     int32 [N], each ray's true row length.  A ray with more records than room sets RT_RAY_HITS_TRUNCATED in `status`.
-    Records come in traversal order (unspecified but deterministic; sort by t if an order is needed); on non-split trees each
+    Records come in traversal order (unspecified but deterministic; RayFirstHits gives the first k in order); on non-split trees each
     crossed triangle appears exactly once.  Asynchronous on `stream`.  Returns N."""
     return _csr_collect(lib().rt_ray_hits_collect, (triangles, nodes, root, count), rays, _ray_batch(rays), (), offsets, hits,
                         "hits", counts=counts, counters=counters, status=status, stream=stream)
@@ -810,6 +816,33 @@ def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False
             order = order[torch.argsort(key[order], stable=True)]
             hits = hits[order].contiguous()
     return offsets, hits
+
+
+def RayFirstHits(triangles, nodes, root: int, count: int, rays, k: int, out, *, counters=None, status=None, stream=None) -> int:
+    """rt_ray_first_hits: for each ray of `rays` (32-byte RAY records, e.g. float32 [N, 8]) a row of k HIT records
+    (t, primitive_id bits, u, v) in `out` (float32 [N, k, 4] on the device; view column 1 as int32): the k nearest crossings
+    inside the ray's [tmin, tmax] window in ascending (t, primitive_id) order, padded with {+inf, MISS, 0, 0}.
+    1 <= k <= RT_RAY_FIRST_MAX_K.  One launch: the window shrinks to the k-th hit while the ray is traced.  Any tree Trace()
+    takes.  Exactness: include/rt_abi.h, first-K block (decided / undecided rays).  counters: optional int64[4] device tensor
+    ([0] box tests, [1] leaf records visited).  status: optional device uint32 the call ORs RT_RAY_FIRST_STACK_OVERFLOW into
+    (the caller clears it; see ray_first_status).  Asynchronous on `stream`, nothing is allocated or read back.  Returns N."""
+    k = int(k)
+    if not 1 <= k <= RT_RAY_FIRST_MAX_K:
+        raise ValueError(f"k must be in 1 .. {RT_RAY_FIRST_MAX_K}")
+    n = _ray_batch(rays)
+    if not out.is_contiguous() or out.dtype != _torch().float32 or tuple(out.shape) != (n, k, 4):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape [{n}, {k}, 4]")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_ray_first_hits(ctypes.byref(a), _ptr(rays), n, k, _ptr(out), _ptr(counters), _ptr(status),
+                                   _stream_ptr(stream)), "rt_ray_first_hits")
+    return n
+
+
+def ray_first_status(status) -> int:
+    """The RT_RAY_FIRST_* flags RayFirstHits ORed into `status` (copies the word back: waits for the work queued before it)."""
+    return _status_word(status)
 
 
 def TriOverlapsScratchBytes(num_queries: int) -> int:

@@ -491,6 +491,17 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
                                           static_cast<hipStream_t>(stream)));
 }
 
+int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out, uint64_t* counters,
+                      uint32_t* status, void* stream)
+{
+    if (!tree_args(as) || !rays || !out) return RT_ERR_INVALID_ARGUMENT;
+    if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(out, 16) || misaligned(status, 4) || misaligned(counters, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_first_hits(*as, rays, num_rays, k, out, counters, status, static_cast<hipStream_t>(stream)));
+}
+
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
 
 int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
@@ -644,6 +655,9 @@ const char* rt_version_string(void)
            "(one lane per ray, unordered traversal, 64-entry stack of 4-byte entries, 16 in LDS) with the tracer's slab and "
            "Moller-Trumbore tests, CSR output by the 64-bit device scan, 16-byte hit records by plain stores into the ray's "
            "own segment | "
+           "rayfirst: first-K ray queries (k <= 32), the all-hit frame pruned against the k-th record's t, nearest-first box "
+           "steps, 64-entry stack of 4-byte entries (16 in LDS), knn's sorted per-lane list of 16-byte hit "
+           "records, one launch | "
            "trioverlap: triangle-overlap queries, every triangle a caller triangle cuts (vertex boxes + seventeen separating "
            "axes in three rolled loops, first separating axis leaves), optional self mode (j > i, no shared corner), the "
            "range query's frame and CSR output | "

@@ -287,6 +287,10 @@ hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_
 hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets,
                                    rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// ray_first_query.hip: rt_ray_first_hits after its argument checks (num_rays > 0, 1 <= k <= RT_RAY_FIRST_MAX_K)
+hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
+                                 uint64_t* counters, uint32_t* status, hipStream_t st);
+
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.
 size_t tri_overlaps_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned

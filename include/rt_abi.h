@@ -686,6 +686,78 @@ int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
 int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
                         uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- first-K ray queries (no reference counterpart).  For each caller ray: the K nearest triangles it crosses inside its
+ * [tmin, tmax] window, in order -- layered transparency, depth peeling, "skip the first surface" picking, thickness (entry /
+ * exit pairs), CSG -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and
+ * every row is misses).  The fixed-length sibling of the all-hit query, as rt_k_nearest is of the sphere range query: row i of
+ * the output has exactly k records, so nothing is counted, scanned, allocated or read back, and the window shrinks while the
+ * ray is traced: ONE launch.
+ *
+ * Rays, slab arithmetic, leaf test.  The all-hit block's, word for word: the liveness rule (a ray with tmin > tmax, or a NaN in
+ * origin, direction, tmin or tmax, is not traced), 1/dir by IEEE division, front / back from rt_trace's float32 slab test,
+ * rt_trace's Moller-Trumbore on the STORED corners, triangle B = (v2, v1, v3) tested iff v3 != v2 bit for bit, (u, v) mapped
+ * back to the caller's corners through rt_triangle_pair.rotations.  Let W be the all-hit row of the ray: the row
+ * rt_ray_hits_collect defines for the same tree and the ray's original window.
+ * Bound.  Each ray carries a bound b: its original tmax while its list holds fewer than k records, the t of the k-th record
+ *   once the list is full.
+ * Slot test.  A non-NONE slot is entered iff back >= front && front <= b && back >= tmin -- the all-hit rule with b in the
+ *   place of tmax, b being the bound at the moment the slot is examined.  A pending entry that is re-tested when it is popped
+ *   is dropped iff front > b with the bound of that moment.  Equality never prunes.
+ * Leaf test.  A triangle is accepted by the all-hit block's test against the window [tmin, b]: t > b rejects, t == b does not.
+ * List.  An accepted candidate (t, primitive_id, u, v) enters the list iff
+ *   - the list is not full, or (t, primitive_id) is lexicographically below the k-th entry, and
+ *   - no listed entry has the same (t, primitive_id).
+ *   The second clause keeps a record once on spatial-split trees, where a triangle has several references (rt_k_nearest's
+ *   rule).  A full list loses its k-th entry to a newcomer.  Floats compare as floats (-0 equals +0).  A NaN t -- products that
+ *   overflowed; Moller-Trumbore's comparisons let it through, and W holds such records too -- orders above every number, NaNs
+ *   are equal to each other, and while the k-th t is NaN the bound stays the original tmax: the bound is never NaN.
+ * Output row.  Row i is out[i*k .. i*k + k) (64-bit indexing), rt_hit records of 16 bytes.  It holds the list, ascending by
+ *   (t, primitive_id): ties on t go to the lower id.  Behind the list come rt_intersect_rays's miss records
+ *   {+inf, RT_MISS, 0, 0}.  A ray that is not traced, and every ray of an empty tree, gets k miss records and counts nothing.
+ *   Rows at i >= num_rays are not written.
+ * Order.  The surviving slot of a run with the smallest front is visited next (ties: the lower slot), the others wait.  The
+ *   order is an implementation matter that the claims below do not depend on; only the counters and the rows of undecided
+ *   rays (below) can see it.
+ *
+ * What is promised.  The slab test and the triangle test are separate float32 computations, so a box's front can round to a
+ * value beyond the t of a hit inside the box.  For the all-hit query, whose window is fixed, that is harmless; here a bound
+ * that has fallen to such a t prunes the box although it holds a nearer hit.  That is why "equals the brute force, sorted" cannot
+ * be promised for rays, and why the contract names the rounding: for a record w of W let its GATE g(w) be the largest slab
+ * front over the slots on the path from the root run to w's leaf slot, the leaf slot included (the smallest over its paths
+ * if a split tree reaches the record through several) -- a function of the tree's bytes and the ray.  Let Ws be W with
+ * duplicates by (t, id) removed, sorted by (t, id); E its first min(k, |Ws|) records; T1 the t of its (k+1)-th record, or the
+ * original tmax if there is none.  With status 0 (DESIGN section 19 has the proofs):
+ *   1. every live record of the row is a record of W, bit for bit in all 16 bytes; the row is strictly ascending in (t, id);
+ *      misses come only at the end;
+ *   2. DECIDED rays: if every w in E has g(w) <= T1, the row is E, bit for bit.  (Before w is offered the list holds only
+ *      records of W without w, so b >= T1: every slot above w passes whenever it is examined or popped, w is accepted, and the
+ *      list keeps the k smallest of what it is offered.)  In particular a ray with |Ws| <= k is decided: its row is all of Ws;
+ *   3. EVERY ray: with T the final bound (the last live t of a full row -- the original tmax if that t is NaN -- else the
+ *      original tmax), every w in W with g(w) <= T and (t, id) below the row's last live record is in the row.  So a full row
+ *      can miss a record only where the float32 slab test put a box's front BEYOND a hit inside that box;
+ *   4. counters[0] and counters[1] are at most rt_ray_hits_count's for the same rays (every slot entered here is entered
+ *      there).  They are equal when every ray has |Ws| < k: the bound never moves and the set of entered slots is the all-hit
+ *      one.  Otherwise they depend on the visiting order and on which pending entries are re-tested -- implementation
+ *      matters, not part of the contract.
+ * Further, without a promise beyond the above: on decided rays the row's first t is at most rt_intersect_rays's closest-hit t
+ * (all-hit claim 1: that record is in W); among coincident triangles the primitive_id at a tied t is the LOWER one here and
+ * whichever was met first there; on split trees the records of a row are distinct in (t, id) -- the references of one triangle
+ * that store its corners in one order give one t, and the row then holds that id once -- and everything above is stated on Ws.
+ *
+ * Stack: 64 pending entries per ray; a push beyond them is dropped and sets RT_RAY_FIRST_STACK_OVERFLOW: the row is then a
+ * sorted subset of W (claim 1 still holds).  There is no restart pass: a shrinking bound keeps fewer entries pending than the
+ * all-hit query, which has none either.
+ * counters: optional device uint64[4]: [0] += box tests (non-NONE slots examined), [1] += leaf records visited; [2] / [3] are
+ * not touched.  status: optional device uint32 the call ORs flags into (the caller clears it).  Asynchronous (no allocation, no
+ * scratch, no host copy, no synchronisation: hipGraph-capturable).  num_rays = 0: nothing runs.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / rays / out, k = 0 or
+ * k > RT_RAY_FIRST_MAX_K, count > 7, a tree with count > 0 and a null node or leaf pointer, rays or out not 16-byte aligned,
+ * status not 4-byte aligned, counters not 8-byte aligned. */
+#define RT_RAY_FIRST_MAX_K 32
+enum { RT_RAY_FIRST_STACK_OVERFLOW = 1 };
+int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
+                      uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
  * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
  * any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every set is empty).
