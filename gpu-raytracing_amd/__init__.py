@@ -15,7 +15,9 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 ``TriOverlapsCollect``, ``TriOverlaps``: every triangle a query triangle cuts, as CSR; ``self_pairs`` for the
 self-intersections of the mesh the tree was built over), signed distance and occupancy (``SignedDistance``, ``Occupancy``:
 how far the nearest triangle is and whether a point is inside a closed mesh, in one launch; ``GenerateGridPoints`` for the
-lattice such queries usually run on), and ray sorting (``SortRays``: a coherence
+lattice such queries usually run on), hit filters for the ray queries (``HitFilter`` with ``IntersectRaysFiltered``,
+``RayHitsCountFiltered``, ``RayHitsCollectFiltered``, ``RayFirstHitsFiltered``: face culling, a skip id per ray, primitive
+masks against ray masks, applied inside the traversal), and ray sorting (``SortRays``: a coherence
 order of a ray batch; ``IntersectRaysIndexed``: a query through that order or any list of ray indices).  torch is used for device
 memory and streams only.  There is NO CPU fallback: if the HIP library is missing, import of the
 native symbols fails loudly.
@@ -85,6 +87,9 @@ RT_KNN_STACK_OVERFLOW = 1
 RT_RAY_HITS_STACK_OVERFLOW, RT_RAY_HITS_TRUNCATED = 1, 2
 # first-K ray queries (rt_ray_first_hits): RAY records in, rows of k HIT records out
 RT_RAY_FIRST_MAX_K = 32
+# rt_ray_filter: a ray's own mask and the primitive_id it skips (MISS: none); RT_FILTER_*: HitFilter.flags
+RAY_FILTER = np.dtype([("mask", "<u4"), ("skip_id", "<u4")])                                                    # 8 B
+RT_FILTER_CULL_BACK, RT_FILTER_CULL_FRONT = 1, 2
 RT_RAY_FIRST_STACK_OVERFLOW = 1
 # triangle-overlap queries (rt_tri_overlaps_count / rt_tri_overlaps_collect): TRIANGLE records in, CSR rows of ids out
 kTriSelf = 1
@@ -160,6 +165,11 @@ class _RaySortLayout(ctypes.Structure):
                 ("total", ctypes.c_size_t)]
 
 
+class _HitFilter(ctypes.Structure):  # rt_hit_filter
+    _fields_ = [("flags", ctypes.c_uint32), ("ray_mask", ctypes.c_uint32), ("num_primitives", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("prim_masks", ctypes.c_void_p), ("per_ray", ctypes.c_void_p)]
+
+
 class _RefitPlanLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
                 ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
@@ -175,6 +185,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
            "rt_ray_first_hits",
+           "rt_intersect_rays_filtered", "rt_ray_hits_count_filtered", "rt_ray_hits_collect_filtered",
+           "rt_ray_first_hits_filtered",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
@@ -270,6 +282,15 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_collect.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, vp, vp, vp, vp]
     L.rt_ray_first_hits.restype = i32
     L.rt_ray_first_hits.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, vp, vp, vp, vp]
+    fl = ctypes.POINTER(_HitFilter)
+    L.rt_intersect_rays_filtered.restype = i32
+    L.rt_intersect_rays_filtered.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, i32, u32, fl, vp, vp]
+    L.rt_ray_hits_count_filtered.restype = i32
+    L.rt_ray_hits_count_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, fl, vp, vp, vp, vp, vp]
+    L.rt_ray_hits_collect_filtered.restype = i32
+    L.rt_ray_hits_collect_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, fl, vp, vp, vp, vp, vp, vp]
+    L.rt_ray_first_hits_filtered.restype = i32
+    L.rt_ray_first_hits_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, fl, vp, vp, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -843,6 +864,84 @@ def RayFirstHits(triangles, nodes, root: int, count: int, rays, k: int, out, *, 
 def ray_first_status(status) -> int:
     """The RT_RAY_FIRST_* flags RayFirstHits ORed into `status` (copies the word back: waits for the work queued before it)."""
     return _status_word(status)
+
+
+class HitFilter:
+    """rt_hit_filter: which of the triangles a ray crosses count (include/rt_abi.h, hit-filter block).  flags:
+    RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT (front: the side the counter-clockwise normal points to).  prim_masks: optional
+    contiguous device int32 / uint32 tensor [num_primitives], one mask per primitive_id (ids beyond it: all ones).  per_ray:
+    optional contiguous device buffer of 8-byte RAY_FILTER records (mask, skip_id), e.g. int32 [N, 2], one per ray of the batch
+    it is used with; without it every ray has `ray_mask` and skips nothing.  A candidate is kept iff it is not culled, its
+    primitive_id is not the ray's skip_id (MISS: none) and prim mask & ray mask != 0.  The object keeps its tensors alive."""
+
+    def __init__(self, flags: int = 0, ray_mask: int = 0xFFFFFFFF, prim_masks=None, per_ray=None):
+        for name, t, rec in (("prim_masks", prim_masks, 4), ("per_ray", per_ray, 8)):
+            if t is not None and (not t.is_contiguous() or _nbytes(t) % rec):
+                raise ValueError(f"{name} must be a contiguous device buffer of {rec}-byte records")
+        self.flags, self.ray_mask, self.prim_masks, self.per_ray = int(flags), int(ray_mask) & 0xFFFFFFFF, prim_masks, per_ray
+
+    def _struct(self, num_rays: int) -> _HitFilter:
+        if self.per_ray is not None and _nbytes(self.per_ray) < 8 * num_rays:
+            raise ValueError(f"per_ray must hold {num_rays} 8-byte records")
+        num_prims = 0 if self.prim_masks is None else _nbytes(self.prim_masks) // 4
+        return _HitFilter(self.flags, self.ray_mask, num_prims, 0, _ptr(self.prim_masks) or None, _ptr(self.per_ray) or None)
+
+
+def _filter_ref(filter, num_rays: int):
+    """the `filter` argument of a filtered entry point: NULL for None (the call forwards to the unfiltered entry point)"""
+    return None if filter is None else ctypes.byref(filter._struct(num_rays))
+
+
+def IntersectRaysFiltered(triangles, nodes, root: int, count: int, rays, hits, filter, *, any_hit: bool = False,
+                          num_primitives: int = 0, counters=None, stream=None) -> None:
+    """rt_intersect_rays_filtered: IntersectRays over the candidates `filter` (a HitFilter, or None for all) keeps.  The filter
+    acts inside the traversal: a rejected triangle neither shrinks the ray's window nor ends an any-hit ray."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_intersect_rays_filtered(ctypes.byref(a), _ptr(rays), _ptr(hits), n, kAnyHit if any_hit else kClosestHit,
+                                            int(num_primitives), _filter_ref(filter, n), _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_filtered")
+
+
+def RayHitsCountFiltered(triangles, nodes, root: int, count: int, rays, filter, offsets, *, scratch=None, counters=None,
+                         status=None, stream=None) -> int:
+    """rt_ray_hits_count_filtered: RayHitsCount over the candidates `filter` (a HitFilter, or None for all) keeps.  The counters
+    are the unfiltered call's: the filter acts after the leaf test."""
+    n = _ray_batch(rays)
+    return _csr_count(lib().rt_ray_hits_count_filtered, RayHitsScratchBytes, (triangles, nodes, root, count), rays, n,
+                      (_filter_ref(filter, n),), offsets, scratch=scratch, counters=counters, status=status, stream=stream)
+
+
+def RayHitsCollectFiltered(triangles, nodes, root: int, count: int, rays, filter, offsets, hits, *, counts=None, counters=None,
+                           status=None, stream=None) -> int:
+    """rt_ray_hits_collect_filtered: RayHitsCollect over the candidates `filter` keeps (the same filter as the count call)."""
+    n = _ray_batch(rays)
+    return _csr_collect(lib().rt_ray_hits_collect_filtered, (triangles, nodes, root, count), rays, n, (_filter_ref(filter, n),),
+                        offsets, hits, "hits", counts=counts, counters=counters, status=status, stream=stream)
+
+
+def RayFirstHitsFiltered(triangles, nodes, root: int, count: int, rays, k: int, filter, out, *, counters=None, status=None,
+                         stream=None) -> int:
+    """rt_ray_first_hits_filtered: RayFirstHits over the candidates `filter` (a HitFilter, or None for all) keeps: the k nearest
+    KEPT crossings, in order; the bound only falls to the t of a kept record."""
+    k = int(k)
+    if not 1 <= k <= RT_RAY_FIRST_MAX_K:
+        raise ValueError(f"k must be in 1 .. {RT_RAY_FIRST_MAX_K}")
+    n = _ray_batch(rays)
+    if not out.is_contiguous() or out.dtype != _torch().float32 or tuple(out.shape) != (n, k, 4):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape [{n}, {k}, 4]")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_ray_first_hits_filtered(ctypes.byref(a), _ptr(rays), n, k, _filter_ref(filter, n), _ptr(out), _ptr(counters),
+                                            _ptr(status), _stream_ptr(stream)), "rt_ray_first_hits_filtered")
+    return n
 
 
 def TriOverlapsScratchBytes(num_queries: int) -> int:

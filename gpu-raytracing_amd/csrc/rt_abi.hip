@@ -502,6 +502,62 @@ int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
     return hip_rc(launch_ray_first_hits(*as, rays, num_rays, k, out, counters, status, static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_ray_filter) == 8 && sizeof(rt_hit_filter) == 32, "rt_abi.h: the filter records' sizes");
+
+// the filter's own checks (the sibling's come first, from the sibling's own code path or its restatement below)
+static inline bool filter_args(const rt_hit_filter* f)
+{
+    return !(f->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) && !misaligned(f->prim_masks, 4) &&
+           !misaligned(f->per_ray, 8);
+}
+
+int rt_intersect_rays_filtered(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
+                               uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, void* stream)
+{
+    if (!filter) return rt_intersect_rays(as, rays, hits, num_rays, mode, num_primitives, counters, stream);
+    if (!tree_args(as) || !rays || !hits || !filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_query_filtered(*as, rays, hits, num_rays, mode == RT_RAY_ANY_HIT, num_primitives, *filter, counters,
+                                            static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_count_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                               uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!filter) return rt_ray_hits_count(as, rays, num_rays, offsets, scratch, counters, status, stream);
+    if (!csr_args(as, rays, 16, filter_args(filter), offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
+    // (num_rays = 0 still launches the scan's one workgroup: offsets[0] = 0)
+    return hip_rc(launch_ray_hits_count_filtered(*as, rays, num_rays, *filter, offsets, scratch, counters, status,
+                                                 static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_collect_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                                 const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status,
+                                 void* stream)
+{
+    if (!filter) return rt_ray_hits_collect(as, rays, num_rays, offsets, hits, counts, counters, status, stream);
+    if (!csr_args(as, rays, 16, filter_args(filter), offsets, status) || !csr_collect_args(hits, 16, counts))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_hits_collect_filtered(*as, rays, num_rays, *filter, offsets, hits, counts, counters, status,
+                                                   static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
+                               const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, void* stream)
+{
+    if (!filter) return rt_ray_first_hits(as, rays, num_rays, k, out, counters, status, stream);
+    if (!tree_args(as) || !rays || !out || !filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
+    if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(out, 16) || misaligned(status, 4) || misaligned(counters, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_first_hits_filtered(*as, rays, num_rays, k, *filter, out, counters, status,
+                                                 static_cast<hipStream_t>(stream)));
+}
+
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
 
 int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
@@ -658,6 +714,9 @@ const char* rt_version_string(void)
            "rayfirst: first-K ray queries (k <= 32), the all-hit frame pruned against the k-th record's t, nearest-first box "
            "steps, 64-entry stack of 4-byte entries (16 in LDS), knn's sorted per-lane list of 16-byte hit "
            "records, one launch | "
+           "rayfilter: hit filters for the closest / any, all-hit and first-K ray queries (face culling by the sign of the "
+           "stored-corner determinant, a skip id and a mask per ray, a mask per primitive), asked inside the leaf test after the "
+           "t window test: the siblings' traversals, one 8-byte load per ray and one 4-byte load per surviving candidate | "
            "trioverlap: triangle-overlap queries, every triangle a caller triangle cuts (vertex boxes + seventeen separating "
            "axes in three rolled loops, first separating axis leaves), optional self mode (j > i, no shared corner), the "
            "range query's frame and CSR output | "

@@ -291,6 +291,19 @@ hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint3
 hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
                                  uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// ray_filter_query.hip: the filtered siblings of the four ray queries after their argument checks (the siblings' own, plus the
+// filter's flags and alignments); `filter` is never null here
+hipError_t launch_ray_query_filtered(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
+                                     uint32_t num_primitives, const rt_hit_filter& filter, uint64_t* counters, hipStream_t st);
+hipError_t launch_ray_hits_count_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter& filter,
+                                          uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_ray_hits_collect_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter& filter,
+                                            const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters,
+                                            uint32_t* status, hipStream_t st);
+hipError_t launch_ray_first_hits_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
+                                          const rt_hit_filter& filter, rt_hit* out, uint64_t* counters, uint32_t* status,
+                                          hipStream_t st);
+
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.
 size_t tri_overlaps_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned

@@ -84,10 +84,20 @@ struct Hit {
     float bu, bv;
 };
 
+// The hit-filter policy of intersect_tri / trace_ray.  NoFilter: every triangle Moller-Trumbore accepts is accepted (all
+// existing kernels; `if constexpr` leaves no trace of the policy in them).  A policy with active = true (rt_ray_filter.hpp)
+// supplies keep(a, primitive_id), asked after the t window test and before r.tmax is written: a candidate it turns down is a
+// candidate the leaf test rejected.  The object travels by value: handed down by reference, even the empty NoFilter changed the
+// code of existing kernels.
+struct NoFilter {
+    static constexpr bool active = false;
+};
+
 // Tracer.cu:256-291
+template <class Filter = NoFilter>
 __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, float v1x, float v1y, float v1z,
                                               float v2x, float v2y, float v2z, Ray& r, Hit& h, uint32_t tri_id,
-                                              uint32_t prim_id)
+                                              uint32_t prim_id, Filter flt = Filter())
 {
     const float epsilon = 0.000000001f;
     const float e1x = v1x - v0x, e1y = v1y - v0y, e1z = v1z - v0z;
@@ -104,6 +114,9 @@ __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, f
     if (v < 0.0f || (u + v) > 1.0f) return false;
     const float t = f * (e2x * qx + e2y * qy + e2z * qz);
     if (t < r.tmin || t > r.tmax) return false;
+    if constexpr (Filter::active) {
+        if (!flt.keep(a, prim_id)) return false;
+    }
     r.tmax = t;
     h.primitive_id = prim_id;
     h.tri_id = tri_id;
@@ -309,8 +322,10 @@ __device__ __forceinline__ bool box_step_wave(const Params& p, const Ray& r, Tra
 // steps[0] / steps[1] count the wave's box-phase / leaf-phase iterations (profiling aid).
 // ANY (any-hit): a lane whose leaf test hits is done (PH_DONE) -- until that first hit its sequence of tests is the
 // closest-hit one, step for step.  Params: anything with nodes, leaves, root, count, park_num, park_den.
-template <bool PF, bool ANY = false, class Params>
-__device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav& t, bool active, uint32_t* steps)
+// Filter: the hit-filter policy handed to every leaf test (NoFilter: none).
+template <bool PF, bool ANY = false, class Params, class Filter = NoFilter>
+__device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav& t, bool active, uint32_t* steps,
+                                          Filter flt = Filter())
 {
     t.sp = 0;
     t.cur = (p.root & kIndexMask) | (p.count << 29);
@@ -382,14 +397,14 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
             bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
                                          __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
                                          __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                         r, h, li << 1, l0.w);
+                                         r, h, li << 1, l0.w, flt);
             // triangle B = (v2, v1, v3) is requested whenever count > 0; for a single triangle v3 == v2
             // bit for bit, B's edge2 is exactly 0, a == 0 and the reference rejects it: skipped, same result.
             if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
                 hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
                                          __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
                                          __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                         r, h, (li << 1) + 1, l1.w);
+                                         r, h, (li << 1) + 1, l1.w, flt);
             tri_hit |= hit_tri;
             if (ANY && hit_tri) {
                 t.phase = PH_DONE;

@@ -758,6 +758,84 @@ enum { RT_RAY_FIRST_STACK_OVERFLOW = 1 };
 int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
                       uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- hit filters for the ray queries (no reference counterpart).  The four ray queries above accept every triangle that
+ * Moller-Trumbore accepts.  Their filtered siblings take one more argument, an rt_hit_filter, that says which of those
+ * candidates count: "front faces only" (face culling), "not the triangle I am standing on" (a per-ray skip id), "only the
+ * triangles of these groups" (a mask per primitive against a mask per ray) -- the ray flags, masks and filters of the other
+ * ray APIs.  The filter sits at the one place where a candidate is accepted, inside the traversal: a closest-hit ray that meets
+ * a filtered-out triangle first does not shrink its window on it and does not prune what lies behind it, which no pass over
+ * the unfiltered result can undo.  Every argument other than `filter` keeps the type and meaning it has in the unfiltered
+ * sibling (rt_intersect_rays, rt_ray_hits_count, rt_ray_hits_collect, rt_ray_first_hits); box tests, leaf visits, the liveness
+ * rule, the stack and the status flags are the sibling's.
+ *
+ * rt_hit_filter is a HOST struct holding device pointers, like rt_accel; it is read during the call and need not outlive it.
+ *   flags: RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT; both together are legal.
+ *   ray_mask: the mask of every ray when per_ray is null.
+ *   prim_masks: optional DEVICE uint32[num_primitives], indexed by primitive_id.  A null prim_masks is an absent array whatever
+ *     num_primitives says.
+ *   per_ray: optional DEVICE rt_ray_filter[num_rays], indexed by the ray's index i (the index of rays[i] and of its result):
+ *     the ray's own mask and the primitive_id it skips, RT_MISS for none.  One 8-byte load per ray.
+ *   pad: 0 (not read).
+ * Acceptance rule.  A candidate is a triangle A = (v0, v1, v2) or B = (v2, v1, v3) of a leaf record that the sibling's leaf
+ * test accepts (its Moller-Trumbore on the STORED corners, against the window the sibling tests it against), with the
+ * determinant a = e1 . (dir x e2), e1 = c1 - c0, e2 = c2 - c0, exactly as that test computes it in float32 on the stored
+ * corners (c0, c1, c2), and the record's primitive_id.  It is KEPT iff all four hold:
+ *   1. not (RT_FILTER_CULL_BACK and a < 0);
+ *   2. not (RT_FILTER_CULL_FRONT and a > 0).  a = -dir . n with n = (c1 - c0) x (c2 - c0), the counter-clockwise normal: a > 0
+ *      means the ray meets the side that normal points to, the FRONT.  A NaN a (overflowed products) is neither front nor
+ *      back and is never culled; with both bits set only such records survive;
+ *   3. primitive_id != the ray's skip_id.  skip_id = RT_MISS skips nothing; with a null per_ray nothing is skipped;
+ *   4. (pm & rm) != 0, rm the ray's mask (ray_mask when per_ray is null), pm = prim_masks[primitive_id] when prim_masks is
+ *      non-null and primitive_id < num_primitives, else pm = 0xFFFFFFFF and nothing is read.
+ *   The tests run in this order, so prim_masks is read only for a candidate that passed 1-3.
+ *   A candidate that is not kept is treated exactly as if the leaf test had rejected it: no record, no window or bound update,
+ *   no list entry, and an any-hit ray does not end on it.
+ * Facing and the caller's winding.  A leaf record stores cyclic rotations of the caller's corners (rt_triangle_pair.rotations),
+ *   and a pair forms only across an edge its two triangles traverse in opposite directions (the pairing asks for A's edge
+ *   reversed in B), so the stored A = (v0, v1, v2) and B = (v2, v1, v3) both keep the caller's winding: front and back are the
+ *   caller's, on every tree.  Near a = 0 the sign of the stored-corner determinant decides, not a recomputation on the caller's
+ *   corner order (a rotation changes the rounding, not the winding).
+ *
+ * Contracts.  Let W be the all-hit row of the ray (all-hit block) and W_f the kept records of W.
+ *   rt_ray_hits_count_filtered / rt_ray_hits_collect_filtered: the all-hit block with W_f in the place of the row: the row is
+ *     W_f as a set; its claims hold with the filtered closest hit in the place of the closest hit.  The window is fixed and the
+ *     filter acts after the leaf test, so counters [0] and [1] equal the unfiltered call's exactly.
+ *   rt_ray_first_hits_filtered: the first-K block with W_f for W throughout: Ws, E, T1, gates, decided rays and claims 1-4,
+ *     claim 4 against rt_ray_hits_count_filtered's row lengths (|Ws| < k on every ray: the counters equal the all-hit
+ *     counters).  The bound only ever falls to the t of a kept record.
+ *   rt_intersect_rays_filtered: rt_intersect_rays's traversal with the rule above.  With no dropped push: the record is a record
+ *     of W_f, bit for bit in (t, u, v); a miss iff W_f is empty; any-hit hits iff closest-hit hits; on a ray that is decided
+ *     for k = 1 on W_f the record's t is E's t, bit for bit (before E is offered the window's end is the t of another kept
+ *     record, so it is at least T1 and at least g(E), and slot tests pass on equality).
+ *   filter == NULL forwards to the unfiltered entry point.  A filter that keeps everything -- flags 0 with null arrays, or with
+ *     arrays of all-ones masks and skip_id = RT_MISS -- gives the unfiltered call's bytes and counters.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of the sibling's; a flag bit other than
+ * RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT; prim_masks not 4-byte aligned; per_ray not 8-byte aligned.  num_primitives > 0
+ * with a null prim_masks is fine.  Asynchronous and hipGraph-capturable like the siblings.
+ * Out of scope: the instanced and indexed ray queries, rt_trace, and the point, range and overlap queries take no filter. */
+enum { RT_FILTER_CULL_BACK = 1, RT_FILTER_CULL_FRONT = 2 };
+typedef struct rt_ray_filter {
+    uint32_t mask;                        /* rm of rule 4 */
+    uint32_t skip_id;                     /* rule 3; RT_MISS: nothing */
+} rt_ray_filter;                          /* 8 bytes, per ray */
+typedef struct rt_hit_filter {
+    uint32_t flags;                       /* RT_FILTER_*; any other bit: RT_ERR_INVALID_ARGUMENT */
+    uint32_t ray_mask;                    /* the mask of every ray when per_ray is null */
+    uint32_t num_primitives;              /* length of prim_masks */
+    uint32_t pad;                         /* 0 */
+    const uint32_t* prim_masks;           /* optional DEVICE uint32[num_primitives], indexed by primitive_id */
+    const rt_ray_filter* per_ray;         /* optional DEVICE array [num_rays], indexed by the ray's index */
+} rt_hit_filter;                          /* 32 bytes */
+int rt_intersect_rays_filtered(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
+                               uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, void* stream);
+int rt_ray_hits_count_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                               uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream);
+int rt_ray_hits_collect_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                                 const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status,
+                                 void* stream);
+int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
+                               const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
  * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
  * any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and every set is empty).
