@@ -90,6 +90,12 @@ RT_RAY_FIRST_MAX_K = 32
 # rt_ray_filter: a ray's own mask and the primitive_id it skips (MISS: none); RT_FILTER_*: HitFilter.flags
 RAY_FILTER = np.dtype([("mask", "<u4"), ("skip_id", "<u4")])                                                    # 8 B
 RT_FILTER_CULL_BACK, RT_FILTER_CULL_FRONT = 1, 2
+# rt_instance_filter / rt_instance_ray_filter (rt_intersect_rays_instanced_filtered): an instance's mask and
+# RT_INSTANCE_FILTER_* flags; a ray's own mask and the (instance, primitive_id) pair it skips (skip_instance MISS: none)
+INSTANCE_FILTER = np.dtype([("mask", "<u4"), ("flags", "<u4")])                                                 # 8 B
+INSTANCE_RAY_FILTER = np.dtype([("mask", "<u4"), ("skip_instance", "<u4"), ("skip_id", "<u4"), ("pad", "<u4")])  # 16 B
+assert INSTANCE_FILTER.itemsize == 8 and INSTANCE_RAY_FILTER.itemsize == 16
+RT_INSTANCE_FILTER_CULL_DISABLE, RT_INSTANCE_FILTER_FLIP_FACING = 1, 2
 RT_RAY_FIRST_STACK_OVERFLOW = 1
 # triangle-overlap queries (rt_tri_overlaps_count / rt_tri_overlaps_collect): TRIANGLE records in, CSR rows of ids out
 kTriSelf = 1
@@ -170,6 +176,11 @@ class _HitFilter(ctypes.Structure):  # rt_hit_filter
                 ("pad", ctypes.c_uint32), ("prim_masks", ctypes.c_void_p), ("per_ray", ctypes.c_void_p)]
 
 
+class _InstanceHitFilter(ctypes.Structure):  # rt_instance_hit_filter
+    _fields_ = [("flags", ctypes.c_uint32), ("ray_mask", ctypes.c_uint32), ("num_instance_filters", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("per_instance", ctypes.c_void_p), ("per_ray", ctypes.c_void_p)]
+
+
 class _RefitPlanLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
                 ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
@@ -186,7 +197,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
            "rt_ray_first_hits",
            "rt_intersect_rays_filtered", "rt_ray_hits_count_filtered", "rt_ray_hits_collect_filtered",
-           "rt_ray_first_hits_filtered",
+           "rt_ray_first_hits_filtered", "rt_intersect_rays_instanced_filtered",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
@@ -291,6 +302,9 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_collect_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, fl, vp, vp, vp, vp, vp, vp]
     L.rt_ray_first_hits_filtered.restype = i32
     L.rt_ray_first_hits_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, u32, fl, vp, vp, vp, vp]
+    L.rt_intersect_rays_instanced_filtered.restype = i32
+    L.rt_intersect_rays_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32,
+                                                       ctypes.POINTER(_InstanceHitFilter), vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -942,6 +956,54 @@ def RayFirstHitsFiltered(triangles, nodes, root: int, count: int, rays, k: int, 
     _check(lib().rt_ray_first_hits_filtered(ctypes.byref(a), _ptr(rays), n, k, _filter_ref(filter, n), _ptr(out), _ptr(counters),
                                             _ptr(status), _stream_ptr(stream)), "rt_ray_first_hits_filtered")
     return n
+
+
+class InstanceHitFilter:
+    """rt_instance_hit_filter: the filter of the instanced ray query (include/rt_abi.h, instance-filter block).  flags:
+    RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT, decided on the WORLD-space facing (a mirrored instance swaps them).
+    per_instance: optional contiguous device buffer of 8-byte INSTANCE_FILTER records (mask, flags), e.g. int32 [K, 2], indexed
+    by the instance index; instances beyond it have an all-ones mask and no flags.  per_ray: optional contiguous device buffer
+    of 16-byte INSTANCE_RAY_FILTER records (mask, skip_instance, skip_id, pad), e.g. int32 [N, 4], one per ray of the batch it
+    is used with; without it every ray has `ray_mask` and skips nothing.  An instance is entered only if its mask & the ray's
+    mask != 0; a candidate is kept iff it is not culled and is not primitive skip_id of instance skip_instance.  The object
+    keeps its tensors alive."""
+
+    def __init__(self, flags: int = 0, ray_mask: int = 0xFFFFFFFF, per_instance=None, per_ray=None):
+        for name, t, rec in (("per_instance", per_instance, 8), ("per_ray", per_ray, 16)):
+            if t is not None and (not t.is_contiguous() or _nbytes(t) % rec):
+                raise ValueError(f"{name} must be a contiguous device buffer of {rec}-byte records")
+        self.flags, self.ray_mask = int(flags), int(ray_mask) & 0xFFFFFFFF
+        self.per_instance, self.per_ray = per_instance, per_ray
+
+    def _struct(self, num_rays: int) -> _InstanceHitFilter:
+        if self.per_ray is not None and _nbytes(self.per_ray) < 16 * num_rays:
+            raise ValueError(f"per_ray must hold {num_rays} 16-byte records")
+        num = 0 if self.per_instance is None else _nbytes(self.per_instance) // 8
+        return _InstanceHitFilter(self.flags, self.ray_mask, num, 0, _ptr(self.per_instance) or None, _ptr(self.per_ray) or None)
+
+
+def IntersectRaysInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                   num_blas: int, rays, hits, instance_ids, filter, *, any_hit: bool = False,
+                                   num_primitives: int = 0, counters=None, stream=None) -> None:
+    """rt_intersect_rays_instanced_filtered: IntersectRaysInstanced over the instances and candidates `filter` (an
+    InstanceHitFilter, or None for all) keeps.  A masked-out instance is never entered (no BLAS descent); a rejected triangle
+    neither shrinks the ray's window nor ends an any-hit ray."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits / instance_ids contiguous buffers")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records and instance_ids {n} words")
+    if filter is not None and not isinstance(filter, InstanceHitFilter):
+        raise ValueError("filter must be an InstanceHitFilter or None")
+    flt = _filter_ref(filter, n)
+    if n == 0:
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced_filtered(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                      int(num_blas), _ptr(rays), _ptr(hits), _ptr(instance_ids), n,
+                                                      kAnyHit if any_hit else kClosestHit, int(num_primitives), flt,
+                                                      _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_filtered")
 
 
 def TriOverlapsScratchBytes(num_queries: int) -> int:

@@ -523,6 +523,44 @@ int rt_intersect_rays_filtered(const rt_accel* as, const rt_ray* rays, rt_hit* h
                                             static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_instance_filter) == 8 && sizeof(rt_instance_ray_filter) == 16 && sizeof(rt_instance_hit_filter) == 32,
+              "rt_abi.h: the instance filter records' sizes");
+
+int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream)
+{
+    if (!filter)
+        return rt_intersect_rays_instanced(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays,
+                                           mode, num_primitives, counters, stream);
+    // the sibling's checks, restated, then the filter's own
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
+        misaligned(blas_table, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if ((filter->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) || misaligned(filter->per_instance, 8) ||
+        misaligned(filter->per_ray, 16))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    InstanceQuery q;
+    q.tlas = *tlas;
+    q.records = records;
+    q.num_instances = num_instances;
+    q.blas_table = blas_table;
+    q.num_blas = num_blas;
+    q.rays = rays;
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    q.num_rays = num_rays;
+    q.any_hit = mode == RT_RAY_ANY_HIT;
+    q.num_primitives = num_primitives;
+    q.counters = counters;
+    return hip_rc(launch_instance_query_filtered(q, *filter, static_cast<hipStream_t>(stream)));
+}
+
 int rt_ray_hits_count_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
                                uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
 {
@@ -717,6 +755,10 @@ const char* rt_version_string(void)
            "rayfilter: hit filters for the closest / any, all-hit and first-K ray queries (face culling by the sign of the "
            "stored-corner determinant, a skip id and a mask per ray, a mask per primitive), asked inside the leaf test after the "
            "t window test: the siblings' traversals, one 8-byte load per ray and one 4-byte load per surviving candidate | "
+           "instancefilter: the instanced ray query with an instance mask asked at the TLAS leaf before the record is read (one "
+           "8-byte load, a masked instance costs no BLAS descent), world-space face culling (the sign of the record's 3x3 "
+           "determinant swaps the cull bits, per-instance disable / flip) and a per-ray (instance, primitive) skip: the sibling's "
+           "two-level loop, one 16-byte load per ray | "
            "trioverlap: triangle-overlap queries, every triangle a caller triangle cuts (vertex boxes + seventeen separating "
            "axes in three rolled loops, first separating axis leaves), optional self mode (j > i, no shared corner), the "
            "range query's frame and CSR output | "

@@ -304,6 +304,10 @@ hipError_t launch_ray_first_hits_filtered(const rt_accel& as, const rt_ray* rays
                                           const rt_hit_filter& filter, rt_hit* out, uint64_t* counters, uint32_t* status,
                                           hipStream_t st);
 
+// instance_filter_query.hip: rt_intersect_rays_instanced_filtered after its argument checks (the sibling's own, plus the
+// filter's flags and alignments; num_rays > 0); `filter` is never null here
+hipError_t launch_instance_query_filtered(const InstanceQuery& q, const rt_instance_hit_filter& filter, hipStream_t st);
+
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.
 size_t tri_overlaps_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned

@@ -812,7 +812,9 @@ int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
  * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of the sibling's; a flag bit other than
  * RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT; prim_masks not 4-byte aligned; per_ray not 8-byte aligned.  num_primitives > 0
  * with a null prim_masks is fine.  Asynchronous and hipGraph-capturable like the siblings.
- * Out of scope: the instanced and indexed ray queries, rt_trace, and the point, range and overlap queries take no filter. */
+ * Out of scope: rt_hit_filter is the filter of the four single-tree ray queries only.  The instanced ray query has a filter of
+ * its own (rt_intersect_rays_instanced_filtered, the instance-filter block below); the indexed ray query, rt_trace, and the
+ * point, range and overlap queries take no filter. */
 enum { RT_FILTER_CULL_BACK = 1, RT_FILTER_CULL_FRONT = 2 };
 typedef struct rt_ray_filter {
     uint32_t mask;                        /* rm of rule 4 */
@@ -835,6 +837,96 @@ int rt_ray_hits_collect_filtered(const rt_accel* as, const rt_ray* rays, uint32_
                                  void* stream);
 int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
                                const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, void* stream);
+
+/* ---- hit filters and instance masks for the instanced ray query (no reference counterpart).  rt_hit_filter cannot serve a scene
+ * of placed copies: its skip_id is a bare primitive_id, and the same id exists in every copy of a BLAS; its facing is decided on
+ * the stored object-space corners, so a mirrored instance shows the caller the wrong side; and its masks are per triangle, so a
+ * masked instance would still be entered, its BLAS walked and its candidates rejected one by one.  This block is the filter of
+ * the two-level query: an instance visibility mask asked at the TLAS leaf (DXR's InstanceMask, OptiX's visibility mask: shadow
+ * casters only, no self-shadowing of one model, a per-layer ray) -- the one filter that makes a ray cheaper, because the whole
+ * BLAS descent is saved --, face culling by the WORLD-space facing, and a per-ray (instance, primitive) pair to skip.
+ *
+ * rt_intersect_rays_instanced_filtered: every argument other than `filter` keeps the type and meaning it has in
+ * rt_intersect_rays_instanced, and all of that call's rules carry over unchanged: rays, records, modes, the NaN and empty-window
+ * rule, the ONE 64-entry stack of both levels, the rule for when an instance is never entered, the world ray reloaded on exit,
+ * the counters.  rt_instance_hit_filter is a HOST struct holding device pointers, like rt_hit_filter; it is read during the call
+ * and need not outlive it.
+ *   flags: RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT (the hit-filter block's bits); both together are legal.
+ *   ray_mask: the mask of every ray when per_ray is null.
+ *   per_instance: optional DEVICE rt_instance_filter[num_instance_filters], indexed by the instance index (a TLAS leaf's
+ *     primitive_id_0, the value reported in instance_ids): the instance's mask and its RT_INSTANCE_FILTER_* flags.  A null
+ *     per_instance is an absent array whatever num_instance_filters says; the array may be shorter than num_instances.
+ *   per_ray: optional DEVICE rt_instance_ray_filter[num_rays], indexed by the ray's index i: the ray's own mask and the
+ *     (skip_instance, skip_id) pair it skips.  One 16-byte load per ray.
+ *   pad: 0 (not read); rt_instance_ray_filter.pad: not read.
+ * The call adds two rules.
+ * 1. Instance rule, asked at the TLAS leaf when the traversal is about to enter instance `id` (id < num_instances), BEFORE the
+ *    instance record is read:
+ *      rm = per_ray[i].mask, or ray_mask when per_ray is null;
+ *      im = per_instance[id].mask when per_instance is non-null and id < num_instance_filters (one 8-byte load that also
+ *           brings the instance's flags), else im = 0xFFFFFFFF and nothing is read;
+ *      the instance is entered only if (im & rm) != 0 -- and, as before, only if its record's flags are zero, its blas <
+ *      num_blas and the table entry's count is 1 .. 7.
+ *    An instance that is not entered is treated exactly like a flagged one: the lane advances in the TLAS; the instance
+ *    contributes no box test, no leaf visit and no candidate, and neither its record nor its rt_accel is read.
+ * 2. Candidate rule, asked at the leaf test's acceptance point inside the entered instance `id`.  A candidate is a triangle
+ *    A = (v0, v1, v2) or B = (v2, v1, v3) of a BLAS leaf record that rt_intersect_rays_instanced's leaf test accepts
+ *    (Moller-Trumbore on the STORED corners with the object-space ray, against the current [tmin, tmax]), with the determinant
+ *    a = e1 . (dir' x e2) exactly as that test computes it in float32 (the hit-filter block's `a`, in object space), and the
+ *    record's primitive_id.  With W = the record's float32 world_to_object, rows w0, w1, w2:
+ *      det  = (w0.x*(w1.y*w2.z - w1.z*w2.y) - w0.y*(w1.x*w2.z - w1.z*w2.x)) + w0.z*(w1.x*w2.y - w1.y*w2.x), every product,
+ *             difference and sum rounded to float32 in the order written (no fused multiply-add); it is computed only when
+ *             a cull bit is set;
+ *      flip = (det < 0) XOR (per_instance[id].flags & RT_INSTANCE_FILTER_FLIP_FACING); a NaN det counts as not mirrored.  A
+ *             mirroring object_to_world (negative determinant, and so a negative det) reverses the winding the world sees;
+ *      world-facing = a when flip is false, -a when it is true (the sign of a is unchanged by a non-mirroring affine map:
+ *             a = -dir . n scales by the determinant);
+ *    the candidate is KEPT iff all three hold:
+ *      a. not (RT_FILTER_CULL_BACK and world-facing < 0), unless the instance has RT_INSTANCE_FILTER_CULL_DISABLE;
+ *      b. not (RT_FILTER_CULL_FRONT and world-facing > 0), unless the instance has RT_INSTANCE_FILTER_CULL_DISABLE;
+ *      c. not (id == skip_instance and primitive_id == skip_id and skip_id != RT_MISS).  RT_MISS in either word is "none":
+ *         skip_instance = RT_MISS matches no instance (id < num_instances), and skip_id = RT_MISS skips nothing whatever
+ *         skip_instance is (no leaf record carries that primitive_id in a tree the builders make; the rule does not depend
+ *         on it).  A null per_ray skips nothing.
+ *    A NaN a is neither front nor back and is never culled.  Equivalently the kernel applies, to `a` itself, the call's cull
+ *    bits with BACK and FRONT exchanged when flip is true and cleared under CULL_DISABLE, and skip_id only inside skip_instance.
+ *    A rejected candidate is treated exactly as if the leaf test had rejected it: no window update, and an any-hit ray goes on.
+ *    An instance without a per_instance record has flags 0.  An unknown bit in a device-side per_instance[].flags is ignored.
+ * Contracts.
+ *   filter == NULL forwards to rt_intersect_rays_instanced.
+ *   A filter that keeps everything -- null arrays with ray_mask all ones and flags 0, or arrays of all-ones masks with zero flags
+ *     and skip_instance = RT_MISS -- gives the unfiltered call's hits, instance_ids and all four counters, byte for byte.
+ *   Any-hit hits iff closest-hit hits (no dropped push): both run one sequence of tests until the first kept candidate.
+ *   One identity instance with no per_instance: the call equals rt_intersect_rays_filtered on the BLAS with the same flags,
+ *     null prim_masks and per-ray records {mask, skip_id} for rays whose skip_instance is 0, on rays without -0 components.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of rt_intersect_rays_instanced's; a flag bit
+ * other than RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT in filter->flags; per_instance not 8-byte aligned; per_ray not 16-byte
+ * aligned.  num_instance_filters > 0 with a null per_instance is fine.  Asynchronous and hipGraph-capturable like the sibling.
+ * Out of scope: there is no per-primitive mask in this call -- grouping is per instance --, and the indexed, all-hit and first-K
+ * queries have no instanced form, filtered or not. */
+enum { RT_INSTANCE_FILTER_CULL_DISABLE = 1, RT_INSTANCE_FILTER_FLIP_FACING = 2 };
+typedef struct rt_instance_filter {
+    uint32_t mask;                        /* im of rule 1 */
+    uint32_t flags;                       /* RT_INSTANCE_FILTER_*; other bits are ignored */
+} rt_instance_filter;                     /* 8 bytes, per instance */
+typedef struct rt_instance_ray_filter {
+    uint32_t mask;                        /* rm of rule 1 */
+    uint32_t skip_instance;               /* rule 2c; RT_MISS: nothing */
+    uint32_t skip_id;                     /* rule 2c: the primitive_id skipped inside skip_instance */
+    uint32_t pad;                         /* not read */
+} rt_instance_ray_filter;                 /* 16 bytes, per ray */
+typedef struct rt_instance_hit_filter {
+    uint32_t flags;                       /* RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT; any other bit: RT_ERR_INVALID_ARGUMENT */
+    uint32_t ray_mask;                    /* the mask of every ray when per_ray is null */
+    uint32_t num_instance_filters;        /* length of per_instance */
+    uint32_t pad;                         /* 0, not read */
+    const rt_instance_filter* per_instance;   /* optional DEVICE array, indexed by the instance index */
+    const rt_instance_ray_filter* per_ray;    /* optional DEVICE array [num_rays], indexed by the ray's index */
+} rt_instance_hit_filter;                 /* 32 bytes */
+int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream);
 
 /* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
  * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
