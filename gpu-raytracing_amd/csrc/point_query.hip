@@ -68,6 +68,9 @@ struct Tri {
     float ax, ay, az, bx, by, bz, cx, cy, cz;
 };
 
+// rt_abi.h's FACE_NOISE: a face sum at or below this share of the magnitudes of its six products is rounding noise
+constexpr float kFaceNoise = 0x1p-20f;
+
 // dist2 of p to q after q is clamped into the triangle's vertex box (fmaxf, then fminf)
 __device__ __forceinline__ float pt_clamped(float px, float py, float pz, float qx, float qy, float qz, const Tri& t)
 {
@@ -100,7 +103,7 @@ __device__ __forceinline__ float point_tri_d2(float px, float py, float pz, cons
     }
     const float vc = d1 * d4 - d3 * d2;
     const float t_ab = pt_clamp01(pt_guard(d1, d1 - d3));
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {                      // edge region AB
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f && d1 - d3 > 0.0f) {    // edge region AB (of an edge that has a length)
         u = t_ab; v = 0.0f;
         return pt_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
     }
@@ -112,7 +115,7 @@ __device__ __forceinline__ float point_tri_d2(float px, float py, float pz, cons
     }
     const float vb = d5 * d2 - d1 * d6;
     const float t_ac = pt_clamp01(pt_guard(d2, d2 - d6));
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {                      // edge region AC
+    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f && d2 - d6 > 0.0f) {    // edge region AC
         u = 0.0f; v = t_ac;
         return pt_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
     }
@@ -120,26 +123,34 @@ __device__ __forceinline__ float point_tri_d2(float px, float py, float pz, cons
     const float e43 = d4 - d3, e56 = d5 - d6;
     const float t_bc = pt_clamp01(pt_guard(e43, e43 + e56));
     const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
-    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) {                    // edge region BC
+    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f && e43 + e56 > 0.0f) {   // edge region BC
         u = 1.0f - t_bc; v = t_bc;
         return pt_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
     }
+    // no vertex or edge region holds.  s is the squared area (times 4) as a sum of six products: where it stands clear of their
+    // rounding noise, the face point as Ericson takes it
     const float s = (va + vb) + vc;
-    if (s > 0.0f) {                                                     // face region
-        const float fv = vb / s, fw = vc / s;
-        qx = (t.ax + abx * fv) + acx * fw;
-        qy = (t.ay + aby * fv) + acy * fw;
-        qz = (t.az + abz * fv) + acz * fw;
+    const float noise = ((fabsf(d1 * d4) + fabsf(d3 * d2)) + (fabsf(d5 * d2) + fabsf(d1 * d6))) + (fabsf(d3 * d6) + fabsf(d5 * d4));
+    const float fv = vb / s, fw = vc / s;
+    qx = (t.ax + abx * fv) + acx * fw;
+    qy = (t.ay + aby * fv) + acy * fw;
+    qz = (t.az + abz * fv) + acz * fw;
+    if (s > kFaceNoise * noise) {                                       // (false for a NaN)
         u = fv; v = fw;
         return pt_clamped(px, py, pz, qx, qy, qz, t);
     }
-    // degenerate face: the nearest of the three edge points (ties: AB, then AC)
+    // a face whose area is rounding noise (a collinear triangle: va, vb, vc are residues of any sign): the nearest of the three
+    // edge points (ties: AB, then AC), unless the face point is a point of the triangle and no edge point is strictly nearer
     float best = pt_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
     u = t_ab; v = 0.0f;
     const float g_ac = pt_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
     if (g_ac < best) { best = g_ac; u = 0.0f; v = t_ac; }
     const float g_bc = pt_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
     if (g_bc < best) { best = g_bc; u = 1.0f - t_bc; v = t_bc; }
+    if (s > 0.0f && fv >= 0.0f && fw >= 0.0f && fv + fw <= 1.0f) {
+        const float g_f = pt_clamped(px, py, pz, qx, qy, qz, t);
+        if (!(best < g_f)) { best = g_f; u = fv; v = fw; }
+    }
     return best;
 }
 

@@ -26,6 +26,9 @@ __device__ __forceinline__ float rg_clamp01(float t)
     return t < 1.0f ? t : 1.0f;
 }
 
+// rt_abi.h's FACE_NOISE: a face sum at or below this share of the magnitudes of its six products is rounding noise
+constexpr float kFaceNoise = 0x1p-20f;
+
 struct Tri {
     float ax, ay, az, bx, by, bz, cx, cy, cz;
 };
@@ -55,32 +58,35 @@ __device__ __forceinline__ float range_tri_d2(float px, float py, float pz, cons
     if (d3 >= 0.0f && d4 <= d3) return rg_clamped(px, py, pz, t.bx, t.by, t.bz, t);                   // vertex region B
     const float vc = d1 * d4 - d3 * d2;
     const float t_ab = rg_clamp01(rg_guard(d1, d1 - d3));
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f)                                                       // edge region AB
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f && d1 - d3 > 0.0f)                                     // edge region AB
         return rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
     const float cpx = px - t.cx, cpy = py - t.cy, cpz = pz - t.cz;
     const float d5 = rg_dot(abx, aby, abz, cpx, cpy, cpz), d6 = rg_dot(acx, acy, acz, cpx, cpy, cpz);
     if (d6 >= 0.0f && d5 <= d6) return rg_clamped(px, py, pz, t.cx, t.cy, t.cz, t);                   // vertex region C
     const float vb = d5 * d2 - d1 * d6;
     const float t_ac = rg_clamp01(rg_guard(d2, d2 - d6));
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f)                                                       // edge region AC
+    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f && d2 - d6 > 0.0f)                                     // edge region AC
         return rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
     const float va = d3 * d6 - d5 * d4;
     const float e43 = d4 - d3, e56 = d5 - d6;
     const float t_bc = rg_clamp01(rg_guard(e43, e43 + e56));
     const float bcx = t.cx - t.bx, bcy = t.cy - t.by, bcz = t.cz - t.bz;
-    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f)                                                     // edge region BC
+    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f && e43 + e56 > 0.0f)                                 // edge region BC
         return rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
+    // no vertex or edge region holds: the face point where s stands clear of the rounding noise of its six products ...
     const float s = (va + vb) + vc;
-    if (s > 0.0f) {                                                                                   // face region
-        const float fv = vb / s, fw = vc / s;
-        return rg_clamped(px, py, pz, (t.ax + abx * fv) + acx * fw, (t.ay + aby * fv) + acy * fw, (t.az + abz * fv) + acz * fw, t);
-    }
-    // degenerate face: the nearest of the three edge points
+    const float noise = ((fabsf(d1 * d4) + fabsf(d3 * d2)) + (fabsf(d5 * d2) + fabsf(d1 * d6))) + (fabsf(d3 * d6) + fabsf(d5 * d4));
+    const float fv = vb / s, fw = vc / s;
+    const float g_f = rg_clamped(px, py, pz, (t.ax + abx * fv) + acx * fw, (t.ay + aby * fv) + acy * fw, (t.az + abz * fv) + acz * fw, t);
+    if (s > kFaceNoise * noise) return g_f;                                                           // (false for a NaN)
+    // ... else (a collinear triangle) the nearest of the three edge points, unless the face point is a point of the triangle and
+    // no edge point is strictly nearer
     float best = rg_clamped(px, py, pz, t.ax + t_ab * abx, t.ay + t_ab * aby, t.az + t_ab * abz, t);
     const float g_ac = rg_clamped(px, py, pz, t.ax + t_ac * acx, t.ay + t_ac * acy, t.az + t_ac * acz, t);
     if (g_ac < best) best = g_ac;
     const float g_bc = rg_clamped(px, py, pz, t.bx + t_bc * bcx, t.by + t_bc * bcy, t.bz + t_bc * bcz, t);
     if (g_bc < best) best = g_bc;
+    if (s > 0.0f && fv >= 0.0f && fw >= 0.0f && fv + fw <= 1.0f && !(best < g_f)) best = g_f;
     return best;
 }
 

@@ -407,16 +407,25 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
  *        bp = p - b, d3 = dot(ab, bp), d4 = dot(ac, bp)
  *        d3 >= 0 && d4 <= d3                     q = b                       (1, 0)
  *        vc = d1*d4 - d3*d2, t_ab = clamp01(guard(d1, d1 - d3))
- *        vc <= 0 && d1 >= 0 && d3 <= 0           q = a + t_ab*ab             (t_ab, 0)
+ *        vc <= 0 && d1 >= 0 && d3 <= 0 && d1 - d3 > 0            q = a + t_ab*ab     (t_ab, 0)
  *        cp = p - c, d5 = dot(ab, cp), d6 = dot(ac, cp)
  *        d6 >= 0 && d5 <= d6                     q = c                       (0, 1)
  *        vb = d5*d2 - d1*d6, t_ac = clamp01(guard(d2, d2 - d6))
- *        vb <= 0 && d2 >= 0 && d6 <= 0           q = a + t_ac*ac             (0, t_ac)
+ *        vb <= 0 && d2 >= 0 && d6 <= 0 && d2 - d6 > 0            q = a + t_ac*ac     (0, t_ac)
  *        va = d3*d6 - d5*d4, e43 = d4 - d3, e56 = d5 - d6, t_bc = clamp01(guard(e43, e43 + e56)), bc = c - b
- *        va <= 0 && e43 >= 0 && e56 >= 0         q = b + t_bc*bc             (1 - t_bc, t_bc)
- *        s = (va + vb) + vc, s > 0               fv = vb / s, fw = vc / s, q = (a + ab*fv) + ac*fw     (fv, fw)
- *        otherwise (a degenerate face)           the nearest of the three edge points a + t_ab*ab, a + t_ac*ac, b + t_bc*bc
- *                                                by the float dist2 of steps 2-3 (ties: AB, then AC), with their weights;
+ *        va <= 0 && e43 >= 0 && e56 >= 0 && e43 + e56 > 0        q = b + t_bc*bc     (1 - t_bc, t_bc)
+ *      (the fourth term of an edge region is the edge's squared length: an edge of two equal corners has no region, so a
+ *      triangle with a repeated corner is answered through its other edges)
+ *        s = (va + vb) + vc, fv = vb / s, fw = vc / s, face point f = (a + ab*fv) + ac*fw,
+ *        noise = ((|d1*d4| + |d3*d2|) + (|d5*d2| + |d1*d6|)) + (|d3*d6| + |d5*d4|), FACE_NOISE = 2^-20
+ *        s > FACE_NOISE * noise                  q = f                       (fv, fw)
+ *                                                (false for a NaN and for an infinite noise: products beyond float range)
+ *        otherwise                               s is the rounding noise of its six products (a collinear triangle: va, vb, vc
+ *                                                are residues of any sign, and f alone may lie anywhere along the triangle or
+ *                                                off it): the nearest of the three edge points a + t_ab*ab, a + t_ac*ac,
+ *                                                b + t_bc*bc by the float dist2 of steps 2-3 (ties: AB, then AC), with their
+ *                                                weights -- unless s > 0, fv >= 0, fw >= 0, fv + fw <= 1 and no edge point is
+ *                                                strictly nearer than f: then f, (fv, fw);
  *   2. clamp: q = fminf(fmaxf(q, lo), hi) componentwise, lo / hi = fminf / fmaxf of the three corners (the vertex box);
  *   3. dist2 = (dx*dx + dy*dy) + dz*dz, d = p - q.  u, v are returned + 0 (a -0 becomes +0).
  * The clamp is a projection onto a convex set that holds the triangle, so it only moves q toward the true closest point.  It

@@ -1,11 +1,13 @@
 """Reference closest-point queries in numpy: what rt_closest_points must return, restated from include/rt_abi.h with no code
 shared with the kernel.
 
-d2(p, a, b, c) is the float32 routine of the header, line for line: Ericson's ClosestPtPointTriangle (vertex regions, then edge
-regions, then face region; dots (x*x' + y*y') + z*z'; every division guarded, every edge weight clamped to [0, 1] by selects;
-the nearest of the three edge points when the face denominator is not > 0), then the clamp of the point into the triangle's
-vertex box (np.fmax then np.fmin: they drop NaN as fmaxf / fminf do), then dist2 = (dx*dx + dy*dy) + dz*dz.  numpy float32
-arithmetic is IEEE single with round-to-nearest and no contraction: the kernel's -ffp-contract=off arithmetic.
+d2(p, a, b, c) is the float32 routine of the header, line for line: Ericson's ClosestPtPointTriangle (vertex regions, then the
+regions of the edges that have a length, then the face point where s stands clear of the rounding noise of its products, else
+the nearest of the three edge points unless the face point is a point of the triangle and none of them is strictly nearer;
+dots (x*x' + y*y') + z*z'; every division guarded, every edge weight clamped to [0, 1] by selects), then the clamp of the
+point into the triangle's vertex box (np.fmax then np.fmin: they drop NaN as fmaxf / fminf do), then dist2 = (dx*dx + dy*dy) +
+dz*dz.  numpy float32 arithmetic is IEEE single with round-to-nearest and no contraction: the kernel's -ffp-contract=off
+arithmetic.
 
 brute_force(points, dist2_max, tris) is the lexicographic minimum of (dist2, id) over the triangles with dist2 <= dist2_max, the
 record every exact tree must return.  closest_f64 is an independent float64 closest point for accuracy checks."""
@@ -13,6 +15,7 @@ import numpy as np
 
 F = np.float32
 MISS = 0xFFFFFFFF
+FACE_NOISE = F(2.0 ** -20)      # s at or below this share of the sum of its products' magnitudes is rounding noise
 
 
 def _dot(ax, ay, az, bx, by, bz):
@@ -70,7 +73,7 @@ def d2(p, a, b, c):
         lo = [np.fmin(np.fmin(A[k], B[k]), C[k]) for k in range(3)]
         hi = [np.fmax(np.fmax(A[k], B[k]), C[k]) for k in range(3)]
 
-        # the face fallback: nearest of the three edge points by the clamped float dist2, ties to AB, then AC
+        # the nearest of the three edge points by the clamped float dist2, ties to AB, then AC
         g_ab, g_ac, g_bc = (_clamped_d2(P, q, lo, hi) for q in (q_ab, q_ac, q_bc))
         fb_d = g_ab
         fb_u, fb_v = t_ab, np.zeros_like(t_ab)
@@ -85,11 +88,10 @@ def d2(p, a, b, c):
         regions = [
             ((d1 <= 0) & (d2_ <= 0), A, F(0), F(0)),
             ((d3 >= 0) & (d4 <= d3), B, F(1), F(0)),
-            ((vc <= 0) & (d1 >= 0) & (d3 <= 0), q_ab, t_ab, F(0)),
+            ((vc <= 0) & (d1 >= 0) & (d3 <= 0) & ((d1 - d3) > 0), q_ab, t_ab, F(0)),
             ((d6 >= 0) & (d5 <= d6), C, F(0), F(1)),
-            ((vb <= 0) & (d2_ >= 0) & (d6 <= 0), q_ac, F(0), t_ac),
-            ((va <= 0) & (e43 >= 0) & (e56 >= 0), q_bc, F(1) - t_bc, t_bc),
-            (s > 0, q_f, fv, fw),
+            ((vb <= 0) & (d2_ >= 0) & (d6 <= 0) & ((d2_ - d6) > 0), q_ac, F(0), t_ac),
+            ((va <= 0) & (e43 >= 0) & (e56 >= 0) & ((e43 + e56) > 0), q_bc, F(1) - t_bc, t_bc),
         ]
         shape = np.broadcast(d1, P[0]).shape
         q = [np.zeros(shape, F) for _ in range(3)]
@@ -103,9 +105,17 @@ def d2(p, a, b, c):
             u, v = np.where(sel, uu, u), np.where(sel, vv, v)
             done |= sel
         dist = _clamped_d2(P, q, lo, hi)
-        dist = np.where(done, dist, fb_d).astype(F)
-        u = np.where(done, u, fb_u).astype(F) + F(0)       # + 0: -0 becomes +0, as in the kernel
-        v = np.where(done, v, fb_v).astype(F) + F(0)
+        # no vertex or edge region.  s is the squared area (times 4) as a sum of six products; where it stands clear of their
+        # rounding noise the face point is taken as Ericson takes it.  Where it does not (a collinear triangle: va, vb, vc are
+        # rounding residues) the face point only if its weights are those of a point of the triangle and no edge point is
+        # strictly nearer, else the nearest edge point
+        noise = ((np.abs(d1 * d4) + np.abs(d3 * d2_)) + (np.abs(d5 * d2_) + np.abs(d1 * d6))) + (np.abs(d3 * d6) + np.abs(d5 * d4))
+        clear = s > FACE_NOISE * noise                         # (false for a NaN)
+        g_f = _clamped_d2(P, q_f, lo, hi)
+        face = (s > 0) & (clear | ((fv >= 0) & (fw >= 0) & ((fv + fw) <= 1) & ~(fb_d < g_f)))
+        dist = np.where(done, dist, np.where(face, g_f, fb_d)).astype(F)
+        u = np.where(done, u, np.where(face, fv, fb_u)).astype(F) + F(0)       # + 0: -0 becomes +0, as in the kernel
+        v = np.where(done, v, np.where(face, fw, fb_v)).astype(F) + F(0)
     return dist, u, v
 
 

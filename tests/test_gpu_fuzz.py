@@ -1,7 +1,9 @@
 """Randomised GPU-vs-oracle parity over scene shapes the fixed tests do not enumerate: random sizes (incl. just above /
 below workgroup and tile boundaries), clustered and duplicated triangles, flat axes, huge and tiny triangles mixed,
 every builder (bottom-up, pairs, hybrid, SAH with pairs / splits) -- Node[] and TrianglePair[] bit-exact, kDepth and
-kBoxtests frames and one surface mode per seed (textured, per-corner attributes) byte-exact, counters equal.  Seeds are fixed: failures reproduce."""
+kBoxtests frames and one surface mode per seed (textured, per-corner attributes) byte-exact, counters equal.  Seeds are fixed: failures reproduce.
+Builders and traces only: the QUERIES on scenes of these kinds (and on trees of one to five triangles) are in
+tests/test_gpu_small_scenes.py, over the fixed scenes of tests/small_scenes.py."""
 import numpy as np
 import pytest
 

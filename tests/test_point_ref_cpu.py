@@ -117,3 +117,101 @@ def test_monotone_on_adversarial_points():
         for box in ((lo, hi), (blo, bhi)):
             d, _, _ = pr.d2(P, T[:, 0], T[:, 1], T[:, 2])
             assert (d >= pr.box_d2(P, *box)).all()
+
+
+def test_collinear_triangles_with_rounding_residues():
+    """c = a + w (b - a) rounded to float32: Ericson's va, vb, vc are then rounding residues of any sign, and a face point
+    formed from them alone lies anywhere along the triangle, or off it.  (The collinear triangles of signed_zero_mesh have
+    exact midpoints: their residues are zero.)  Found by the `points` scene of tests/small_scenes.py."""
+    for seed, scale, off in ((15, 1, 0), (16, 1e-3, 0), (17, 1, 50), (18, 100, 0), (19, 0.01, 3)):
+        rng = np.random.default_rng(seed)
+        n = 4000
+        a, b = ((rng.uniform(-1, 1, (n, 3)) * scale + off).astype(F) for _ in range(2))
+        c = (a + (b - a) * rng.uniform(-0.5, 1.5, (n, 1)).astype(F)).astype(F)
+        P = (rng.uniform(-1.5, 1.5, (n, 3)) * scale + off).astype(F)
+        M = np.abs(np.concatenate([a, b, c, P], 1)).max(1).astype(np.float64)
+        for corners in ((a, b, c), (c, a, b), (b, c, a)):
+            d, u, v = pr.d2(P, *corners)
+            assert np.isfinite(d).all() and ((u >= 0) & (v >= 0) & (u + v <= 1 + 1e-6)).all()
+            err = _rel_err(d, pr.closest_f64(P, *corners), M)
+            assert err.max() <= 8, f"scale {scale} at {off}: {err.max():.1f} ulps of the largest coordinate on {(err > 8).sum()} of {n}"
+
+
+def test_a_repeated_corner_in_any_position():
+    """Ericson's region of an edge of two equal corners would answer by that corner whatever the other edge offers
+    (signed_zero_mesh repeats the LAST corner only, which never reaches that region)"""
+    rng = np.random.default_rng(20)
+    n = 3000
+    a, b = rng.uniform(-1, 1, (n, 3)).astype(F), rng.uniform(-1, 1, (n, 3)).astype(F)
+    P = rng.uniform(-1.5, 1.5, (n, 3)).astype(F)
+    for corners in ((a, a, b), (a, b, a), (b, a, a), (a, b, b)):
+        d, _, _ = pr.d2(P, *corners)
+        assert _rel_err(d, pr.closest_f64(P, *corners), 1.5).max() <= 8
+
+
+def _collinear_errors(n):
+    """ulps of the largest coordinate between d2 and float64 on 15 n collinear triangles: five scales and offsets, the three
+    rotations of the corners"""
+    out = []
+    for seed, scale, off in ((1, 1, 0), (2, 1e-3, 0), (3, 1, 50), (4, 100, 0), (5, 0.01, 3)):
+        rng = np.random.default_rng(seed)
+        a, b = ((rng.uniform(-1, 1, (n, 3)) * scale + off).astype(F) for _ in range(2))
+        c = (a + (b - a) * rng.uniform(-0.5, 1.5, (n, 1)).astype(F)).astype(F)
+        P = (rng.uniform(-1.5, 1.5, (n, 3)) * scale + off).astype(F)
+        M = np.abs(np.concatenate([a, b, c, P], 1)).max(1).astype(np.float64)
+        for corners in ((a, b, c), (c, a, b), (b, c, a)):
+            out.append(_rel_err(pr.d2(P, *corners)[0], pr.closest_f64(P, *corners), M))
+    return np.concatenate(out)
+
+
+def test_the_noise_factor_is_where_the_sweep_puts_it(monkeypatch):
+    """FACE_NOISE = 2^-20: on 150,000 collinear triangles the factors 2^-17 .. 2^-21 leave none more than 8 ulps from float64,
+    2^-22 and below let noise through as a face; a negative factor is Ericson's rule itself (s > 0 alone)"""
+    assert pr.FACE_NOISE == F(2.0 ** -20)
+    bad = {}
+    for e in (-17, -20, -21, -23, None):
+        monkeypatch.setattr(pr, "FACE_NOISE", F(-1) if e is None else F(2.0 ** e))
+        err = _collinear_errors(10000)
+        bad[e] = int((err > 8).sum())
+        print(f"FACE_NOISE {'none (Ericson)' if e is None else f'2^{e}'}: {bad[e]} of {err.size} beyond 8 ulps, worst {err.max():.1f}")
+    assert bad[-17] == 0 and bad[-20] == 0 and bad[-21] == 0, bad
+    assert bad[-23] > 0 and bad[None] > 100, f"the sample does not need the gate: {bad}"
+
+
+def _pairs_that_differ(tris, points, monkeypatch):
+    """(d2 under the rule, d2 under Ericson's face rule, float64 distance) of the (point, triangle) pairs whose d2 differs"""
+    T = tris.reshape(-1, 3, 3)
+    new, old, ref = [], [], []
+    for s0 in range(0, len(points), 64):
+        q = points[s0:s0 + 64]
+        monkeypatch.setattr(pr, "FACE_NOISE", F(2.0 ** -20))
+        dn = pr.d2(q[:, None, :], T[None, :, 0], T[None, :, 1], T[None, :, 2])[0]
+        monkeypatch.setattr(pr, "FACE_NOISE", F(-1))             # s > -noise: Ericson's s > 0 alone, overflowed products too
+        do = pr.d2(q[:, None, :], T[None, :, 0], T[None, :, 1], T[None, :, 2])[0]
+        i, j = np.nonzero(dn.view(np.uint32) != do.view(np.uint32))
+        new.append(dn[i, j]); old.append(do[i, j]); ref.append(pr.closest_f64(q[i], T[j, 0], T[j, 1], T[j, 2]))
+    return np.concatenate(new), np.concatenate(old), np.concatenate(ref)
+
+
+def test_the_gate_changes_ordinary_scenes_nowhere_and_the_fractal_toward_float64(scenes, monkeypatch):
+    """With a negative FACE_NOISE the face rule is Ericson's.  On the grid and soup scenes with the GPU tests' point sets no
+    (point, triangle) pair has another d2 under the gate.  On the fractal scene some do: its coordinates reach 2^45, the
+    products overflow, s and the noise are both infinite and the face weights NaN -- an infinite noise is never cleared, so
+    the edges answer, and the gated value is the one closer to float64"""
+    from test_gpu_point_queries import _point_sets
+    from test_gpu_ray_queries import _scene
+    for name in ("grid", "soup"):
+        tris = np.ascontiguousarray(_scene(name, scenes)[0], F).reshape(-1, 9)
+        for kind, p in _point_sets(tris, sum(name.encode())).items():
+            new, _, _ = _pairs_that_differ(tris, p[:256], monkeypatch)
+            assert new.size == 0, f"{name}/{kind}: {new.size} pairs change"
+    tris = np.ascontiguousarray(_scene("fractal", scenes)[0], F).reshape(-1, 9)
+    sets = _point_sets(tris, sum(b"fractal"))
+    new, old, ref = (np.concatenate(x) for x in zip(*(_pairs_that_differ(tris, sets[k][:256], monkeypatch)
+                                                      for k in ("near", "on_vertex_edge"))))
+    with np.errstate(all="ignore"):
+        en, eo = (np.abs(np.sqrt(d.astype(np.float64)) - ref) / np.maximum(ref, 1e-300) for d in (new, old))
+    closer = int((en < eo).sum())
+    print(f"fractal: {new.size} pairs differ, the gated d2 is closer to float64 in {closer}; median relative error "
+          f"{np.median(en):.2e} against {np.median(eo):.2e}")
+    assert new.size >= 100 and closer >= 0.99 * new.size and np.median(en) < 1e-3 * np.median(eo)
