@@ -125,8 +125,24 @@ __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, f
     return true;
 }
 
-// per-lane traversal state
-enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3 };
+// Hold at pop (trace_ray<.., QW = true>; 0 here builds every kernel without it, the parent arm of tools/quad_wait_arms.sh):
+// a lane that has just popped entry E from level s of its stack takes no box step while a quad-mate still holds E at level s
+// of its own stack -- the mate is deeper in the subtree both took first, and when it pops E the two step on E with one
+// address, which the address path charges as one request (quad_hold below).
+#ifndef RT_TRACE_QUAD_WAIT
+#define RT_TRACE_QUAD_WAIT 1
+#endif
+
+// 0 (shipped): the rule is evaluated once per vote -- the second box step under the vote steps every lane in PH_STEP, so a
+// lane that popped in the first step is not held until the next vote.  1: the second step evaluates the rule again: more
+// merged requests (TA busy -19 %), but the LDS read and the DPP moves then sit in front of every step's loads and
+// the waves wait longer than the address path gains: -2.4 % where 0 is +5 %.
+#ifndef RT_TRACE_QUAD_WAIT_SECOND
+#define RT_TRACE_QUAD_WAIT_SECOND 0
+#endif
+
+// per-lane traversal state.  PH_STEP_POP (QW traversals only): PH_STEP whose cur was popped from the stack, from level sp.
+enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3, PH_STEP_POP = 4 };
 constexpr uint32_t kNoNear = 0xFFFFFFFFu;  // "no Box child hit yet" (child 2^29-1, count 7: not a real entry)
 
 // The private spill array is NOT a member: a dynamically indexed member would pin the whole struct in scratch.
@@ -170,6 +186,8 @@ struct Trav {
     // the current pair is finished: remaining slots of the same node (count > 2 only, never in an LBVH), else
     // the nearest child (the reference pushes it last and pops it first -- so on a FULL stack that push is dropped
     // like any other and the entry below it is popped instead: same rule as the oracle), else a popped entry, else done
+    // QW: a popped cur is marked (PH_STEP_POP); the lane is in PH_STEP when it gets here.
+    template <bool QW = false>
     __device__ __forceinline__ void advance()
     {
         const uint32_t cnt = cur >> 29;
@@ -177,7 +195,10 @@ struct Trav {
         const bool keep = (near_e != kNoNear) & (sp < kStackMax);
         if (keep) cur = near_e;
         else if (sp == 0) phase = PH_DONE;
-        else { --sp; cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds]; }
+        else {
+            --sp; cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds];
+            if constexpr (QW) phase = PH_STEP_POP;
+        }
         near_e = kNoNear;
         near_d = __builtin_inff();
     }
@@ -221,10 +242,11 @@ __device__ __forceinline__ void prefetch_pair(const Params& p, Trav& t)
 // The tests of one box step on a fetched pair (Tracer.cu:323-352 for one pair): both slabs are computed before the ordered
 // tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.  `two`: the pair has a second slot
 // (else a1 / b1 repeat the first).
-template <bool PF, class Params>
+template <bool PF, bool QW = false, class Params>
 __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0,
                                             const uint4& a1, const uint4& b1)
 {
+    if constexpr (QW) t.phase = PH_STEP;   // (PH_STEP_POP: the popped entry is being stepped on)
     float f0, k0;
     slab(a0, b0, r, f0, k0);
     slab(a1, b1, r, t.f1, t.k1);
@@ -240,12 +262,12 @@ __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav&
     if (leaf0) { t.leaf = e0; t.phase = PH_LEAF0; }
     else {
         t.second_slot(r.tmin, r.tmax);
-        if (t.phase == PH_STEP) { t.advance(); prefetch_pair<PF>(p, t); }
+        if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
     }
 }
 
 // One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
-template <bool PF, class Params>
+template <bool PF, bool QW = false, class Params>
 __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
 {
     const uint32_t cnt = t.cur >> 29;
@@ -264,7 +286,41 @@ __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
         __builtin_amdgcn_sched_barrier(0);
 #endif
     }
-    box_step_on<PF>(p, r, t, two, a0, b0, a1, b1);
+    box_step_on<PF, QW>(p, r, t, two, a0, b0, a1, b1);
+}
+
+// Hold at pop, evaluated by the WHOLE wave (it reads its quad-mates' registers through DPP, and a switched-off lane's registers
+// are not defined data for such a read: never call this under a lane-divergent branch).  True for a lane that sits on a
+// freshly popped entry (PH_STEP_POP, popped from level sp < kStackLds) while a quad-mate that is still traversing has
+// mate.sp > sp and the same entry at level sp of its own stack.  The quad's four entries of one level lie side by side in
+// the stack column layout: one 16-byte LDS read.  Levels from kStackLds up live in private memory: never looked at, never
+// held for.  A finished lane (PH_DONE; a lane outside the frame is finished from the start) counts as sp = 0, which no level
+// is below.
+//
+// Why nobody waits for ever: a lane holds only for a mate with strictly greater sp, so the unfinished lane of a quad with the
+// greatest sp never holds -- it steps, or it is parked for a leaf test.  A wave with an unfinished lane therefore always has a
+// lane that steps or a parked lane, and every pass of trace_ray's loop takes a box step with at least one lane or runs a leaf
+// phase that frees the parked ones.  The entry a lane holds for is a live entry of the mate's stack (level sp < mate.sp): the
+// mate pops it after finitely many of its own tests -- pops are LIFO also on a full stack, where only pushes are dropped -- or
+// finishes first (any-hit), and either ends the hold.  No spin, no flag, nothing outside the wave.
+template <bool ANY>
+__device__ __forceinline__ bool quad_hold(const Trav& t)
+{
+    const bool popped = t.phase == PH_STEP_POP && t.sp < kStackLds;
+    const int key = ANY && t.phase == PH_DONE ? 0 : t.sp;   // (a closest-hit lane finishes on an empty stack: sp = 0 already)
+    // quad_perm broadcasts of the quad's lanes 0..3 (row_mask / bank_mask all, bound_ctrl on)
+    const int k0 = __builtin_amdgcn_mov_dpp(key, 0x00, 0xF, 0xF, true), k1 = __builtin_amdgcn_mov_dpp(key, 0x55, 0xF, 0xF, true);
+    const int k2 = __builtin_amdgcn_mov_dpp(key, 0xAA, 0xF, 0xF, true), k3 = __builtin_amdgcn_mov_dpp(key, 0xFF, 0xF, 0xF, true);
+    bool hold = false;
+    if (popped) {
+        typedef uint32_t lds_u32x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) lds_u32x4 lds_quad;
+        // (the stack array is 16-byte aligned and a quad's four columns share one 16-byte group: rounding the lane's own column down finds it)
+        const lds_u32x4 e = *(const lds_quad*)(((uintptr_t)t.lds & ~(uintptr_t)15) + (uintptr_t)t.sp * 256u);
+        hold = ((k0 > t.sp) & (e.x == t.cur)) | ((k1 > t.sp) & (e.y == t.cur)) | ((k2 > t.sp) & (e.z == t.cur)) |
+               ((k3 > t.sp) & (e.w == t.cur));
+    }
+    return hold;
 }
 
 // The same step for the lanes that sit on the pair `c` (packed like Trav::cur), c WAVE-UNIFORM: the pair's 64 bytes are read
@@ -323,10 +379,13 @@ __device__ __forceinline__ bool box_step_wave(const Params& p, const Ray& r, Tra
 // ANY (any-hit): a lane whose leaf test hits is done (PH_DONE) -- until that first hit its sequence of tests is the
 // closest-hit one, step for step.  Params: anything with nodes, leaves, root, count, park_num, park_den.
 // Filter: the hit-filter policy handed to every leaf test (NoFilter: none).
-template <bool PF, bool ANY = false, class Params, class Filter = NoFilter>
+// QW: hold at pop (quad_hold above): a held lane stays in its phase and sits out the vote's first box step; the vote counts the
+// lanes that will really step.  t.lds must then be a column of a 16-byte aligned [kStackLds][64] array.
+template <bool PF, bool ANY = false, bool QW = false, class Params, class Filter = NoFilter>
 __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav& t, bool active, uint32_t* steps,
                                           Filter flt = Filter())
 {
+    static_assert(!(PF && QW), "prefetch_pair tests phase == PH_STEP: a PH_STEP_POP lane would step on a stale prefetched pair");
     t.sp = 0;
     t.cur = (p.root & kIndexMask) | (p.count << 29);
     t.near_e = kNoNear;
@@ -350,6 +409,22 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
         // ---------------------------------------------------- box phase: step while enough lanes want to
         uint64_t stepping, parked;
         while (true) {
+            if constexpr (QW) {
+                const bool go = ((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t);
+                stepping = __builtin_amdgcn_ballot_w64(go);
+                parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
+                // (held lanes counted on the stepping side of this threshold instead: measured, no different -- DESIGN section 5)
+                if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
+                nbox += 2;
+                if (go) box_step<PF, true>(p, r, t);
+                // second step under the same vote
+#if RT_TRACE_QUAD_WAIT_SECOND
+                if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true>(p, r, t);
+#else
+                if ((t.phase & 3u) == PH_STEP) box_step<PF, true>(p, r, t);
+#endif
+                continue;
+            }
             stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
             parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
             if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
@@ -412,7 +487,7 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 const bool was_first = t.phase == PH_LEAF0;
                 t.phase = PH_STEP;
                 if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) { t.advance(); prefetch_pair<PF>(p, t); }
+                if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
             }
         }
     }

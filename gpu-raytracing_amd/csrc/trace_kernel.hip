@@ -19,6 +19,14 @@
 //     wave keeps stepping boxes for the others; when parked lanes outnumber stepping lanes
 //     (one __builtin_amdgcn_ballot_w64 pair per step) the wave runs ONE leaf phase for all of them.
 //     Only the interleaving ACROSS lanes changes; each ray's own sequence of tests is untouched;
+//   * HOLD AT POP (quad_hold, rt_traverse.hpp; the instantiations trace_quad_wait() names): the address path charges a quad
+//     ONE request for a load only when its lanes carry one address, and the four rays of a 2 x 2 pixel quad visit nearly the
+//     same pairs a step or more apart.  A lane that has just popped entry E from level s of its stack sits out the FIRST
+//     box step of a vote while a quad-mate still holds E at level s of its own (the mate is deeper in the subtree both
+//     took first); the rule is asked once per vote, the vote counts the lanes that will take that first step, and the
+//     second step under the vote steps every lane in PH_STEP, held ones included.  A held lane keeps its phase; a mate
+//     that pops E in the meantime steps on it with the held lane, one address, one request.  Again only the
+//     interleaving across lanes changes.  Nobody waits for ever: see the comment at quad_hold;
 //   * a leaf (64 bytes) is fetched with four 16-byte loads issued together, the words no test reads included: left to
 //     itself the compiler narrows them to seven smaller requests, and the address path charges per request;
 //   * the traversal stack is a lane-interleaved LDS column addressed through an address_space(3)
@@ -101,10 +109,19 @@ struct TraceParams {
 // rt_shade.hpp, shared with shade.hip.  shade_sample below keeps its own text of the shaders after the hit: routing it through
 // rt_shade.hpp's shade_unlit / shade_lit changed the instruction order and spill counts of modes 3 and 5-8)
 
+// Which instantiations can hold at pop (rt_traverse.hpp quad_hold): RT_TRACE_QUAD_WAIT = 1 the 64-VGPR ones (kDepth / kBoxtests /
+// kTriangleTests) of cache-resident scenes, 2 the shaded ones as well (both traversals of kTextureLitShadows), 0 none.  The
+// PF instantiations wait for L2 misses, not for the address path, and keep the plain loop.  Each such instantiation exists
+// with and without the rule (trace_kernel's QW) and launch_trace picks by tree: see there.  How each was decided: DESIGN section 5.
+constexpr bool trace_quad_wait(int render, bool pf)
+{
+    return !pf && (RT_TRACE_QUAD_WAIT >= 2 || (RT_TRACE_QUAD_WAIT == 1 && (render <= 2 || render == kRenderDebugBoxCount)));
+}
+
 // one sample of one pixel -> float colour 0..255 per channel + alpha (TraceRays body, Tracer.cu:482-593).
 // Every lane of the wave calls this (inactive lanes trace nothing) because trace_ray votes with ballots; the shadow
 // ray of kTextureLitShadows is a second wave-level traversal over the lanes that hit something.
-template <int RENDER, bool PF>
+template <int RENDER, bool PF, bool QW>
 __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_camera& cam, uint32_t x, uint32_t y,
                                              float ox, float oy, Trav& t, bool active, uint32_t& box_acc,
                                              uint32_t& tri_acc, uint32_t* steps, float& R, float& G, float& B, float& A)
@@ -114,7 +131,7 @@ __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_came
     camera_ray(cam, p.w, p.h, x, y, ox, oy, r);
     r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
     Hit h = {0u, 0u, 0.f, 0.f};
-    const bool hit = trace_ray<PF>(p, r, h, t, active, steps);
+    const bool hit = trace_ray<PF, false, QW>(p, r, h, t, active, steps);
     const uint32_t box_tests = t.box_tests, tri_tests = t.tri_tests;
     box_acc += box_tests;
     tri_acc += tri_tests;
@@ -218,7 +235,7 @@ __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_came
         sr.tmin = 0.001f;
         sr.tmax = to_light;
         Hit sh = {0u, 0u, 0.f, 0.f};
-        shadowed = trace_ray<PF>(p, sr, sh, t, lit, steps);   // its test counts are not reported (shadow_stats, :451)
+        shadowed = trace_ray<PF, false, QW>(p, sr, sh, t, lit, steps);   // its test counts are not reported (shadow_stats, :451)
     }
     if (!lit) return;
     const float w0 = 1 - h.bu - h.bv;
@@ -273,13 +290,13 @@ __device__ __forceinline__ void shade_sample(const TraceParams& p, const rt_came
 // +16 % with frames in flight on camera A, +6 / +14 % on camera B; on the cache-resident 1M tree the same kernel is 25 % SLOWER
 // (five waves instead of eight feed the address path), at 4.5M -7 % / +6 %; at 64 - 80 VGPRs the sixteen extra registers
 // spill and it is 2 - 5 x slower everywhere (profiles/r04_trace_10m_experiments.txt).  launch_trace picks it by scene size.
-template <int RENDER, bool PF>
+template <int RENDER, bool PF, bool QW = false>
 // kDepth / kBoxtests / kTriangleTests end in a one-line colour conversion: they fit 64 VGPRs (8 waves per SIMD); the
 // shading of the other render types would spill there, they keep 72 VGPRs (7 waves) (RT_TRACE_LEAN_EXTRA: rt_traverse.hpp)
 __global__ __launch_bounds__(kTraceWaves * 64, PF ? RT_TRACE_PF_WAVES : ((RENDER <= 2 || RENDER == kRenderDebugBoxCount) ? RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA : RT_TRACE_MIN_WAVES))
 void trace_kernel(TraceParams p)
 {
-    __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
+    __shared__ __attribute__((aligned(16))) uint32_t stack_lds[kTraceWaves][kStackLds][64];   // (aligned: quad_hold reads a quad's four columns of a level as 16 bytes)
     __shared__ unsigned long long csum[4];   // the workgroup's test counters (see the end of the kernel)
     __shared__ uint32_t carrive;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -321,13 +338,13 @@ void trace_kernel(TraceParams p)
     uint32_t steps[2] = {0u, 0u};
     float R, G, B, A;
     if (p.spp <= 1) {
-        shade_sample<RENDER, PF>(p, cam, x, y, 0.5f, 0.5f, t, active, box_acc, tri_acc, steps, R, G, B, A);
+        shade_sample<RENDER, PF, QW>(p, cam, x, y, 0.5f, 0.5f, t, active, box_acc, tri_acc, steps, R, G, B, A);
     } else {
         float ar = 0, ag = 0, ab = 0, aa = 0;
         const uint32_t side = p.spp == 4 ? 2u : 4u;   // stratified side x side sub-pixel grid (2 x 2 or 4 x 4)
         for (uint32_t s = 0; s < p.spp; s++) {
             const float ox = ((float)(s % side) + 0.5f) / (float)side, oy = ((float)((s / side) % side) + 0.5f) / (float)side;
-            shade_sample<RENDER, PF>(p, cam, x, y, ox, oy, t, active, box_acc, tri_acc, steps, R, G, B, A);
+            shade_sample<RENDER, PF, QW>(p, cam, x, y, ox, oy, t, active, box_acc, tri_acc, steps, R, G, B, A);
             ar += R; ag += G; ab += B; aa += A;
         }
         R = ar / (float)p.spp; G = ag / (float)p.spp; B = ab / (float)p.spp; A = aa / (float)p.spp;
@@ -442,7 +459,16 @@ hipError_t launch_trace(const TraceLaunch& t, hipStream_t st)
     // scene size (DeviceScene::num_attributes, filled by the caller as main.cu:166 does; 0 = unknown): a tree of kPrefetchMinPrims
     // primitives is 1 GB of nodes + leaves, four times the Infinity Cache
     const bool pf = t.scene.num_attributes >= kPrefetchMinPrims;
-#define RT_TRACE_CASE(R) case R: if (pf) trace_kernel<R, true><<<grid, block, 0, st>>>(p); else trace_kernel<R, false><<<grid, block, 0, st>>>(p); break;
+    // Hold at pop by tree: a tree entered through a root PAIR (the bottom-up builders: LBVH, pairs, hybrid) takes the
+    // instantiation with the rule; one entered through a single root slot (the SAH builder's, whose traversals are a quarter
+    // as long and leaf-heavy) keeps the plain loop -- with the rule it ties with frames in flight and loses 1.1 % one frame
+    // at a time (profiles/quad_wait_bench.txt).  Both loops do the same tests: the choice is about time only.
+    const bool qw = t.as.count >= 2;
+#define RT_TRACE_CASE(R) case R: \
+        if (pf) trace_kernel<R, true><<<grid, block, 0, st>>>(p); \
+        else if (trace_quad_wait(R, false) && qw) trace_kernel<R, false, trace_quad_wait(R, false)><<<grid, block, 0, st>>>(p); \
+        else trace_kernel<R, false><<<grid, block, 0, st>>>(p); \
+        break;
     switch (t.render_type) {
     RT_TRACE_CASE(RT_RENDER_DEPTH)
     RT_TRACE_CASE(RT_RENDER_BOXTESTS)
