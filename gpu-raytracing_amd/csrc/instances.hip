@@ -4,8 +4,8 @@
 // prepare_instances_kernel, one thread per instance: the world box of the BLAS's root run through object_to_world, the
 // padded box as a proxy triangle (the TLAS build input), world_to_object in double.
 //
-// instance_query_kernel<PF, ANY>: rt_traverse.hpp's wave-level two-phase loop with a second level (trace_instanced,
-// rt_instance_traverse.hpp: shared with the filtered query of instance_filter_query.hip).  One lane per ray, the
+// instance_query_kernel<PF, ANY, FILTERED>: rt_traverse.hpp's wave-level two-phase loop with a second level (trace_instanced,
+// rt_instance_traverse.hpp).  One lane per ray, the
 // launch geometry, LDS stack, XCD remap and counters of ray_query_kernel.  What the second level adds to a lane:
 //   * per-lane node / leaf base pointers: the lanes of one wave sit in different BLASes (and in the TLAS);
 //   * TLAS leaves are ordered with the box children: a leaf hit in the TLAS becomes an entry of count 0 (child : 29 | 0,
@@ -19,16 +19,31 @@
 //     world ray from the ray array (the original bits), switches back to the TLAS and advances there -- which may enter the
 //     next instance in the same leaf phase.
 // tmax is shared by both spaces (an affine map preserves t): one closest hit across all instances.
+// FILTERED (rt_intersect_rays_instanced_filtered; rt_abi.h, instance-filter block) hands trace_instanced one
+// more policy, the lane's InstanceRayFilter (rt_instance_filter.hpp); the unfiltered arms keep their code, instruction for
+// instruction:
+//   * ray setup: one 16-byte load of the ray's {mask, skip_instance, skip_id} when the caller gave per-ray records;
+//   * PH_ENTER: the instance rule comes first -- one 8-byte load of the instance's {mask, flags} (none when the instance has no
+//     record), and an instance whose mask misses the ray's is left like a flagged one: no record load, no rt_accel load, the
+//     lane advances in the TLAS.  An entered instance sets the lane's per-instance part from the w0 .. w2 rows the kernel has
+//     already loaded: the effective cull bits (the 3x3 determinant's sign only when a cull bit is set -- the flags are
+//     wave-uniform) and the effective skip id;
+//   * leaf test: that per-instance part goes by value to intersect_tri, which asks it after the t window test and before
+//     r.tmax = t -- a rejected candidate shrinks no window and ends no any-hit ray.
 // Compiled with -ffp-contract=off: every float operation is the documented one.
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
+#include "rt_instance_filter.hpp"
 #include "rt_instance_traverse.hpp"
 #include "rt_traverse.hpp"
+
+#include <type_traits>
 
 static_assert(sizeof(rt_instance) == 64 && offsetof(rt_instance, blas) == 48, "rt_instance: 3x4 matrix, blas, 3 pads");
 static_assert(sizeof(rt_instance_record) == 64 && offsetof(rt_instance_record, blas) == 48 &&
               offsetof(rt_instance_record, flags) == 52, "rt_instance_record: 3x4 matrix, blas, flags, 2 spare");
 static_assert(sizeof(rt_accel) == 24, "rt_accel: two pointers, root, count");
+static_assert(rt::kQueryBlock == rt::kTraceWaves * 64, "rt_launch.hpp: one lane per ray, kTraceWaves waves per workgroup");
 
 namespace rt {
 
@@ -130,13 +145,78 @@ __global__ __launch_bounds__(256) void prepare_instances_kernel(const rt_instanc
 
 // ---------------------------------------------------------------- query (the two-level loop: rt_instance_traverse.hpp)
 
-template <bool PF, bool ANY>
+struct FilteredInstParams : InstParams {
+    InstanceFilterParams filter;
+};
+
+// ray setup, the two-level traversal, the record and instance id of the hit, the per-workgroup counters
+template <bool PF, bool ANY, bool FILTERED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_INSTANCE_QUERY_WAVES)
-void instance_query_kernel(InstParams p)
+void instance_query_kernel(std::conditional_t<FILTERED, FilteredInstParams, InstParams> p)
 {
-#define RT_BODY_MAKE_FILTER(i, in_range) NoInstanceFilter()
-#include "rt_instance_query_body.inc"
-#undef RT_BODY_MAKE_FILTER
+    __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
+    __shared__ unsigned long long csum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (p.counters) {
+        if (threadIdx.x < 4) csum[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
+    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    const bool in_range = i < p.num_rays;
+
+    Ray r;
+    r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
+    r.tmin = 0.0f;
+    r.tmax = -1.0f;
+    if (in_range) {
+        load_world_ray(p, i, r);
+        r.tmin = p.rays[2 * i].w;
+        r.tmax = p.rays[2 * i + 1].w;
+    }
+    const bool nan_ray = __builtin_isnan(r.ox) | __builtin_isnan(r.oy) | __builtin_isnan(r.oz) | __builtin_isnan(r.dx) |
+                         __builtin_isnan(r.dy) | __builtin_isnan(r.dz);
+    const bool active = in_range && r.tmin <= r.tmax && !nan_ray;
+
+    SpillArray spill;
+    Trav t;
+    t.lds = (lds_u32*)&stack_lds[wave][0][lane];
+    t.spill = spill;
+    uint32_t steps[2] = {0u, 0u};
+    Hit h = {0u, 0u, 0.f, 0.f};
+    uint32_t hit_inst = RT_MISS;
+    // the lane's filter, made HERE under `if constexpr`, not by a helper function (DESIGN sections 20 and 21)
+    std::conditional_t<FILTERED, InstanceRayFilter, NoInstanceFilter> flt;
+    if constexpr (FILTERED) flt = instance_ray_filter(p.filter, i, in_range);
+    const bool hit = trace_instanced<PF, ANY>(p, i, r, h, hit_inst, t, active, steps, flt);
+
+    if (in_range) {
+        float4 o = {__builtin_inff(), __uint_as_float(RT_MISS), 0.f, 0.f};
+        if (hit) {
+            // the hit instance's BLAS leaves; (u, v) back to the caller's corners as ray_query_kernel does
+            const uint32_t b = reinterpret_cast<const uint4*>(p.records + hit_inst)[3].x;
+            const rt_triangle_pair* lv = reinterpret_cast<const rt_triangle_pair*>(
+                *reinterpret_cast<const uint64_t*>(p.blas_table + b));
+            const uint32_t rot = lv[h.tri_id >> 1].rotations[h.tri_id & 1];
+            o = hit_record(r.tmax, h.primitive_id, h.bu, h.bv, rot);
+        }
+        p.hits[i] = o;
+        p.instance_ids[i] = hit ? hit_inst : RT_MISS;
+    }
+    if (p.counters) {
+        const uint32_t bsum = wave_sum_u32(t.box_tests), tsum = wave_sum_u32(t.tri_tests);
+        if (lane == 0) {
+            atomicAdd(&csum[0], (unsigned long long)bsum);
+            atomicAdd(&csum[1], (unsigned long long)tsum);
+            atomicAdd(&csum[2], (unsigned long long)steps[0]);
+            atomicAdd(&csum[3], (unsigned long long)steps[1]);
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const unsigned long long v = csum[threadIdx.x];
+            if (v) atomicAdd(&p.counters[threadIdx.x], v);
+        }
+    }
 }
 
 }  // namespace
@@ -152,9 +232,9 @@ hipError_t launch_prepare_instances(const rt_instance* instances, uint32_t num_i
     return hipGetLastError();
 }
 
-hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st)
+hipError_t launch_instance_query(const InstanceQuery& q, const rt_instance_hit_filter* filter, hipStream_t st)
 {
-    InstParams p;
+    FilteredInstParams p;
     p.tlas_nodes = q.tlas.nodes;
     p.tlas_leaves = q.tlas.triangles;
     p.root = q.tlas.root;
@@ -168,16 +248,12 @@ hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st)
     p.instance_ids = q.instance_ids;
     p.num_rays = q.num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(q.counters);
-    const uint32_t rays_per_block = kTraceWaves * 64;
-    const dim3 grid((uint32_t)(((uint64_t)q.num_rays + rays_per_block - 1) / rays_per_block)), block(rays_per_block);
-    const bool pf = q.num_primitives >= kPrefetchMinPrims;
-    if (pf) {
-        if (q.any_hit) instance_query_kernel<true, true><<<grid, block, 0, st>>>(p);
-        else instance_query_kernel<true, false><<<grid, block, 0, st>>>(p);
-    } else {
-        if (q.any_hit) instance_query_kernel<false, true><<<grid, block, 0, st>>>(p);
-        else instance_query_kernel<false, false><<<grid, block, 0, st>>>(p);
-    }
+    if (filter) p.filter = instance_filter_params(*filter);
+    const dim3 grid(query_blocks(q.num_rays)), block(kQueryBlock);
+    dispatch_pf_any(q.num_primitives >= kPrefetchMinPrims, q.any_hit, [&](auto pf, auto any) {
+        if (filter) instance_query_kernel<pf(), any(), true><<<grid, block, 0, st>>>(p);
+        else instance_query_kernel<pf(), any(), false><<<grid, block, 0, st>>>(p);   // (its InstParams part)
+    });
     return hipGetLastError();
 }
 

@@ -15,10 +15,17 @@
 //   * counters (optional): the four sums are wave-reduced, added in LDS, and published with 4 device atomics per workgroup
 //     (exact; no shared slots).  At 8,100 workgroups per 1080p frame those same-address atomics queue at ~18 ns each, about
 //     0.15 ms behind the last workgroup -- a cost of counting, not of the query (counters off: none).
+//   * FILTERED (rt_intersect_rays_filtered; rt_abi.h, hit-filter block): the lane's RayFilter
+//     (rt_ray_filter.hpp) goes down to intersect_tri, which asks it after the t window test and before r.tmax = t -- a
+//     rejected candidate shrinks no window and ends no any-hit ray.  No post-pass: box tests, leaf visits and stack are the
+//     unfiltered arm's.  Cost: one 8-byte load per ray at ray setup when the caller gave per-ray records, and per candidate
+//     that passed Moller-Trumbore and the window two compares of the determinant already in registers, one compare against
+//     skip_id and -- only for a survivor -- one 4-byte prim_masks load.  A kept record is the unfiltered record, bit for bit.
 // No shading: the launch bounds are those of trace_kernel's lean (kDepth) instantiation.
 // Compiled with -ffp-contract=off: results are bit-identical to trace_kernel's and the C oracle's.
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
+#include "rt_ray_filter.hpp"
 #include "rt_traverse.hpp"
 
 #include <type_traits>
@@ -43,6 +50,11 @@ struct IndexedQueryParams : QueryParams {
     uint32_t num_indices;
 };
 
+// rt_intersect_rays_filtered: the same query with a hit filter (never indexed: there is no such entry point)
+struct FilteredQueryParams : QueryParams {
+    FilterParams filter;
+};
+
 // launch position j -> ray index (0xFFFFFFFF: no ray -- num_rays is a uint32, so it is never in range)
 template <bool INDEXED, class Params>
 __device__ __forceinline__ uint64_t ray_index(const Params& p, uint64_t j)
@@ -51,12 +63,16 @@ __device__ __forceinline__ uint64_t ray_index(const Params& p, uint64_t j)
     else return j;
 }
 
-// One kernel body for both entry points.  INDEXED only changes how the lane's ray index i is obtained: the launch position
-// itself, or order[position] (positions past num_indices and indices >= num_rays: no ray, nothing written).
-template <bool PF, bool ANY, bool INDEXED>
+// One kernel body for the three entry points.  INDEXED only changes how the lane's ray index i is obtained: the launch
+// position itself, or order[position] (positions past num_indices and indices >= num_rays: no ray, nothing written).
+// FILTERED only changes the policy handed to trace_ray.  The lane's filter is made HERE, under `if constexpr`: made by a
+// helper function it changes the unfiltered arms' code.
+template <bool PF, bool ANY, bool INDEXED, bool FILTERED>
 __global__ __launch_bounds__(kTraceWaves * 64, PF ? RT_TRACE_PF_WAVES : RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA)
-void ray_query_kernel(std::conditional_t<INDEXED, IndexedQueryParams, QueryParams> p)
+void ray_query_kernel(std::conditional_t<FILTERED, FilteredQueryParams,
+                                         std::conditional_t<INDEXED, IndexedQueryParams, QueryParams>> p)
 {
+    static_assert(!(INDEXED && FILTERED), "there is no filtered indexed query");
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -79,6 +95,8 @@ void ray_query_kernel(std::conditional_t<INDEXED, IndexedQueryParams, QueryParam
     const bool nan_ray = __builtin_isnan(r.ox) | __builtin_isnan(r.oy) | __builtin_isnan(r.oz) | __builtin_isnan(r.dx) |
                          __builtin_isnan(r.dy) | __builtin_isnan(r.dz);
     const bool active = in_range && r.tmin <= r.tmax && !nan_ray;
+    std::conditional_t<FILTERED, RayFilter, NoFilter> flt;
+    if constexpr (FILTERED) flt = ray_filter(p.filter, i, in_range);
 
     SpillArray spill;
     Trav t;
@@ -86,19 +104,13 @@ void ray_query_kernel(std::conditional_t<INDEXED, IndexedQueryParams, QueryParam
     t.spill = spill;
     uint32_t steps[2] = {0u, 0u};
     Hit h = {0u, 0u, 0.f, 0.f};
-    const bool hit = trace_ray<PF, ANY>(p, r, h, t, active, steps);
+    const bool hit = trace_ray<PF, ANY>(p, r, h, t, active, steps, flt);
 
     if (in_range) {
         float4 o = {__builtin_inff(), __uint_as_float(RT_MISS), 0.f, 0.f};
         if (hit) {
-            // RotateAttributes: leaf corner k is the caller's corner i_k, so the caller's weights are W[i0] = 1-bu-bv,
-            // W[i1] = bu, W[i2] = bv, and (u, v) = (W[1], W[2])
             const uint32_t rot = p.leaves[h.tri_id >> 1].rotations[h.tri_id & 1];
-            const float w0 = 1 - h.bu - h.bv;
-            o.x = r.tmax;
-            o.y = __uint_as_float(h.primitive_id);
-            o.z = rot == 1 ? h.bv : (rot == 2 ? w0 : h.bu);
-            o.w = rot == 1 ? w0 : (rot == 2 ? h.bu : h.bv);
+            o = hit_record(r.tmax, h.primitive_id, h.bu, h.bv, rot);
         }
         p.hits[i] = o;
     }
@@ -151,28 +163,32 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const rt_camera* camer
     rays[2 * i + 1] = float4{r.dx, r.dy, r.dz, r.tmax};
 }
 
-hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
-                            uint32_t num_primitives, uint64_t* counters, hipStream_t st)
+static_assert(kQueryBlock == kTraceWaves * 64, "rt_launch.hpp: one lane per ray, kTraceWaves waves per workgroup");
+
+// the fields both launches fill (P: FilteredQueryParams or IndexedQueryParams)
+template <class P>
+static P query_params(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, uint64_t* counters)
 {
-    QueryParams p;
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
+    P p;
+    set_tree(p, as);
     p.rays = reinterpret_cast<const float4*>(rays);
     p.hits = reinterpret_cast<float4*>(hits);
     p.num_rays = num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    const uint32_t rays_per_block = kTraceWaves * 64;
-    const dim3 grid((uint32_t)(((uint64_t)num_rays + rays_per_block - 1) / rays_per_block)), block(rays_per_block);
-    const bool pf = num_primitives >= kPrefetchMinPrims;   // as launch_trace: trees that do not fit the caches
-    if (pf) {
-        if (any_hit) ray_query_kernel<true, true, false><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<true, false, false><<<grid, block, 0, st>>>(p);
-    } else {
-        if (any_hit) ray_query_kernel<false, true, false><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<false, false, false><<<grid, block, 0, st>>>(p);
-    }
+    return p;
+}
+
+hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
+                            uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, hipStream_t st)
+{
+    FilteredQueryParams p = query_params<FilteredQueryParams>(as, rays, hits, num_rays, counters);
+    if (filter) p.filter = filter_params(*filter);
+    const dim3 grid(query_blocks(num_rays)), block(kQueryBlock);
+    // pf as launch_trace: trees that do not fit the caches
+    dispatch_pf_any(num_primitives >= kPrefetchMinPrims, any_hit, [&](auto pf, auto any) {
+        if (filter) ray_query_kernel<pf(), any(), false, true><<<grid, block, 0, st>>>(p);
+        else ray_query_kernel<pf(), any(), false, false><<<grid, block, 0, st>>>(p);   // (its QueryParams part)
+    });
     return hipGetLastError();
 }
 
@@ -180,27 +196,13 @@ hipError_t launch_ray_query_indexed(const rt_accel& as, const rt_ray* rays, uint
                                     uint32_t num_indices, rt_hit* hits, bool any_hit, uint32_t num_primitives,
                                     uint64_t* counters, hipStream_t st)
 {
-    IndexedQueryParams p;
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
-    p.rays = reinterpret_cast<const float4*>(rays);
-    p.hits = reinterpret_cast<float4*>(hits);
-    p.num_rays = num_rays;
-    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    IndexedQueryParams p = query_params<IndexedQueryParams>(as, rays, hits, num_rays, counters);
     p.order = order;
     p.num_indices = num_indices;
-    const uint32_t rays_per_block = kTraceWaves * 64;
-    const dim3 grid((uint32_t)(((uint64_t)num_indices + rays_per_block - 1) / rays_per_block)), block(rays_per_block);
-    const bool pf = num_primitives >= kPrefetchMinPrims;   // as launch_ray_query
-    if (pf) {
-        if (any_hit) ray_query_kernel<true, true, true><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<true, false, true><<<grid, block, 0, st>>>(p);
-    } else {
-        if (any_hit) ray_query_kernel<false, true, true><<<grid, block, 0, st>>>(p);
-        else ray_query_kernel<false, false, true><<<grid, block, 0, st>>>(p);
-    }
+    const dim3 grid(query_blocks(num_indices)), block(kQueryBlock);
+    dispatch_pf_any(num_primitives >= kPrefetchMinPrims, any_hit, [&](auto pf, auto any) {
+        ray_query_kernel<pf(), any(), true, false><<<grid, block, 0, st>>>(p);
+    });
     return hipGetLastError();
 }
 

@@ -272,15 +272,32 @@ static inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_
 // a tree a query can walk: count = 0 is an empty tree, nothing is read through it
 static inline bool tree_args(const rt_accel* as) { return as && as->count <= 7 && (!as->count || (as->nodes && as->triangles)); }
 
+static_assert(sizeof(rt_ray_filter) == 8 && sizeof(rt_hit_filter) == 32, "rt_abi.h: the filter records' sizes");
+
+// the filter's own checks; no filter (the unfiltered entry points, a null pointer at the filtered ones) passes
+static inline bool filter_args(const rt_hit_filter* f)
+{
+    return !f || (!(f->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) && !misaligned(f->prim_masks, 4) &&
+                  !misaligned(f->per_ray, 8));
+}
+
+// An unfiltered ray query is its filtered entry point with no filter: one set of checks, and a null filter launches the
+// unfiltered kernel.
+int rt_intersect_rays_filtered(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
+                               uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, void* stream)
+{
+    if (!tree_args(as) || !rays || !hits || !filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_query(*as, rays, hits, num_rays, mode == RT_RAY_ANY_HIT, num_primitives, filter, counters,
+                                   static_cast<hipStream_t>(stream)));
+}
+
 int rt_intersect_rays(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
                       uint32_t num_primitives, uint64_t* counters, void* stream)
 {
-    if (!tree_args(as) || !rays || !hits) return RT_ERR_INVALID_ARGUMENT;
-    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (reinterpret_cast<uintptr_t>(hits) & 15u)) return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_query(*as, rays, hits, num_rays, mode == RT_RAY_ANY_HIT, num_primitives, counters,
-                                   static_cast<hipStream_t>(stream)));
+    return rt_intersect_rays_filtered(as, rays, hits, num_rays, mode, num_primitives, nullptr, counters, stream);
 }
 
 int rt_intersect_rays_indexed(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint32_t* order,
@@ -387,16 +404,23 @@ int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, c
                                            static_cast<hipStream_t>(stream)));
 }
 
-int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
-                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
-                                uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
-                                uint64_t* counters, void* stream)
+static_assert(sizeof(rt_instance_filter) == 8 && sizeof(rt_instance_ray_filter) == 16 && sizeof(rt_instance_hit_filter) == 32,
+              "rt_abi.h: the instance filter records' sizes");
+
+int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream)
 {
     if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
         misaligned(blas_table, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    // the filter's own checks (none: the unfiltered kernel)
+    if (filter && ((filter->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) ||
+                   misaligned(filter->per_instance, 8) || misaligned(filter->per_ray, 16)))
         return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
     InstanceQuery q;
@@ -412,7 +436,16 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
     q.any_hit = mode == RT_RAY_ANY_HIT;
     q.num_primitives = num_primitives;
     q.counters = counters;
-    return hip_rc(launch_instance_query(q, static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_instance_query(q, filter, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                uint64_t* counters, void* stream)
+{
+    return rt_intersect_rays_instanced_filtered(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids,
+                                                num_rays, mode, num_primitives, nullptr, counters, stream);
 }
 
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
@@ -474,126 +507,53 @@ int rt_k_nearest(const rt_accel* as, const rt_point_query* queries, uint32_t num
 
 size_t rt_ray_hits_scratch_bytes(uint32_t num_rays) { return ray_hits_scratch_bytes(num_rays); }
 
-int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
-                      uint64_t* counters, uint32_t* status, void* stream)
-{
-    if (!csr_args(as, rays, 16, true, offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
-    // (num_rays = 0 still launches the scan's one workgroup: offsets[0] = 0)
-    return hip_rc(launch_ray_hits_count(*as, rays, num_rays, offsets, scratch, counters, status, static_cast<hipStream_t>(stream)));
-}
-
-int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
-                        uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
-{
-    if (!csr_args(as, rays, 16, true, offsets, status) || !csr_collect_args(hits, 16, counts)) return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_hits_collect(*as, rays, num_rays, offsets, hits, counts, counters, status,
-                                          static_cast<hipStream_t>(stream)));
-}
-
-int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out, uint64_t* counters,
-                      uint32_t* status, void* stream)
-{
-    if (!tree_args(as) || !rays || !out) return RT_ERR_INVALID_ARGUMENT;
-    if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(rays, 16) || misaligned(out, 16) || misaligned(status, 4) || misaligned(counters, 8))
-        return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_first_hits(*as, rays, num_rays, k, out, counters, status, static_cast<hipStream_t>(stream)));
-}
-
-static_assert(sizeof(rt_ray_filter) == 8 && sizeof(rt_hit_filter) == 32, "rt_abi.h: the filter records' sizes");
-
-// the filter's own checks (the sibling's come first, from the sibling's own code path or its restatement below)
-static inline bool filter_args(const rt_hit_filter* f)
-{
-    return !(f->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) && !misaligned(f->prim_masks, 4) &&
-           !misaligned(f->per_ray, 8);
-}
-
-int rt_intersect_rays_filtered(const rt_accel* as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, int mode,
-                               uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, void* stream)
-{
-    if (!filter) return rt_intersect_rays(as, rays, hits, num_rays, mode, num_primitives, counters, stream);
-    if (!tree_args(as) || !rays || !hits || !filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
-    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(rays, 16) || misaligned(hits, 16)) return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_query_filtered(*as, rays, hits, num_rays, mode == RT_RAY_ANY_HIT, num_primitives, *filter, counters,
-                                            static_cast<hipStream_t>(stream)));
-}
-
-static_assert(sizeof(rt_instance_filter) == 8 && sizeof(rt_instance_ray_filter) == 16 && sizeof(rt_instance_hit_filter) == 32,
-              "rt_abi.h: the instance filter records' sizes");
-
-int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
-                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
-                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
-                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream)
-{
-    if (!filter)
-        return rt_intersect_rays_instanced(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays,
-                                           mode, num_primitives, counters, stream);
-    // the sibling's checks, restated, then the filter's own
-    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
-    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
-    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
-        misaligned(blas_table, 8))
-        return RT_ERR_INVALID_ARGUMENT;
-    if ((filter->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) || misaligned(filter->per_instance, 8) ||
-        misaligned(filter->per_ray, 16))
-        return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    InstanceQuery q;
-    q.tlas = *tlas;
-    q.records = records;
-    q.num_instances = num_instances;
-    q.blas_table = blas_table;
-    q.num_blas = num_blas;
-    q.rays = rays;
-    q.hits = hits;
-    q.instance_ids = instance_ids;
-    q.num_rays = num_rays;
-    q.any_hit = mode == RT_RAY_ANY_HIT;
-    q.num_primitives = num_primitives;
-    q.counters = counters;
-    return hip_rc(launch_instance_query_filtered(q, *filter, static_cast<hipStream_t>(stream)));
-}
-
 int rt_ray_hits_count_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
                                uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
 {
-    if (!filter) return rt_ray_hits_count(as, rays, num_rays, offsets, scratch, counters, status, stream);
     if (!csr_args(as, rays, 16, filter_args(filter), offsets, status) || !csr_count_args(scratch)) return RT_ERR_INVALID_ARGUMENT;
     // (num_rays = 0 still launches the scan's one workgroup: offsets[0] = 0)
-    return hip_rc(launch_ray_hits_count_filtered(*as, rays, num_rays, *filter, offsets, scratch, counters, status,
-                                                 static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_ray_hits_count(*as, rays, num_rays, filter, offsets, scratch, counters, status,
+                                        static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
+                      uint64_t* counters, uint32_t* status, void* stream)
+{
+    return rt_ray_hits_count_filtered(as, rays, num_rays, nullptr, offsets, scratch, counters, status, stream);
 }
 
 int rt_ray_hits_collect_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
                                  const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status,
                                  void* stream)
 {
-    if (!filter) return rt_ray_hits_collect(as, rays, num_rays, offsets, hits, counts, counters, status, stream);
     if (!csr_args(as, rays, 16, filter_args(filter), offsets, status) || !csr_collect_args(hits, 16, counts))
         return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_hits_collect_filtered(*as, rays, num_rays, *filter, offsets, hits, counts, counters, status,
-                                                   static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_ray_hits_collect(*as, rays, num_rays, filter, offsets, hits, counts, counters, status,
+                                          static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
+                        uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream)
+{
+    return rt_ray_hits_collect_filtered(as, rays, num_rays, nullptr, offsets, hits, counts, counters, status, stream);
 }
 
 int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
                                const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, void* stream)
 {
-    if (!filter) return rt_ray_first_hits(as, rays, num_rays, k, out, counters, status, stream);
     if (!tree_args(as) || !rays || !out || !filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
     if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(out, 16) || misaligned(status, 4) || misaligned(counters, 8))
         return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_first_hits_filtered(*as, rays, num_rays, k, *filter, out, counters, status,
-                                                 static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_ray_first_hits(*as, rays, num_rays, k, filter, out, counters, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out, uint64_t* counters,
+                      uint32_t* status, void* stream)
+{
+    return rt_ray_first_hits_filtered(as, rays, num_rays, k, nullptr, out, counters, status, stream);
 }
 
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }

@@ -88,6 +88,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int /*lane*/ 
     return (uint32_t)x;
 }
 
+// the hit record of an accepted triangle.  RotateAttributes: leaf corner k is the caller's corner i_k, so the caller's weights
+// are W[i0] = 1-bu-bv, W[i1] = bu, W[i2] = bv, and (u, v) = (W[1], W[2])
+__device__ __forceinline__ float4 hit_record(float t, uint32_t prim, float bu, float bv, uint32_t rot)
+{
+    const float w0 = 1 - bu - bv;
+    float4 o;
+    o.x = t;
+    o.y = __uint_as_float(prim);
+    o.z = rot == 1 ? bv : (rot == 2 ? w0 : bu);
+    o.w = rot == 1 ? w0 : (rot == 2 ? bu : bv);
+    return o;
+}
+
 // Workgroups are dealt to the 8 XCDs round-robin (b -> XCD b % 8; observed, speed only -- MI355X_MICROARCH.md, dispatch):
 // map workgroup b of nb to a work item such that XCD x gets the contiguous range [x * nb/8 ..).  A bijection on [0, nb).
 __device__ __forceinline__ uint32_t xcd_contiguous(uint32_t b, uint32_t nb)

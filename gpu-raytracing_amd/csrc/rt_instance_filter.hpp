@@ -1,8 +1,9 @@
 // rt_instance_filter.hpp -- the filter of rt_intersect_rays_instanced_filtered (rt_abi.h, instance-filter block; DESIGN
 // section 21): the kernel-side image of rt_instance_hit_filter and the per-lane policy InstanceRayFilter that trace_instanced
 // (rt_instance_traverse.hpp) asks at the TLAS leaf (enter), tells which instance it entered (set_instance) and hands, as `tri`,
-// to intersect_tri (rt_traverse.hpp) at its one acceptance point.
-// Device code only; force-inlined.
+// to intersect_tri (rt_traverse.hpp) at its one acceptance point.  Included by instances.hip, whose query kernel has a
+// FILTERED arm.
+// Device code, force-inlined; the one host function is instance_filter_params, the launch's conversion.
 #pragma once
 
 #include "rt_device.hpp"
@@ -16,6 +17,17 @@ struct InstanceFilterParams {
     const uint2* per_instance;    // rt_instance_filter = one uint2: (mask, flags)
     const uint4* per_ray;         // rt_instance_ray_filter = one uint4: (mask, skip_instance, skip_id, pad)
 };
+
+inline InstanceFilterParams instance_filter_params(const rt_instance_hit_filter& f)   // (host)
+{
+    InstanceFilterParams fp;
+    fp.flags = f.flags;
+    fp.ray_mask = f.ray_mask;
+    fp.num_filters = f.per_instance ? f.num_instance_filters : 0u;   // an absent array: nothing is read, every instance mask is all ones
+    fp.per_instance = reinterpret_cast<const uint2*>(f.per_instance);
+    fp.per_ray = reinterpret_cast<const uint4*>(f.per_ray);
+    return fp;
+}
 
 // The per-instance part of a lane's filter, the policy of intersect_tri inside the entered instance: the cull bits that act on
 // the OBJECT-space determinant (the call's bits, swapped when the instance shows the world its other side, 0 under

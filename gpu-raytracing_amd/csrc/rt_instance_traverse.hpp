@@ -1,5 +1,5 @@
-// rt_instance_traverse.hpp -- the two-level traversal of the instanced ray queries, shared by instances.hip
-// (rt_intersect_rays_instanced) and instance_filter_query.hip (rt_intersect_rays_instanced_filtered): the kernel parameters, the
+// rt_instance_traverse.hpp -- the two-level traversal of the instanced ray queries of instances.hip
+// (rt_intersect_rays_instanced and rt_intersect_rays_instanced_filtered, the two arms of one kernel): the kernel parameters, the
 // TLAS-aware box step and trace_instanced, the wave-level two-phase loop with its second level (what the second level adds to a
 // lane: instances.hip's header; DESIGN sections 9 and 21).  trace_instanced takes an instance-filter policy the way trace_ray
 // takes a hit-filter policy: with NoInstanceFilter the code is instance_query_kernel's, instruction for instruction.
@@ -16,7 +16,7 @@
 
 namespace rt {
 
-namespace {   // (as in the kernels' own files: every translation unit has its own copy, and its own kernel symbols)
+namespace {   // (as in the kernels' own file)
 
 constexpr uint32_t kTop = 0xFFFFFFFFu;              // "in the TLAS" (the lane's current instance)
 enum : uint32_t { PH_ENTER = 4, PH_EXIT = 5 };      // parked phases of the second level (PH_STEP .. PH_DONE: rt_traverse.hpp)

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "rt_abi.h"
 
@@ -181,9 +182,34 @@ struct TraceLaunch {
 };
 hipError_t launch_trace(const TraceLaunch& t, hipStream_t st);
 
-// ray_query.hip: rt_intersect_rays / rt_generate_camera_rays after their argument checks (num_rays > 0, w * h > 0)
+// ---- what the launches of the ray query families share (ray_query.hip, ray_hits_query.hip, ray_first_query.hip,
+// instances.hip).  Each of them takes a filter pointer: null launches the unfiltered instantiation of its kernel, anything
+// else (checked by the entry point: flags, alignments) the FILTERED one.
+constexpr uint32_t kQueryBlock = 256;   // one lane per ray, four waves per workgroup (the files assert it against kTraceWaves)
+inline uint32_t query_blocks(uint64_t n) { return (uint32_t)((n + kQueryBlock - 1) / kQueryBlock); }
+// the tree's four fields, which every params struct of these kernels begins with
+template <class P> inline void set_tree(P& p, const rt_accel& as)
+{
+    p.nodes = as.nodes;
+    p.leaves = as.triangles;
+    p.root = as.root;
+    p.count = as.count;
+}
+// the pair-prefetch x any-hit choice of a kernel instantiation: launch(pf, any) gets two std::bool_constant values
+template <class F> inline void dispatch_pf_any(bool pf, bool any_hit, F launch)
+{
+    if (pf) {
+        if (any_hit) launch(std::true_type(), std::true_type());
+        else launch(std::true_type(), std::false_type());
+    } else {
+        if (any_hit) launch(std::false_type(), std::true_type());
+        else launch(std::false_type(), std::false_type());
+    }
+}
+
+// ray_query.hip: rt_intersect_rays[_filtered] / rt_generate_camera_rays after their argument checks (num_rays > 0, w * h > 0)
 hipError_t launch_ray_query(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
-                            uint32_t num_primitives, uint64_t* counters, hipStream_t st);
+                            uint32_t num_primitives, const rt_hit_filter* filter, uint64_t* counters, hipStream_t st);
 hipError_t launch_camera_rays(const rt_camera* camera, uint32_t w, uint32_t h, uint32_t spp, bool tiled, rt_ray* rays,
                               hipStream_t st);
 
@@ -237,7 +263,8 @@ struct ShadeLaunch {
 };
 hipError_t launch_shade_frame(const ShadeLaunch& t, hipStream_t st);
 
-// instances.hip: rt_prepare_instances / rt_intersect_rays_instanced after their argument checks (the query: num_rays > 0)
+// instances.hip: rt_prepare_instances / rt_intersect_rays_instanced[_filtered] after their argument checks (the query:
+// num_rays > 0)
 hipError_t launch_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
                                     uint32_t num_blas, rt_triangle* proxies, rt_instance_record* records, uint32_t* status,
                                     hipStream_t st);
@@ -255,7 +282,7 @@ struct InstanceQuery {
     uint32_t num_primitives;
     uint64_t* counters;
 };
-hipError_t launch_instance_query(const InstanceQuery& q, hipStream_t st);
+hipError_t launch_instance_query(const InstanceQuery& q, const rt_instance_hit_filter* filter, hipStream_t st);
 
 // point_query.hip: rt_closest_points after its argument checks (num_queries > 0)
 hipError_t launch_point_query(const rt_accel& as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
@@ -279,34 +306,18 @@ hipError_t launch_range_collect(const rt_accel& as, const void* queries, uint32_
 hipError_t launch_knn_query(const rt_accel& as, const rt_point_query* queries, uint32_t num_queries, uint32_t k, rt_knn_hit* out,
                             uint64_t* counters, uint32_t* status, hipStream_t st);
 
-// ray_hits_query.hip: rt_ray_hits_count / rt_ray_hits_collect after their argument checks.  Count runs for num_rays = 0 too
-// (it writes offsets[0] = 0); collect is called with num_rays > 0.
+// ray_hits_query.hip: rt_ray_hits_count[_filtered] / rt_ray_hits_collect[_filtered] after their argument checks.  Count runs
+// for num_rays = 0 too (it writes offsets[0] = 0); collect is called with num_rays > 0.
 size_t ray_hits_scratch_bytes(uint32_t num_rays);   // uint64 per workgroup of 256 rays, 256-byte aligned
-hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint64_t* offsets, void* scratch,
-                                 uint64_t* counters, uint32_t* status, hipStream_t st);
-hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets,
-                                   rt_hit* hits, uint32_t* counts, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_ray_hits_count(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                                 uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st);
+hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter* filter,
+                                   const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters,
+                                   uint32_t* status, hipStream_t st);
 
-// ray_first_query.hip: rt_ray_first_hits after its argument checks (num_rays > 0, 1 <= k <= RT_RAY_FIRST_MAX_K)
-hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
-                                 uint64_t* counters, uint32_t* status, hipStream_t st);
-
-// ray_filter_query.hip: the filtered siblings of the four ray queries after their argument checks (the siblings' own, plus the
-// filter's flags and alignments); `filter` is never null here
-hipError_t launch_ray_query_filtered(const rt_accel& as, const rt_ray* rays, rt_hit* hits, uint32_t num_rays, bool any_hit,
-                                     uint32_t num_primitives, const rt_hit_filter& filter, uint64_t* counters, hipStream_t st);
-hipError_t launch_ray_hits_count_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter& filter,
-                                          uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, hipStream_t st);
-hipError_t launch_ray_hits_collect_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, const rt_hit_filter& filter,
-                                            const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters,
-                                            uint32_t* status, hipStream_t st);
-hipError_t launch_ray_first_hits_filtered(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
-                                          const rt_hit_filter& filter, rt_hit* out, uint64_t* counters, uint32_t* status,
-                                          hipStream_t st);
-
-// instance_filter_query.hip: rt_intersect_rays_instanced_filtered after its argument checks (the sibling's own, plus the
-// filter's flags and alignments; num_rays > 0); `filter` is never null here
-hipError_t launch_instance_query_filtered(const InstanceQuery& q, const rt_instance_hit_filter& filter, hipStream_t st);
+// ray_first_query.hip: rt_ray_first_hits[_filtered] after its argument checks (num_rays > 0, 1 <= k <= RT_RAY_FIRST_MAX_K)
+hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
+                                 const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, hipStream_t st);
 
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.

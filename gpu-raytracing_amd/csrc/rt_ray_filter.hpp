@@ -1,7 +1,8 @@
 // rt_ray_filter.hpp -- the hit filter of the filtered ray queries (rt_abi.h, hit-filter block): the
 // kernel-side image of rt_hit_filter and the per-lane policy RayFilter that intersect_tri / trace_ray (rt_traverse.hpp), the
-// all-hit loop (rt_ray_hits.hpp) and the first-K loop (rt_ray_first.hpp) ask at their one acceptance point.
-// Device code only; force-inlined.
+// all-hit loop (ray_hits_query.hip) and the first-K loop (ray_first_query.hip) ask at their one acceptance point.  Included by
+// ray_query.hip, ray_hits_query.hip and ray_first_query.hip, whose kernels have a FILTERED arm.
+// Device code, force-inlined; the one host function is filter_params, the launches' conversion.
 #pragma once
 
 #include "rt_device.hpp"
@@ -14,6 +15,17 @@ struct FilterParams {
     const uint32_t* prim_masks;
     const uint2* per_ray;         // rt_ray_filter = one uint2: (mask, skip_id)
 };
+
+inline FilterParams filter_params(const rt_hit_filter& f)   // (host)
+{
+    FilterParams fp;
+    fp.flags = f.flags;
+    fp.ray_mask = f.ray_mask;
+    fp.num_prims = f.prim_masks ? f.num_primitives : 0u;   // an absent array: nothing is read, every primitive mask is all ones
+    fp.prim_masks = f.prim_masks;
+    fp.per_ray = reinterpret_cast<const uint2*>(f.per_ray);
+    return fp;
+}
 
 // One lane's filter.  keep() orders its tests by cost: facing (a is in registers), the skip compare, then the one 4-byte
 // prim_masks load -- only for a candidate that survived everything else.
