@@ -5,7 +5,7 @@
 // waves (256 queries) per workgroup, xcd_chunk_block, the query in one 16-byte load, the nearest-first box step with 8-byte
 // (entry, boxdist2) stack entries (16 in an LDS column per lane, 48 private), pops re-culled against the current bound,
 // rt_traverse.hpp's wave-level two phases, a leaf in four 16-byte requests, the restart rule (a pass that dropped a push is
-// followed by another from the root, at most kKnnRestarts more), exact per-workgroup counters.  What differs: the lane keeps
+// followed by another from the root, at most kNearRestarts more), exact per-workgroup counters.  What differs: the lane keeps
 // the K best instead of one and prunes against the K-th.
 //   * bound = dist2_max while the list holds fewer than k entries, the k-th dist2 once it is full; a slot or a popped entry is
 //     skipped iff boxdist2 > bound;
@@ -40,8 +40,7 @@ namespace rt {
 
 namespace {
 
-constexpr int kKnnStackLds = 16;   // LDS-resident entries per lane: 16 x 8 B x 256 lanes = 32 KB per workgroup
-constexpr int kKnnRestarts = 2;    // passes from the root after a pass that dropped a push (each keeps the list so far)
+static_assert(kQueryBlock == kTraceWaves * 64, "rt_launch.hpp: one lane per query, kTraceWaves waves per workgroup");
 
 struct KnnParams {
     const rt_node* nodes;
@@ -54,14 +53,13 @@ struct KnnParams {
     uint32_t* status;
 };
 
-typedef uint64_t KnnEntry;   // entry (low word) | boxdist2 bits (high word)
-typedef KnnEntry KnnSpill[kStackMax - kKnnStackLds];
-typedef __attribute__((address_space(3))) KnnEntry lds_knn_entry;
+typedef NearEntry KnnSpill[kStackMax - kNearStackLds];
+typedef __attribute__((address_space(3))) NearEntry lds_knn_entry;
 
 __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p)
 {
     // the counters' workgroup sums reuse the stack's LDS once every lane is done with it (no extra bytes: 32 KB exactly)
-    __shared__ alignas(8) KnnEntry stack_lds[kTraceWaves][kKnnStackLds][64];
+    __shared__ alignas(8) NearEntry stack_lds[kTraceWaves][kNearStackLds][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
     const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
@@ -126,10 +124,10 @@ __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p
     auto next_from_stack = [&]() {
         while (sp > 0) {
             --sp;
-            const KnnEntry se = sp < kKnnStackLds ? col[sp * 64] : spill[sp - kKnnStackLds];
+            const NearEntry se = sp < kNearStackLds ? col[sp * 64] : spill[sp - kNearStackLds];
             if (__uint_as_float((uint32_t)(se >> 32)) <= bound) { cur = (uint32_t)se; return; }
         }
-        if (!overflow || restarts == kKnnRestarts) { live = false; return; }
+        if (!overflow || restarts == kNearRestarts) { live = false; return; }
         restarts++;
         overflow = false;
         cur = (p.root & kIndexMask) | (p.count << 29);
@@ -141,15 +139,9 @@ __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p
         // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (rt_traverse.hpp)
         asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
                           "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
-        offer(range_tri_d2(px, py, pz, unrotate(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                                __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                l2.w & 0xFFFFu)), l0.w);
+        offer(range_tri_d2(px, py, pz, leaf_tri_a(l0, l1, l2)), l0.w);
         if (l1.w == l0.w + 1u)                // a pair record: B = (v2, v1, v3) with rotations[1]
-            offer(range_tri_d2(px, py, pz, unrotate(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                    __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                    __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                                    l2.w >> 16)), l1.w);
+            offer(range_tri_d2(px, py, pz, leaf_tri_b(l1, l2, l3)), l1.w);
         next_from_stack();
     };
     auto box_step = [&]() {
@@ -165,14 +157,14 @@ __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p
             const float bd = box_d2(a, b, px, py, pz);
             const uint32_t e = slot_entry(a, b);
             if (bd > bound || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // pruned, or an empty run
-            KnnEntry pe = (uint64_t)e | ((uint64_t)__float_as_uint(bd) << 32);
+            NearEntry pe = (uint64_t)e | ((uint64_t)__float_as_uint(bd) << 32);
             if (bd < near_d) {                // the new nearest; the old one (if any) is pushed
                 pe = (uint64_t)near_e | ((uint64_t)__float_as_uint(near_d) << 32);
                 near_e = e; near_d = bd;
             }
             if ((uint32_t)pe != kNoNear) {
-                if (sp < kKnnStackLds) col[sp * 64] = pe;
-                else if (sp < kStackMax) spill[sp - kKnnStackLds] = pe;
+                if (sp < kNearStackLds) col[sp * 64] = pe;
+                else if (sp < kStackMax) spill[sp - kNearStackLds] = pe;
                 else overflow = true;         // dropped: this pass may miss one of the nearest
                 sp = min(sp + 1, kStackMax);
             }
@@ -203,22 +195,7 @@ __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p
 #endif
     }
     if (p.status && __builtin_amdgcn_ballot_w64(overflow) != 0 && lane == 0) atomicOr(p.status, (uint32_t)RT_KNN_STACK_OVERFLOW);
-    if (p.counters) {                         // (kernel argument: the same for every thread)
-        const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
-        unsigned long long* const csum = reinterpret_cast<unsigned long long*>(&stack_lds[0][0][0]);
-        __syncthreads();                      // every lane is done with its stack column
-        if (threadIdx.x < 2) csum[threadIdx.x] = 0ull;
-        __syncthreads();
-        if (lane == 0) {
-            atomicAdd(&csum[0], (unsigned long long)bsum);
-            atomicAdd(&csum[1], (unsigned long long)tsum);
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            const unsigned long long v = csum[threadIdx.x];
-            if (v) atomicAdd(&p.counters[threadIdx.x], v);
-        }
-    }
+    finish_counters(p.counters, reinterpret_cast<unsigned long long*>(&stack_lds[0][0][0]), lane, box_tests, tri_tests);
 }
 
 }  // namespace
@@ -227,18 +204,14 @@ hipError_t launch_knn_query(const rt_accel& as, const rt_point_query* queries, u
                             uint64_t* counters, uint32_t* status, hipStream_t st)
 {
     KnnParams p;
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
+    set_tree(p, as);
     p.queries = reinterpret_cast<const float4*>(queries);
     p.out = reinterpret_cast<uint2*>(out);
     p.num_queries = num_queries;
     p.k = k;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
     p.status = status;
-    const uint32_t per_block = kTraceWaves * 64;
-    const dim3 grid((uint32_t)(((uint64_t)num_queries + per_block - 1) / per_block)), block(per_block);
+    const dim3 grid(query_blocks(num_queries)), block(kQueryBlock);
     knn_query_kernel<<<grid, block, 0, st>>>(p);
     return hipGetLastError();
 }

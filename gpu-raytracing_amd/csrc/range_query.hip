@@ -21,7 +21,7 @@
 //   * COLLECT = true: the lane stores match j < offsets[i+1] - offsets[i] at ids[offsets[i] + j] -- its own segment, in its
 //     own traversal order, plain 4-byte vector stores, no atomics on the output -- and keeps counting beyond the room
 //     (counts[i], RT_RANGE_TRUNCATED).
-// d2, the corner un-rotation, boxdist2 and slot_entry live in rt_point_math.hpp (shared with knn_query.hip); the workgroup
+// d2, the corner un-rotation, boxdist2 and slot_entry live in rt_point_math.hpp (shared with the point queries); the workgroup
 // geometry, the limb scan and the segment prologue in rt_csr.hpp (shared with ray_hits_query.hip and tri_overlap_query.hip),
 // as does the epilogue csr_finish (shared with tri_overlap_query.hip).
 // Compiled with -ffp-contract=off and IEEE division: every float operation is the one rt_abi.h writes down.
@@ -201,10 +201,7 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
 RangeParams range_params(const rt_accel& as, const void* queries, uint32_t num_queries, uint64_t* counters, uint32_t* status)
 {
     RangeParams p = {};
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
+    set_tree(p, as);
     p.queries = reinterpret_cast<const float4*>(queries);
     p.num_queries = num_queries;
     p.counters = reinterpret_cast<unsigned long long*>(counters);

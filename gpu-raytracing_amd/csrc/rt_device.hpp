@@ -88,6 +88,28 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int /*lane*/ 
     return (uint32_t)x;
 }
 
+// the exact test counters of a query kernel whose workgroup sums reuse the stack's LDS (csum: its first 16 bytes) once every
+// lane is done with it: wave sums, an LDS sum per workgroup, then one device atomic per counter that is not 0.  Every thread of
+// the workgroup must call it (counters is a kernel argument: the same for every thread).
+__device__ __forceinline__ void finish_counters(unsigned long long* counters, unsigned long long* csum, int lane,
+                                                uint32_t box_tests, uint32_t tri_tests)
+{
+    if (!counters) return;
+    const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
+    __syncthreads();                          // every lane is done with its stack column
+    if (threadIdx.x < 2) csum[threadIdx.x] = 0ull;
+    __syncthreads();
+    if (lane == 0) {
+        atomicAdd(&csum[0], (unsigned long long)bsum);
+        atomicAdd(&csum[1], (unsigned long long)tsum);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned long long v = csum[threadIdx.x];
+        if (v) atomicAdd(&counters[threadIdx.x], v);
+    }
+}
+
 // the hit record of an accepted triangle.  RotateAttributes: leaf corner k is the caller's corner i_k, so the caller's weights
 // are W[i0] = 1-bu-bv, W[i1] = bu, W[i2] = bv, and (u, v) = (W[1], W[2])
 __device__ __forceinline__ float4 hit_record(float t, uint32_t prim, float bu, float bv, uint32_t rot)

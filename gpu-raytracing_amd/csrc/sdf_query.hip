@@ -7,11 +7,12 @@
 // (DIST) or one byte store (occupancy), no atomics on the output, exact per-workgroup counters, the status word through one
 // ballot per wave.  A lane runs its phases one after the other on ONE stack: the LDS column of the lane (16 slots) and one
 // private tail (48 slots) serve every phase.
-//   1. distance (DIST only): point_query_kernel's visiting order -- the k = 1 case of knn_query_kernel -- with the weight-free
-//      routines of rt_point_math.hpp (box_d2, unrotate, range_tri_d2): the nearest surviving slot next, the others pushed as
-//      8-byte (entry, boxdist2) entries, pops re-culled against the best, (dist2, id) kept in registers, ties to the lower id,
-//      a pass that dropped a push followed by at most kSdfRestarts more from the root.  Operation for operation the traversal
-//      of rt_closest_points, so (dist2, primitive_id) is that call's record bit for bit, overflowed passes included.
+//   1. distance (DIST only): point_query_kernel's descent -- the k = 1 case of knn_query_kernel -- with rt_point_math.hpp's
+//      routines and constants and d2 without the weights: the nearest surviving slot next, the others pushed as 8-byte
+//      (entry, boxdist2) entries, pops re-culled against the best, (dist2, id) kept in registers, ties to the lower id, a pass
+//      that dropped a push followed by at most kNearRestarts more from the root.  Operation for operation the traversal of
+//      rt_closest_points, so (dist2, primitive_id) is that call's record bit for bit, overflowed passes included
+//      (tests/test_gpu_sdf.py::test_overflowed_distance_equals_closest_points): a change to one text is a change to the other.
 //   2. parity, VOTES times: ray_hits_kernel<false>'s traversal without its scan.  The ray is (p, 0, D[j], +inf); slab() and
 //      intersect_tri() are rt_traverse.hpp's, unchanged, the window put back after every test; 4-byte entries, the first
 //      surviving slot visited next and the others pushed in slot order, a leaf in four 16-byte requests, B tested iff
@@ -38,10 +39,9 @@ namespace rt {
 
 namespace {
 
-// kSdfStackLds and kSdfRestarts mirror point_query.hip's kPtStackLds / kPtRestarts (and kCsrStackLds): the record equals
-// rt_closest_points's bit for bit, dropped pushes included, only while they stay equal
-constexpr int kSdfStackLds = 16;   // LDS-resident entries per lane (8 bytes each with DIST: 32 KB per workgroup; else 4: 16 KB)
-constexpr int kSdfRestarts = 2;    // distance passes from the root after a pass that dropped a push (rt_closest_points's rule)
+// both phases share one stack: kNearStackLds entries per lane in LDS (8 bytes each with DIST: 32 KB per workgroup; else 4:
+// 16 KB), the rest of kStackMax in the private tail
+static_assert(kQueryBlock == kTraceWaves * 64, "rt_launch.hpp: one lane per query, kTraceWaves waves per workgroup");
 constexpr int kSdfDistWaves = RT_SDF_DIST_WAVES;
 
 struct SdfParams {
@@ -57,8 +57,7 @@ struct SdfParams {
     float dirs[3 * RT_SDF_MAX_VOTES];
 };
 
-typedef uint64_t SdfEntry;   // distance phase: entry (low word) | boxdist2 bits (high word)
-typedef __attribute__((address_space(3))) SdfEntry lds_sdf_entry;
+typedef __attribute__((address_space(3))) NearEntry lds_sdf_entry;   // distance phase
 
 template <bool DIST, int VOTES>
 __global__ __launch_bounds__(kTraceWaves * 64, DIST ? kSdfDistWaves : RT_TRACE_MIN_WAVES + RT_TRACE_LEAN_EXTRA)
@@ -66,7 +65,8 @@ void sdf_kernel(SdfParams p)
 {
     // one slot per (wave, entry, lane), wide enough for the widest phase; the counters' workgroup sums reuse it at the end
     constexpr int kSlotWords = DIST ? 2 : 1;
-    __shared__ alignas(8) uint32_t stack_lds[kTraceWaves][kSdfStackLds][64 * kSlotWords];
+    static_assert(sizeof(NearEntry) == 2 * sizeof(uint32_t), "a distance-phase entry fills a slot of two words, in LDS and in the tail");
+    __shared__ alignas(8) uint32_t stack_lds[kTraceWaves][kNearStackLds][64 * kSlotWords];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
     const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
@@ -79,7 +79,7 @@ void sdf_kernel(SdfParams p)
     const bool finite_p = __builtin_isfinite(px) & __builtin_isfinite(py) & __builtin_isfinite(pz);
     const bool traced = in_range && finite_p && q.w >= 0.0f && p.count > 0;   // (q.w >= 0 is false for NaN)
 
-    uint32_t spill[(kStackMax - kSdfStackLds) * kSlotWords];   // the private tail: 8-byte entries in word pairs, 4-byte ones in words
+    uint32_t spill[(kStackMax - kNearStackLds) * kSlotWords];   // the private tail: 8-byte entries in word pairs, 4-byte ones in words
     uint32_t box_tests = 0, tri_tests = 0;
     bool flagged = false;             // RT_SDF_STACK_OVERFLOW for this query
     const uint32_t root_entry = (p.root & kIndexMask) | (p.count << 29);
@@ -98,12 +98,12 @@ void sdf_kernel(SdfParams p)
         auto next_from_stack = [&]() {
             while (sp > 0) {
                 --sp;
-                SdfEntry se;
-                if (sp < kSdfStackLds) se = col[sp * 64];
-                else se = (uint64_t)spill[2 * (sp - kSdfStackLds)] | ((uint64_t)spill[2 * (sp - kSdfStackLds) + 1] << 32);
+                NearEntry se;
+                if (sp < kNearStackLds) se = col[sp * 64];
+                else se = (uint64_t)spill[2 * (sp - kNearStackLds)] | ((uint64_t)spill[2 * (sp - kNearStackLds) + 1] << 32);
                 if (__uint_as_float((uint32_t)(se >> 32)) <= best) { cur = (uint32_t)se; return; }
             }
-            if (!overflow || restarts == kSdfRestarts) { live = false; return; }
+            if (!overflow || restarts == kNearRestarts) { live = false; return; }
             restarts++;
             overflow = false;
             cur = root_entry;
@@ -113,17 +113,11 @@ void sdf_kernel(SdfParams p)
             const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + (cur & kIndexMask));
             const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
             {
-                const float d = range_tri_d2(px, py, pz, unrotate(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                                                  __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                                  __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                                  l2.w & 0xFFFFu));
+                const float d = range_tri_d2(px, py, pz, leaf_tri_a(l0, l1, l2));
                 if (d < best || (d == best && l0.w < best_id)) { best = d; best_id = l0.w; }
             }
             if (l1.w == l0.w + 1u) {          // a pair record: B = (v2, v1, v3) with rotations[1]
-                const float d = range_tri_d2(px, py, pz, unrotate(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                                  __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                                  __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                                                  l2.w >> 16));
+                const float d = range_tri_d2(px, py, pz, leaf_tri_b(l1, l2, l3));
                 if (d < best || (d == best && l1.w < best_id)) { best = d; best_id = l1.w; }
             }
             next_from_stack();
@@ -148,10 +142,10 @@ void sdf_kernel(SdfParams p)
                     near_e = e; near_d = bd;
                 }
                 if (pe != kNoNear) {
-                    if (sp < kSdfStackLds) col[sp * 64] = (uint64_t)pe | ((uint64_t)__float_as_uint(pd) << 32);
+                    if (sp < kNearStackLds) col[sp * 64] = (uint64_t)pe | ((uint64_t)__float_as_uint(pd) << 32);
                     else if (sp < kStackMax) {
-                        spill[2 * (sp - kSdfStackLds)] = pe;
-                        spill[2 * (sp - kSdfStackLds) + 1] = __float_as_uint(pd);
+                        spill[2 * (sp - kNearStackLds)] = pe;
+                        spill[2 * (sp - kNearStackLds) + 1] = __float_as_uint(pd);
                     } else overflow = true;   // dropped: this pass may miss the nearest triangle
                     sp = min(sp + 1, kStackMax);
                 }
@@ -198,7 +192,7 @@ void sdf_kernel(SdfParams p)
         auto next_from_stack = [&]() {
             if (sp == 0) { live = false; return; }
             --sp;
-            cur = sp < kSdfStackLds ? col[sp * 64 * kSlotWords] : spill[sp - kSdfStackLds];
+            cur = sp < kNearStackLds ? col[sp * 64 * kSlotWords] : spill[sp - kNearStackLds];
         };
         auto test = [&](float c0x, float c0y, float c0z, float c1x, float c1y, float c1z, float c2x, float c2y, float c2z) {
             Hit h;
@@ -238,8 +232,8 @@ void sdf_kernel(SdfParams p)
                 const bool in = (back >= front) & (front <= tmax0) & (back >= r.tmin);
                 if (!in || (type != RT_CHILD_TRI && (e >> 29) == 0)) continue;   // missed by the ray, or an empty run
                 if (next == kNoNear) { next = e; continue; }   // the first survivor is visited next, the others wait
-                if (sp < kSdfStackLds) col[sp * 64 * kSlotWords] = e;
-                else if (sp < kStackMax) spill[sp - kSdfStackLds] = e;
+                if (sp < kNearStackLds) col[sp * 64 * kSlotWords] = e;
+                else if (sp < kStackMax) spill[sp - kNearStackLds] = e;
                 else overflow = true;         // dropped: what lies below it is not counted
                 sp = min(sp + 1, kStackMax);
             }
@@ -274,6 +268,7 @@ void sdf_kernel(SdfParams p)
         }
     }
     if (p.status && __builtin_amdgcn_ballot_w64(flagged) != 0 && lane == 0) atomicOr(p.status, (uint32_t)RT_SDF_STACK_OVERFLOW);
+    // (finish_counters of rt_device.hpp, written out: through the helper the VOTES = 3 kernels compiled to other code)
     if (p.counters) {                         // (kernel argument: the same for every thread)
         const uint32_t bsum = wave_sum_u32(box_tests), tsum = wave_sum_u32(tri_tests);
         unsigned long long* const csum = reinterpret_cast<unsigned long long*>(&stack_lds[0][0][0]);
@@ -331,10 +326,7 @@ hipError_t launch_sdf(const rt_accel& as, const rt_point_query* queries, uint32_
                       rt_sdf_hit* out, uint8_t* inside, uint64_t* counters, uint32_t* status, hipStream_t st)
 {
     SdfParams p = {};
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
+    set_tree(p, as);
     p.queries = reinterpret_cast<const float4*>(queries);
     p.out = reinterpret_cast<uint2*>(out);
     p.inside = inside;
@@ -342,8 +334,7 @@ hipError_t launch_sdf(const rt_accel& as, const rt_point_query* queries, uint32_
     p.counters = reinterpret_cast<unsigned long long*>(counters);
     p.status = status;
     for (uint32_t k = 0; k < 3 * votes; k++) p.dirs[k] = dirs[k];
-    const uint32_t per_block = kTraceWaves * 64;
-    const dim3 grid((uint32_t)(((uint64_t)num_queries + per_block - 1) / per_block)), block(per_block);
+    const dim3 grid(query_blocks(num_queries)), block(kQueryBlock);
     if (votes == 1) sdf_kernel<DIST, 1><<<grid, block, 0, st>>>(p);
     else sdf_kernel<DIST, RT_SDF_MAX_VOTES><<<grid, block, 0, st>>>(p);
     return hipGetLastError();

@@ -274,10 +274,7 @@ TriOverlapParams tri_params(const rt_accel& as, const rt_triangle* queries, uint
                             uint32_t* status)
 {
     TriOverlapParams p = {};
-    p.nodes = as.nodes;
-    p.leaves = as.triangles;
-    p.root = as.root;
-    p.count = as.count;
+    set_tree(p, as);
     p.queries = reinterpret_cast<const float*>(queries);
     p.num_queries = num_queries;
     p.counters = reinterpret_cast<unsigned long long*>(counters);

@@ -301,6 +301,35 @@ def test_stack_overflow_is_flagged(rt):
         assert (r.ctr_sdf[:2] == c["counters"]).all()
 
 
+def test_overflowed_distance_equals_closest_points(rt):
+    """(|sdist|, primitive_id) is rt_closest_points's record also where pushes were dropped: the deep comb (80 pending entries
+    against 64 slots), where every pass of both calls drops pushes and the record depends on which ones.  The sign and the
+    occupancy byte are not compared: the parity rays overflow too, and their counts are lower bounds."""
+    import torch
+    rng = np.random.default_rng(5)
+    n = 70                                        # ends inside the second wave
+    q = sr.queries(rng.uniform(-0.05, 0.05, (n, 3)).astype(F))
+    L = 80
+    nodes, leaves = _comb(rt, L, rng)
+    tree = (rt.to_device(leaves), rt.to_device(nodes), 0, 2)
+    hits = torch.full((n, 4), np.nan, dtype=torch.float32, device="cuda")
+    st = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rt.ClosestPoints(*tree, _dev_queries(rt, q), hits, status=st)
+    h = hits.cpu().numpy().view(rt.POINT_HIT).reshape(-1)
+    cp_over = bool(rt.point_status(st) & rt.RT_POINT_STACK_OVERFLOW)
+    cp_miss = h["primitive_id"] == rt.MISS
+    assert cp_over, "the comb is meant to overflow the distance traversal"
+    assert (~cp_miss).any() and (h["primitive_id"][~cp_miss] <= L).all()
+    with np.errstate(invalid="ignore"):
+        cp_dist = np.where(cp_miss, F(np.inf), np.sqrt(h["dist2"], dtype=F)).astype(F)
+    for votes in (1, 3):
+        r = _run(rt, tree, q, votes)
+        assert (r.prim == h["primitive_id"]).all()
+        assert ((r.prim == rt.MISS) == cp_miss).all()
+        assert (_bits(np.abs(r.sdist)) == _bits(cp_dist)).all()
+        assert bool(r.st_sdf & rt.RT_SDF_STACK_OVERFLOW) == cp_over
+
+
 # ------------------------------------------------------------------ 7: refit
 def _scale_shear(tris):
     """per vertex, from its float32 bits alone: shared vertices stay shared, the mesh stays closed"""

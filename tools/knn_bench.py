@@ -11,6 +11,7 @@ An arm is one build of the library (RT_KNN_LIST of csrc/knn_query.hip): the ship
 Each arm runs in a child process of its own (a process binds one library), one after the other:
   python tools/knn_bench.py --arms private=gpu-raytracing_amd/csrc/librt_amd.so row=gpu-raytracing_amd/csrc/librt_amd_knn_row.so \
       [--iters 30] [--warmup 5] [--out profiles/knn_bench.json]
+Without --arms the one arm is the shipped library, or the build that RT_LIB=<path> names.
 The parent merges the children's results, requires rows_sha1 to agree across arms for every (tree, set, k), and adds per arm
 the ratios the design discussion needs: k = 1 time / rt_closest_points time, and time and box tests relative to k = 1."""
 import argparse
@@ -111,7 +112,9 @@ def main():
     if a.lib:
         run_arm(a)
         return
-    arms = dict(s.split("=", 1) for s in a.arms) or {"shipped": os.path.join(ROOT, "gpu-raytracing_amd", "csrc", "librt_amd.so")}
+    # without --arms: the shipped library, or the build RT_LIB names (tools/point_query_bench.py's override)
+    shipped = os.environ.get("RT_LIB") or os.path.join(ROOT, "gpu-raytracing_amd", "csrc", "librt_amd.so")
+    arms = dict(s.split("=", 1) for s in a.arms) or {"shipped": shipped}
     got = {}
     for name, lib in arms.items():      # one child at a time: each opens the GPU, measures, and exits
         cmd = [sys.executable, os.path.abspath(__file__), "--lib", lib, "--iters", str(a.iters), "--warmup", str(a.warmup),

@@ -10,9 +10,9 @@ Each launch is timed alone between two device events (warm-up first, then --iter
 query come from one further launch with counters.  For comparison the tiled closest-hit camera rays (camera A, 1920 x 1080)
 through rt_intersect_rays on the same LBVH tree, timed the same way.
 Usage: python tools/point_query_bench.py [--iters 30] [--warmup 5] [--grid 708] [--out profiles/point_query_bench.json]
-RT_LIB=<path>: time an experiment build of the library instead (e.g. the RT_POINT_PHASED / RT_POINT_DIST_STACK arms of
-csrc/point_query.hip, built with `make librt_amd_exp.so EXPFLAGS=...`).  Kernel times per tree and set from a rocprofv3 run of
-this tool: tools/point_query_kstats.py."""
+RT_LIB=<path>: time another build of the library instead (an experiment build made with `make librt_amd_exp.so EXPFLAGS=...`,
+or another commit's library: DESIGN, "What the point queries share").  Kernel times per tree and set from a rocprofv3
+run of this tool: tools/point_query_kstats.py."""
 import argparse
 import hashlib
 import importlib

@@ -17,7 +17,8 @@ the live points -- the only evidence of how often a non-watertight edge crossing
   third_cast_share     the first two votes disagree (the fused kernel casts the third for exactly these)
   not_unanimous_share  the three parities are not all equal
 Usage: python tools/sdf_bench.py [--iters 30] [--warmup 5] [--cells 289] [--lattice 128] [--near 2000000]
-                                 [--out profiles/sdf_bench.json]"""
+                                 [--out profiles/sdf_bench.json]
+RT_LIB=<path>: time another build of the library instead (tools/point_query_bench.py's override)."""
 import argparse
 import importlib
 import json
@@ -60,6 +61,8 @@ def main():
     a = ap.parse_args()
     import torch
     rt = importlib.import_module("gpu-raytracing_amd")
+    if os.environ.get("RT_LIB"):
+        rt.LIB_PATH = os.path.abspath(os.environ["RT_LIB"])
     scenes = importlib.import_module("gpu-raytracing_amd.scenes")
     tris = scenes.noisy_sphere(a.cells, 1)
     V = tris.reshape(-1, 3)
