@@ -141,6 +141,43 @@ __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, f
 #define RT_TRACE_QUAD_WAIT_SECOND 0
 #endif
 
+// The lean vote (trace_ray<.., QW = true> only).  A vote under which no unfinished lane has more than kStackLds - kLeanMargin
+// entries on its stack is LEAN: the pushes and pops of its box steps -- and of the leaf phase that follows it, if the vote ends
+// the box phase -- go straight to the LDS column, with no sp < kStackLds ladder, no private array and no kStackMax clamp.  Any
+// other vote runs the full ladders.  The test is one compare and one ballot per vote, wave-uniform; stack content and sp are
+// the same object either way, so a wave may change arm at every vote, and no ray's sequence of tests depends on the arm.
+// The margin: a lean push at sp writes lds[sp * 64], so every push under the vote must find sp <= kStackLds - 1.  A box step
+// on a pair of a fresh node has no near child yet: the first Box hit becomes `near`, the second is pushed -- at most ONE
+// push.  A pair of a node of more than two slots may start with `near` set: both hits push -- at most TWO.  advance() only
+// pops.  A vote runs two box steps, so a lane that starts it at sp pushes at levels sp .. sp + 3 at most: sp + 3 <=
+// kStackLds - 1.  A vote that ends the box phase runs no box step; the leaf phase's second_slot pushes at most one entry, at
+// level sp: covered by the same bound.  Hence kLeanMargin = 2 steps x 2 pushes = 4, and a lean vote never sees sp above
+// kStackLds (< kStackMax: its pops always read LDS).
+// RT_TRACE_LEAN_STEP picks how the two arms are compiled (profiles/lean_step_bench.txt):
+//   2 (shipped)  ONE loop; each push / pop site takes a scalar branch on the vote's flag (`lean`) to its LDS-only form
+//                or to its ladder: -3.1 % issued instructions, +1.6 % on the headline;
+//   1            TWO copies of the vote's steps, one all-lean (no `keep` term either), one all-full, chosen per vote: the
+//                lean copy is 19 % shorter, but the compiler keeps the lanes' state in different registers in the two copies
+//                and moves it across at every vote (26 v_mov): +5.8 % issued instructions, -1.9 %;
+//   0            every vote runs the full ladders: the loop before this knob.
+#ifndef RT_TRACE_LEAN_STEP
+#define RT_TRACE_LEAN_STEP 2
+#endif
+constexpr int kLeanStep = RT_TRACE_LEAN_STEP;
+constexpr int kLeanMargin = 4;
+// Trims, each its own compile-time arm (tools/lean_step_arms.sh), both measured on RT_TRACE_LEAN_STEP = 1 and left off:
+// RT_TRACE_LEAN_SELECT = 1: the lean copy's advance() as selects instead of branches that re-materialise cur / near_e /
+// near_d / phase at their joins (-0.9 %).  RT_TRACE_HOLD_VECTOR = 1: quad_hold's combine in vector operations instead of
+// 64-bit scalar masks (no difference: four v_cmp -> v_cndmask pairs cost what the scalar ladder did).
+#ifndef RT_TRACE_LEAN_SELECT
+#define RT_TRACE_LEAN_SELECT 0
+#endif
+constexpr bool kLeanSelect = RT_TRACE_LEAN_SELECT != 0;
+#ifndef RT_TRACE_HOLD_VECTOR
+#define RT_TRACE_HOLD_VECTOR 0
+#endif
+static_assert(kLeanMargin <= kStackLds, "the lean vote's threshold is a stack level");
+
 // per-lane traversal state.  PH_STEP_POP (QW traversals only): PH_STEP whose cur was popped from the stack, from level sp.
 enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3, PH_STEP_POP = 4 };
 constexpr uint32_t kNoNear = 0xFFFFFFFFu;  // "no Box child hit yet" (child 2^29-1, count 7: not a real entry)
@@ -166,8 +203,12 @@ struct Trav {
     // loads, issued as soon as advance() has picked it -- before the wave's next vote -- and carried in registers
     uint4 pf0, pf1, pf2, pf3;
 
-    __device__ __forceinline__ void push(uint32_t e)
+    // LEAN (here and below; kLeanMargin): 0 the full ladders, 1 the lean form, 2 the site picks by `lean`, the vote's wave-uniform flag
+    template <int LEAN = 0>
+    __device__ __forceinline__ void push(uint32_t e, bool lean = false)
     {
+        if constexpr (LEAN == 1) { lds[sp * 64] = e; sp++; return; }
+        if (LEAN == 2 && lean) { lds[sp * 64] = e; sp++; return; }
         if (sp < kStackLds) lds[sp * 64] = e;
         else if (sp < kStackMax) spill[sp - kStackLds] = e;
         sp = min(sp + 1, kStackMax);  // a push onto a full stack is dropped (the reference overruns its array, Tracer.cu:353-369)
@@ -175,10 +216,11 @@ struct Trav {
     // A Box child (Tracer.cu:338-363), predicated on `in`: the first hit becomes `near`; a closer one (ties:
     // larger child index) displaces `near` onto the stack; otherwise it is pushed itself.  Bitwise logic on
     // purpose (no short-circuit branches); with no near yet near_d = +inf makes every hit "closer".
-    __device__ __forceinline__ void inner_hit(bool in, uint32_t e, float front)
+    template <int LEAN = 0>
+    __device__ __forceinline__ void inner_hit(bool in, uint32_t e, float front, bool lean = false)
     {
         const bool closer = (front < near_d) | ((front == near_d) & ((e & kIndexMask) > (near_e & kIndexMask)));
-        if (in & (near_e != kNoNear)) push(closer ? near_e : e);
+        if (in & (near_e != kNoNear)) push<LEAN>(closer ? near_e : e, lean);
         const bool take = in & closer;
         near_e = take ? e : near_e;
         near_d = take ? front : near_d;
@@ -187,29 +229,44 @@ struct Trav {
     // the nearest child (the reference pushes it last and pops it first -- so on a FULL stack that push is dropped
     // like any other and the entry below it is popped instead: same rule as the oracle), else a popped entry, else done
     // QW: a popped cur is marked (PH_STEP_POP); the lane is in PH_STEP when it gets here.
-    template <bool QW = false>
-    __device__ __forceinline__ void advance()
+    template <bool QW = false, int LEAN = 0>
+    __device__ __forceinline__ void advance(bool lean = false)
     {
         const uint32_t cnt = cur >> 29;
+        if constexpr (LEAN == 1 && kLeanSelect) {
+            // the same four-way choice as selects on cur / near_e / near_d / phase, which are live anyway; only the pop,
+            // which reads LDS, stays a branch
+            const bool more = cnt > 2, keep = near_e != kNoNear;
+            const bool pop = !more & !keep & (sp != 0);
+            cur = more ? ((cur & kIndexMask) + 2) | ((cnt - 2) << 29) : (keep ? near_e : cur);
+            phase = (more | keep | pop) ? phase : (uint32_t)PH_DONE;
+            near_e = more ? near_e : kNoNear;
+            near_d = more ? near_d : __builtin_inff();
+            if (pop) { --sp; cur = lds[sp * 64]; if constexpr (QW) phase = PH_STEP_POP; }
+            return;
+        }
         if (cnt > 2) { cur = ((cur & kIndexMask) + 2) | ((cnt - 2) << 29); return; }
-        const bool keep = (near_e != kNoNear) & (sp < kStackMax);
+        const bool keep = LEAN == 1 ? near_e != kNoNear : (near_e != kNoNear) & (sp < kStackMax);
         if (keep) cur = near_e;
         else if (sp == 0) phase = PH_DONE;
         else {
-            --sp; cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds];
+            --sp;
+            if (LEAN == 1 || (LEAN == 2 && lean)) cur = lds[sp * 64];
+            else cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds];
             if constexpr (QW) phase = PH_STEP_POP;
         }
         near_e = kNoNear;
         near_d = __builtin_inff();
     }
     // second slot of the pair, evaluated with the CURRENT tmax (after any leaf hit of the first slot)
-    __device__ __forceinline__ void second_slot(float tmin, float tmax)
+    template <int LEAN = 0>
+    __device__ __forceinline__ void second_slot(float tmin, float tmax, bool lean = false)
     {
         const bool valid = t1 != RT_CHILD_NONE;
         const bool hit = valid & (k1 >= f1) & (f1 <= tmax) & (k1 >= tmin);
         box_tests += valid ? 1u : 0u;
         const bool is_leaf = hit & (t1 == RT_CHILD_TRI);
-        inner_hit(hit & !is_leaf, e1, f1);
+        inner_hit<LEAN>(hit & !is_leaf, e1, f1, lean);
         if (is_leaf) { leaf = e1; phase = PH_LEAF1; }
     }
 };
@@ -242,9 +299,9 @@ __device__ __forceinline__ void prefetch_pair(const Params& p, Trav& t)
 // The tests of one box step on a fetched pair (Tracer.cu:323-352 for one pair): both slabs are computed before the ordered
 // tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.  `two`: the pair has a second slot
 // (else a1 / b1 repeat the first).
-template <bool PF, bool QW = false, class Params>
+template <bool PF, bool QW = false, int LEAN = 0, class Params>
 __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0,
-                                            const uint4& a1, const uint4& b1)
+                                            const uint4& a1, const uint4& b1, bool lean = false)
 {
     if constexpr (QW) t.phase = PH_STEP;   // (PH_STEP_POP: the popped entry is being stepped on)
     float f0, k0;
@@ -258,17 +315,17 @@ __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav&
     const bool hit0 = valid0 & (k0 >= f0) & (f0 <= r.tmax) & (k0 >= r.tmin);
     t.box_tests += valid0 ? 1u : 0u;
     const bool leaf0 = hit0 & (type0 == RT_CHILD_TRI);
-    t.inner_hit(hit0 & !leaf0, e0, f0);
+    t.template inner_hit<LEAN>(hit0 & !leaf0, e0, f0, lean);
     if (leaf0) { t.leaf = e0; t.phase = PH_LEAF0; }
     else {
-        t.second_slot(r.tmin, r.tmax);
-        if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
+        t.template second_slot<LEAN>(r.tmin, r.tmax, lean);
+        if (t.phase == PH_STEP) { t.template advance<QW, LEAN>(lean); prefetch_pair<PF>(p, t); }
     }
 }
 
 // One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
-template <bool PF, bool QW = false, class Params>
-__device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
+template <bool PF, bool QW = false, int LEAN = 0, class Params>
+__device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t, bool lean = false)
 {
     const uint32_t cnt = t.cur >> 29;
     const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
@@ -286,7 +343,7 @@ __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t)
         __builtin_amdgcn_sched_barrier(0);
 #endif
     }
-    box_step_on<PF, QW>(p, r, t, two, a0, b0, a1, b1);
+    box_step_on<PF, QW, LEAN>(p, r, t, two, a0, b0, a1, b1, lean);
 }
 
 // Hold at pop, evaluated by the WHOLE wave (it reads its quad-mates' registers through DPP, and a switched-off lane's registers
@@ -317,10 +374,28 @@ __device__ __forceinline__ bool quad_hold(const Trav& t)
         typedef __attribute__((address_space(3))) lds_u32x4 lds_quad;
         // (the stack array is 16-byte aligned and a quad's four columns share one 16-byte group: rounding the lane's own column down finds it)
         const lds_u32x4 e = *(const lds_quad*)(((uintptr_t)t.lds & ~(uintptr_t)15) + (uintptr_t)t.sp * 256u);
+#if RT_TRACE_HOLD_VECTOR
+        // (a key is an sp, never negative: a mate without the entry counts as key 0, which no sp is below)
+        hold = max(max(e.x == t.cur ? k0 : 0, e.y == t.cur ? k1 : 0), max(e.z == t.cur ? k2 : 0, e.w == t.cur ? k3 : 0)) > t.sp;
+#else
         hold = ((k0 > t.sp) & (e.x == t.cur)) | ((k1 > t.sp) & (e.y == t.cur)) | ((k2 > t.sp) & (e.z == t.cur)) |
                ((k3 > t.sp) & (e.w == t.cur));
+#endif
     }
     return hold;
+}
+
+// The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held).  LEAN / lean: the vote's arm.
+template <bool PF, bool ANY, int LEAN, class Params>
+__device__ __forceinline__ void quad_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
+{
+    if (go) box_step<PF, true, LEAN>(p, r, t, lean);
+    // second step under the same vote
+#if RT_TRACE_QUAD_WAIT_SECOND
+    if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true, LEAN>(p, r, t, lean);
+#else
+    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, LEAN>(p, r, t, lean);
+#endif
 }
 
 // The same step for the lanes that sit on the pair `c` (packed like Trav::cur), c WAVE-UNIFORM: the pair's 64 bytes are read
@@ -380,7 +455,8 @@ __device__ __forceinline__ bool box_step_wave(const Params& p, const Ray& r, Tra
 // closest-hit one, step for step.  Params: anything with nodes, leaves, root, count, park_num, park_den.
 // Filter: the hit-filter policy handed to every leaf test (NoFilter: none).
 // QW: hold at pop (quad_hold above): a held lane stays in its phase and sits out the vote's first box step; the vote counts the
-// lanes that will really step.  t.lds must then be a column of a 16-byte aligned [kStackLds][64] array.
+// lanes that will really step.  t.lds must then be a column of a 16-byte aligned [kStackLds][64] array.  Each vote of a QW
+// traversal is also lean or full (kLeanMargin above).
 template <bool PF, bool ANY = false, bool QW = false, class Params, class Filter = NoFilter>
 __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav& t, bool active, uint32_t* steps,
                                           Filter flt = Filter())
@@ -400,6 +476,7 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
     prefetch_pair<PF>(p, t);
     bool tri_hit = false;
     uint32_t nbox = 0, nleaf = 0;
+    bool lean = false;    // wave-uniform, QW only: the last vote was a lean one (kLeanMargin)
     bool shared = true;   // wave-uniform; kUniformSticky: the ray's steps look for shared pairs until one step finds too many
 #ifdef RT_EXP_UNIFORM_STATS
     uint32_t ustat[4] = {0, 0, 0, 0};
@@ -413,16 +490,17 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 const bool go = ((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t);
                 stepping = __builtin_amdgcn_ballot_w64(go);
                 parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
+                // the lean vote (kLeanMargin): no unfinished lane within the margin of its LDS column's end.  (A finished
+                // closest-hit lane has sp = 0; an any-hit lane may finish on a non-empty stack.)
+                if constexpr (kLeanStep != 0)
+                    lean = __builtin_amdgcn_ballot_w64((t.sp > kStackLds - kLeanMargin) & !(ANY && t.phase == PH_DONE)) == 0;
                 // (held lanes counted on the stepping side of this threshold instead: measured, no different -- DESIGN section 5)
                 if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
                 nbox += 2;
-                if (go) box_step<PF, true>(p, r, t);
-                // second step under the same vote
-#if RT_TRACE_QUAD_WAIT_SECOND
-                if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true>(p, r, t);
-#else
-                if ((t.phase & 3u) == PH_STEP) box_step<PF, true>(p, r, t);
-#endif
+                if constexpr (kLeanStep == 1) {
+                    if (lean) quad_vote_steps<PF, ANY, 1>(p, r, t, go, true);
+                    else quad_vote_steps<PF, ANY, 0>(p, r, t, go, false);
+                } else quad_vote_steps<PF, ANY, kLeanStep>(p, r, t, go, lean);
                 continue;
             }
             stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
@@ -486,8 +564,16 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
             } else {
                 const bool was_first = t.phase == PH_LEAF0;
                 t.phase = PH_STEP;
-                if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
+                if (QW && kLeanStep == 1 && lean) {   // (the vote that ended the box phase was lean: a parked lane is outside the margin)
+                    if (was_first) t.template second_slot<1>(r.tmin, r.tmax);
+                    if (t.phase == PH_STEP) t.template advance<QW, 1>();
+                } else if constexpr (QW && kLeanStep == 2) {
+                    if (was_first) t.template second_slot<2>(r.tmin, r.tmax, lean);
+                    if (t.phase == PH_STEP) t.template advance<QW, 2>(lean);
+                } else {
+                    if (was_first) t.second_slot(r.tmin, r.tmax);
+                    if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
+                }
             }
         }
     }
