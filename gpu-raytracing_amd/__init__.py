@@ -60,6 +60,7 @@ kClosestHit, kAnyHit = 0, 1
 kRaysRowMajor, kRaysTiled = 0, 1
 # refit status flags (rt_refit_plan_layout.status)
 RT_REFIT_BAD_TREE, RT_REFIT_PLAN_MISMATCH, RT_REFIT_PAIR_BROKEN = 1, 2, 4
+RT_MOTION_TOPOLOGY_MISMATCH = 1    # rt_motion_validate's status flag
 # instancing (rt_prepare_instances / rt_intersect_rays_instanced)
 INSTANCE = np.dtype([("object_to_world", "<f4", (3, 4)), ("blas", "<u4"), ("pad", "<u4", 3)])                # 64 B
 INSTANCE_RECORD = np.dtype([("world_to_object", "<f4", (3, 4)), ("blas", "<u4"), ("flags", "<u4"), ("spare", "<u4", 2)])
@@ -181,6 +182,11 @@ class _InstanceHitFilter(ctypes.Structure):  # rt_instance_hit_filter
                 ("pad", ctypes.c_uint32), ("per_instance", ctypes.c_void_p), ("per_ray", ctypes.c_void_p)]
 
 
+class _MotionAccel(ctypes.Structure):  # rt_motion_accel
+    _fields_ = [("triangles0", ctypes.c_void_p), ("nodes0", ctypes.c_void_p), ("triangles1", ctypes.c_void_p),
+                ("nodes1", ctypes.c_void_p), ("root", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
 class _RefitPlanLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
                 ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
@@ -191,7 +197,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_calculate_scene_aabb", "rt_generate_morton_codes", "rt_radix_sort_scratch_bytes",
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
-           "rt_build_refit_plan", "rt_refit", "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
+           "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
+           "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
@@ -263,6 +270,10 @@ def lib() -> ctypes.CDLL:
     L.rt_build_refit_plan.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
     L.rt_refit.restype = i32
     L.rt_refit.argtypes = [ctypes.POINTER(_BuildInput), u32, u32, vp, vp]
+    L.rt_motion_validate.restype = i32
+    L.rt_motion_validate.argtypes = [ctypes.POINTER(_MotionAccel), u32, vp, vp]
+    L.rt_intersect_rays_motion.restype = i32
+    L.rt_intersect_rays_motion.argtypes = [ctypes.POINTER(_MotionAccel), vp, vp, vp, u32, i32, vp, vp]
     L.rt_prepare_instances.restype = i32
     L.rt_prepare_instances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     L.rt_intersect_rays_instanced.restype = i32
@@ -609,6 +620,65 @@ def refit_status(plan, num_triangles: int) -> int:
     """The plan's RT_REFIT_* flags (copies the status word back: waits for the work queued before it on the current stream).
     Sticky: BuildRefitPlan clears them, every Refit only adds to them."""
     return int(to_host(plan, np.uint32, 1, refit_plan_layout(num_triangles).status)[0])
+
+
+def MotionPose(inp: BuildInput, root: int, count: int, moved_triangles):
+    """The second key pose of a motion query: clones inp.triangles_out / inp.nodes_out (the built tree, pose 0), builds a refit
+    plan on the clone (a plan fingerprints its nodes_out) and refits it with `moved_triangles` (the same triangles in the same
+    order, moved: a numpy [n, 9] array or a device buffer of TRIANGLE records).  Returns (pose 1 as a BuildInput whose
+    triangles_in holds the moved triangles, its plan): Refit(pose1, root, count, plan) moves it again.  The plan's status
+    (refit_status) must be 0.  On a split tree refit pose 0 with its own triangles first (rt_abi.h, motion block).
+    Asynchronous on the current stream; composes BuildRefitPlan and Refit."""
+    moved = moved_triangles if hasattr(moved_triangles, "data_ptr") else \
+        to_device(np.ascontiguousarray(moved_triangles, np.float32).reshape(-1, 9), inp.nodes_out.device)
+    pose1 = BuildInput(triangles_in=moved, triangles_out=inp.triangles_out.clone(), num_triangles=inp.num_triangles,
+                       nodes_out=inp.nodes_out.clone(), scratch=inp.scratch)
+    plan = device_bytes(RefitPlanBytes(inp.num_triangles), inp.nodes_out.device)
+    BuildRefitPlan(pose1, root, count, plan)
+    Refit(pose1, root, count, plan)
+    return pose1, plan
+
+
+def _pose(pose):
+    """(triangles, nodes) of a key pose given as such a pair or as a BuildInput"""
+    return (pose.triangles_out, pose.nodes_out) if isinstance(pose, BuildInput) else pose
+
+
+def _motion_accel(pose0, pose1, root: int, count: int) -> _MotionAccel:
+    (t0, n0), (t1, n1) = _pose(pose0), _pose(pose1)
+    return _MotionAccel(_ptr(t0), _ptr(n0), _ptr(t1), _ptr(n1), int(root), int(count))
+
+
+def MotionValidate(pose0, pose1, root: int, count: int, num_triangles: int, status, stream=None) -> None:
+    """rt_motion_validate: sets RT_MOTION_TOPOLOGY_MISMATCH in `status` (a device uint32) when the two poses ((triangles, nodes)
+    pairs or BuildInputs) are not one tree -- a w12 / w28 word, an id or a rotation differs -- and clears it otherwise.  Once per
+    pair of poses.  Asynchronous on `stream`; read the word with motion_status."""
+    a = _motion_accel(pose0, pose1, root, count)
+    _check(lib().rt_motion_validate(ctypes.byref(a), int(num_triangles), _ptr(status), _stream_ptr(stream)), "rt_motion_validate")
+
+
+def motion_status(status) -> int:
+    """The RT_MOTION_* flags of the last MotionValidate (copies the word back: waits for the work queued before it)."""
+    return _status_word(status)
+
+
+def IntersectRaysMotion(pose0, pose1, root: int, count: int, rays, times, hits, *, any_hit: bool = False, counters=None,
+                        stream=None) -> None:
+    """rt_intersect_rays_motion: IntersectRays with a time per ray over two key poses of one tree.  pose0 / pose1: (triangles,
+    nodes) pairs or BuildInputs -- pose 0 the built tree, pose 1 from MotionPose.  `times`: a contiguous device float32 tensor,
+    one value in [0, 1] per ray; ray i sees the tree interpolated at times[i] (w0 * pose0 + t * pose1, w0 = 1 - t).  A ray with a
+    NaN time or one outside [0, 1] is a miss.  rays / hits / any_hit / counters as for IntersectRays.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not times.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, times / hits contiguous device buffers")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(times) < 4 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records and times {n} floats")
+    if n == 0:
+        return
+    a = _motion_accel(pose0, pose1, root, count)
+    _check(lib().rt_intersect_rays_motion(ctypes.byref(a), _ptr(rays), _ptr(times), _ptr(hits), n,
+                                          kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_motion")
 
 
 def accel_table(trees, device="cuda"):

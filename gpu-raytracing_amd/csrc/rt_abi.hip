@@ -391,6 +391,35 @@ int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* p
     return hip_rc(launch_refit(*input, root, count, plan, static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_motion_accel) == 40 && offsetof(rt_motion_accel, root) == 32, "rt_abi.h: rt_motion_accel's layout");
+
+// two poses a motion query can walk: count = 0 is an empty tree, nothing is read through it
+static inline bool motion_tree_args(const rt_motion_accel* as)
+{
+    return as && as->count <= 7 && (!as->count || (as->nodes0 && as->triangles0 && as->nodes1 && as->triangles1));
+}
+
+int rt_motion_validate(const rt_motion_accel* as, uint32_t num_triangles, uint32_t* status, void* stream)
+{
+    if (!motion_tree_args(as) || !status || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (as->count && (misaligned(as->nodes0, 16) || misaligned(as->nodes1, 16) || misaligned(as->triangles0, 16) ||
+                      misaligned(as->triangles1, 16)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_triangles > RT_REFIT_MAX_TRIANGLES) return RT_ERR_TOO_LARGE;
+    return hip_rc(launch_motion_validate(*as, num_triangles, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_motion(const rt_motion_accel* as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
+                             int mode, uint64_t* counters, void* stream)
+{
+    if (!motion_tree_args(as) || !rays || !times || !hits) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(times, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_motion_query(*as, rays, times, hits, num_rays, mode == RT_RAY_ANY_HIT, counters,
+                                      static_cast<hipStream_t>(stream)));
+}
+
 int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
                          rt_triangle* proxies, rt_instance_record* records, uint32_t* status, void* stream)
 {
@@ -695,6 +724,9 @@ const char* rt_version_string(void)
            "last, the 3x10bit sort with identity values, indexed queries through the ray-query kernel body | "
            "refit: top-down plan walk (one wide launch per level + one-workgroup tail, one CAS per run), one thread per leaf slot "
            "climbing by last-arrival tickets, sc1 box hand-off, ordered min / max | "
+           "motion: a time per ray over two refitted poses of one tree, boxes and corners interpolated per lane as "
+           "fl(fl(w0*a) + fl(t*b)) (monotone: interpolated boxes bound exactly), eight 16-byte requests per box step, the "
+           "ray query's loop and tests | "
            "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "
            "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "

@@ -218,6 +218,11 @@ hipError_t launch_ray_query_indexed(const rt_accel& as, const rt_ray* rays, uint
                                     uint32_t num_indices, rt_hit* hits, bool any_hit, uint32_t num_primitives,
                                     uint64_t* counters, hipStream_t st);
 
+// motion_query.hip: rt_intersect_rays_motion (num_rays > 0) / rt_motion_validate after their argument checks
+hipError_t launch_motion_query(const rt_motion_accel& as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
+                               bool any_hit, uint64_t* counters, hipStream_t st);
+hipError_t launch_motion_validate(const rt_motion_accel& as, uint32_t num_triangles, uint32_t* status, hipStream_t st);
+
 // ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
 struct RaySortLayout {
     size_t box;         // float lo[4], hi[4] at the start of the 256-byte header

@@ -319,6 +319,57 @@ int rt_refit_plan_layout_get(uint32_t num_triangles, rt_refit_plan_layout* out);
 int rt_build_refit_plan(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
 int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* plan, void* stream);
 
+/* ---- motion-blur ray queries (no reference counterpart: the reference traces one frozen mesh, main.cu:125-192).  A time per
+ * ray over TWO key poses of one tree: what motion blur and any time-sampled visibility query of a deforming mesh need.
+ *
+ * Poses.  Pose 0 is a built tree (any tree rt_intersect_rays takes).  Pose 1 is a byte copy of pose 0's nodes_out /
+ * triangles_out, refitted (rt_refit) with the moved vertices through a plan of its OWN (a plan fingerprints its nodes_out).
+ * Refit keeps topology, ids and rotations, so both poses are one tree with two geometries.  Both poses must have refit status
+ * 0 (a broken pair cannot be represented) and all coordinates must be finite (0 * inf is NaN).
+ *   SPLIT TREES (rt_run_sah_build, enable_splits): pose 0 must be identity-refitted first.  The build clips a split
+ *   reference's leaf box to its grid cell, a refit writes the record's unclipped bound; a clipped box interpolated with an
+ *   unclipped one bounds nothing.
+ *
+ * rt_intersect_rays_motion: hits[i] for rays[i] at times[i], i < num_rays.  times[i] lies in [0, 1].  Ray i sees every box
+ * bound and every leaf-record corner of the tree as
+ *       w0 = 1 - times[i]  (computed once per ray);   v = fl(fl(w0 * a) + fl(times[i] * b))
+ * in float32, a from pose 0 and b from pose 1, the three operations rounded separately (no fused multiply-add).  This form is
+ * monotone in a and in b, so an interpolated box bounds the interpolated corners and boxes under it exactly, and it gives a
+ * at time 0 and b at time 1 (as numbers: a zero may change sign).  a + t * (b - a) has neither property and is not used.
+ * The slots' w12 / w28 words, primitive ids and rotations are read from pose 0.
+ *   Everything else is rt_intersect_rays's contract, applied to the interpolated values: the slab test, Moller-Trumbore with
+ *   the same epsilon, slot order, nearest child first, the 64-entry stack with dropped pushes, pops not re-culled, RT_RAY_ANY_HIT
+ *   ending a ray at its first accepted triangle, a single-triangle record's second triangle skipped (v3 == v2, compared on the
+ *   interpolated corners), (u, v) mapped through rotations, the miss record {+inf, RT_MISS, 0, 0}, and the counters ([0] box
+ *   tests, [1] triangle tests, [2] / [3] wave steps).  With every time 0 (1) the records and counters [0], [1] are
+ *   rt_intersect_rays's over pose 0 (pose 1); t, u, v may differ in the sign of a zero.
+ *   A ray rt_intersect_rays would not trace, and a ray whose time is NaN or outside [0, 1], is not traced: a miss, no tests
+ *   counted.  hits[i >= num_rays] are not written.
+ *   rays / hits: 16-byte aligned device arrays; times: a 4-byte aligned device array of num_rays floats; counters: optional
+ *   device uint64[4].  Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null as / rays / times / hits,
+ *   a null tree pointer with count > 0, count > 7, rays or hits not 16-byte aligned, times not 4-byte aligned, a mode other than
+ *   the two.  num_rays = 0: nothing runs.  Asynchronous, no host copy: hipGraph-capturable.
+ *   Cost: every step fetches from both poses, twice rt_intersect_rays's requests (DESIGN section 22 has the measured ratio).
+ *
+ * rt_motion_validate, once per pair of poses, off the hot path (a memset and one streaming launch): sets
+ * RT_MOTION_TOPOLOGY_MISMATCH in *status (a 4-byte aligned device uint32; read it after the stream has run) when a w12 / w28
+ * word of any of the rt_nodes_bytes(num_triangles) / 32 slots, or the primitive ids or rotations of any of the num_triangles
+ * leaf records, differ between the poses; clears the word otherwise.  count = 0: the word is cleared, nothing is compared.
+ * Argument errors: RT_ERR_INVALID_ARGUMENT for a null as / status, a null tree pointer with count > 0, count > 7, a status not
+ * 4-byte or a tree pointer not 16-byte aligned; RT_ERR_TOO_LARGE for num_triangles > RT_REFIT_MAX_TRIANGLES.
+ *
+ * Out of scope: more than two key poses; motion of instance transforms; filtered, indexed, all-hit and first-K motion forms;
+ * the pair-prefetch traversal; shading of motion hits; the C++ host mirror and rt_cli. */
+typedef struct rt_motion_accel {
+    const rt_triangle_pair* triangles0; const rt_node* nodes0;   /* key pose at time 0 */
+    const rt_triangle_pair* triangles1; const rt_node* nodes1;   /* key pose at time 1: the same tree, refitted */
+    uint32_t root, count;
+} rt_motion_accel;
+enum { RT_MOTION_TOPOLOGY_MISMATCH = 1 };
+int rt_motion_validate(const rt_motion_accel* as, uint32_t num_triangles, uint32_t* status, void* stream);
+int rt_intersect_rays_motion(const rt_motion_accel* as, const rt_ray* rays, const float* times, rt_hit* hits,
+                             uint32_t num_rays, int mode, uint64_t* counters, void* stream);
+
 /* ---- instancing (no reference counterpart: the reference traces one mesh, main.cu:125-192).  A scene of placed copies of
  * a few meshes: every mesh has its own built tree (a bottom-level tree, BLAS: any tree rt_trace takes -- LBVH, pairs, hybrid,
  * SAH, splits, mixed kinds in one table), and a small top-level tree (TLAS) is built over the placed copies.
