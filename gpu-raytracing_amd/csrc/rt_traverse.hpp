@@ -178,6 +178,34 @@ constexpr bool kLeanSelect = RT_TRACE_LEAN_SELECT != 0;
 #endif
 static_assert(kLeanMargin <= kStackLds, "the lean vote's threshold is a stack level");
 
+// The pair-local step (trace_ray<.., QW = true> only; pair_step_on below).  near_e / near_d are carried from box step to box
+// step, but advance() resets them at the end of every pair unless the node has more than two slots: in an LBVH, a pairs
+// tree or a hybrid tree EVERY pair is entered with near_e == kNoNear.  For such a pair slot 0's push site is dead, its
+// `closer` test compares against +inf and the nearest child never leaves the step: the pair-local form decides slot 0,
+// slot 1, the one possible push and the advance from values of the step alone, and writes near_e / near_d only where
+// they outlive it (a leaf in slot 1, the first pair of a node of more than two slots).  A ray's sequence of tests, pushes
+// and pops is the general form's.
+// A vote is NARROW iff no unfinished lane -- stepping, held or parked -- has (cur >> 29) > 2 or near_e != kNoNear.  A narrow
+// vote runs both of its steps in the pair-local form, any other vote today's general step.  Why no lane of a narrow vote
+// starts a step with a carried near: at the vote no lane's cur is wider than a pair and none carries a near.  A lane's first
+// step ends in advance -- near_e untouched, still kNoNear -- or in a park, and a parked lane takes no second step.  The cur
+// it advances to may be a node of more than two slots: the lane steps that node's FIRST pair in the second step at the
+// earliest, near_e == kNoNear as the form asks, and the form's tail leaves the near in near_e / near_d and cur on the
+// node's next pair.  That carried near makes the next vote a general one, and a general vote steps anything.  A lane freed by
+// a leaf phase comes back with whatever second_slot / advance left: counted by the next vote like any other.  (A parked lane
+// takes neither step of a vote, so the rule could leave it out -- a lane parked in PH_LEAF1 often carries a near and makes
+// the votes it sits out general ones.  Measured as a second arm: 100 % instead of 99.2 % narrow votes on the bench frame
+// and no different in time on any workload, profiles/pair_step_bench.txt; the rule counts every unfinished lane.)
+// The lean margin is untouched: the pair-local form pushes at most once per step.  Nothing in either form makes a lane wait
+// (quad_hold's progress argument holds word for word); one traversal state and one sp, so a wave may change form at every
+// vote.  How the two forms are laid out in the loop, and why: at the vote in trace_ray and profiles/pair_step_asm.txt.
+//   1 (shipped)  narrow votes run the pair-local form: -7.8 % issued instructions, +3.6 % on the headline;
+//   0            every vote runs the general step: the loop before this knob, instruction for instruction.
+#ifndef RT_TRACE_PAIR_STEP
+#define RT_TRACE_PAIR_STEP 1
+#endif
+constexpr int kPairStep = RT_TRACE_PAIR_STEP;
+
 // per-lane traversal state.  PH_STEP_POP (QW traversals only): PH_STEP whose cur was popped from the stack, from level sp.
 enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3, PH_STEP_POP = 4 };
 constexpr uint32_t kNoNear = 0xFFFFFFFFu;  // "no Box child hit yet" (child 2^29-1, count 7: not a real entry)
@@ -190,8 +218,8 @@ struct Trav {
     uint32_t* spill;
     int sp;
     uint32_t cur;       // slots still to visit of the current node: first slot : 29 | slot count : 3
-    uint32_t near_e;    // nearest Box child so far (packed like cur) or kNoNear
-    float near_d;       // its front distance (+inf while kNoNear)
+    uint32_t near_e;    // nearest Box child so far (packed like cur) or kNoNear.  Outlives a box step only inside a node of more
+    float near_d;       // than two slots or across a leaf test; the pair-local step writes the two only then.  near_d: its front distance (+inf while kNoNear)
     uint32_t phase;
     uint32_t leaf;      // pending leaf: index : 29 | count : 3
     // second slot of the current pair, kept while parked in PH_LEAF0
@@ -323,8 +351,71 @@ __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav&
     }
 }
 
+// The same tests for a pair entered WITHOUT a carried near (t.near_e == kNoNear, t.near_d == +inf: every pair of a narrow
+// vote, see RT_TRACE_PAIR_STEP), QW traversals only.  Both slots are decided before anything is pushed: no leaf test lies
+// between them unless slot 0 is a leaf hit, and that parks the lane exactly as box_step_on does.  Otherwise the general form
+// would make slot 0's Box hit the near (nothing to displace, nothing pushed) and hand slot 1 to inner_hit against it:
+// `closer` below is that call's test, the one push its push, `near` / `nd` what it leaves in near_e / near_d.  (A Box hit
+// whose front is +inf is "not closer than no near" there and is lost; it takes tmax = +inf and a ray without a direction,
+// which no camera ray has, and the `<` against +inf that would keep even that is not spent here.)  Then advance(), inline
+// on the local near.  TAIL: the pair may be the first of a node of more than two slots (the second step of a narrow vote;
+// never its first): near and its front go to near_e / near_d and cur moves on to the node's next pair.
+template <int LEAN, bool TAIL>
+__device__ __forceinline__ void pair_step_on(const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0, const uint4& a1,
+                                             const uint4& b1, bool lean)
+{
+    t.phase = PH_STEP;   // (PH_STEP_POP: the popped entry is being stepped on)
+    float f0, k0, f1, k1;
+    slab(a0, b0, r, f0, k0);
+    slab(a1, b1, r, f1, k1);
+    const uint32_t e0 = (b0.w & kIndexMask) | (a0.w & ~kIndexMask), e1 = (b1.w & kIndexMask) | (a1.w & ~kIndexMask);
+    const uint32_t type0 = b0.w >> 29, type1 = two ? (b1.w >> 29) : (uint32_t)RT_CHILD_NONE;
+    const bool valid0 = type0 != RT_CHILD_NONE, valid1 = type1 != RT_CHILD_NONE;
+    const bool hit0 = valid0 & (k0 >= f0) & (f0 <= r.tmax) & (k0 >= r.tmin);
+    t.box_tests += valid0 ? 1u : 0u;
+    // (the second slot goes to t.f1 .. t.t1 on every path, as in box_step_on, though only a lane parked in PH_LEAF0 reads it:
+    // written under that branch alone, the four registers are copied aside and back on every other path)
+    t.f1 = f1; t.k1 = k1; t.e1 = e1; t.t1 = type1;
+    if (hit0 & (type0 == RT_CHILD_TRI)) {   // parks as in box_step_on, nothing else touched
+        t.leaf = e0; t.phase = PH_LEAF0;
+        return;
+    }
+    const bool hit1 = valid1 & (k1 >= f1) & (f1 <= r.tmax) & (k1 >= r.tmin);
+    t.box_tests += valid1 ? 1u : 0u;
+    const bool leaf1 = hit1 & (type1 == RT_CHILD_TRI), box1 = hit1 & !leaf1;
+    const bool closer = (f1 < f0) | ((f1 == f0) & ((e1 & kIndexMask) > (e0 & kIndexMask)));
+    if (hit0 & box1) t.template push<LEAN>(closer ? e0 : e1, lean);
+    const bool second = box1 & (closer | !hit0);
+    const uint32_t near = second ? e1 : (hit0 ? e0 : kNoNear);
+    const float nd = second ? f1 : (hit0 ? f0 : __builtin_inff());
+    if (leaf1) {   // the leaf phase's advance() reads the near; its front is needed if the node goes on
+        t.near_e = near; t.near_d = nd;
+        t.leaf = e1; t.phase = PH_LEAF1;
+        return;
+    }
+    if constexpr (TAIL) {
+        const uint32_t cnt = t.cur >> 29;
+        if (cnt > 2) {
+            t.near_e = near; t.near_d = nd;
+            t.cur = ((t.cur & kIndexMask) + 2) | ((cnt - 2) << 29);
+            return;
+        }
+    }
+    // advance(): the near under the keep rule, else a popped entry, else done; near_e / near_d stay kNoNear / +inf
+    const bool keep = LEAN == 1 ? near != kNoNear : (near != kNoNear) & (t.sp < kStackMax);
+    if (keep) t.cur = near;
+    else if (t.sp == 0) t.phase = PH_DONE;
+    else {
+        --t.sp;
+        if (LEAN == 1 || (LEAN == 2 && lean)) t.cur = t.lds[t.sp * 64];
+        else t.cur = t.sp < kStackLds ? t.lds[t.sp * 64] : t.spill[t.sp - kStackLds];
+        t.phase = PH_STEP_POP;
+    }
+}
+
 // One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
-template <bool PF, bool QW = false, int LEAN = 0, class Params>
+// PAIR (QW only): 0 the general tests, 1 / 2 the pair-local ones of a narrow vote (1: its first step, no TAIL; 2: its second).
+template <bool PF, bool QW = false, int LEAN = 0, int PAIR = 0, class Params>
 __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t, bool lean = false)
 {
     const uint32_t cnt = t.cur >> 29;
@@ -343,7 +434,8 @@ __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t,
         __builtin_amdgcn_sched_barrier(0);
 #endif
     }
-    box_step_on<PF, QW, LEAN>(p, r, t, two, a0, b0, a1, b1, lean);
+    if constexpr (QW && PAIR != 0) pair_step_on<LEAN, PAIR == 2>(r, t, two, a0, b0, a1, b1, lean);
+    else box_step_on<PF, QW, LEAN>(p, r, t, two, a0, b0, a1, b1, lean);
 }
 
 // Hold at pop, evaluated by the WHOLE wave (it reads its quad-mates' registers through DPP, and a switched-off lane's registers
@@ -385,16 +477,17 @@ __device__ __forceinline__ bool quad_hold(const Trav& t)
     return hold;
 }
 
-// The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held).  LEAN / lean: the vote's arm.
-template <bool PF, bool ANY, int LEAN, class Params>
+// The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held).  LEAN / lean: the vote's arm;
+// NARROW: both steps in the pair-local form (RT_TRACE_PAIR_STEP).
+template <bool PF, bool ANY, int LEAN, bool NARROW = false, class Params>
 __device__ __forceinline__ void quad_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
 {
-    if (go) box_step<PF, true, LEAN>(p, r, t, lean);
+    if (go) box_step<PF, true, LEAN, NARROW ? 1 : 0>(p, r, t, lean);
     // second step under the same vote
 #if RT_TRACE_QUAD_WAIT_SECOND
-    if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true, LEAN>(p, r, t, lean);
+    if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true, LEAN, NARROW ? 2 : 0>(p, r, t, lean);
 #else
-    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, LEAN>(p, r, t, lean);
+    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, LEAN, NARROW ? 2 : 0>(p, r, t, lean);
 #endif
 }
 
@@ -497,10 +590,27 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 // (held lanes counted on the stepping side of this threshold instead: measured, no different -- DESIGN section 5)
                 if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
                 nbox += 2;
-                if constexpr (kLeanStep == 1) {
-                    if (lean) quad_vote_steps<PF, ANY, 1>(p, r, t, go, true);
-                    else quad_vote_steps<PF, ANY, 0>(p, r, t, go, false);
-                } else quad_vote_steps<PF, ANY, kLeanStep>(p, r, t, go, lean);
+                // the narrow vote (RT_TRACE_PAIR_STEP): no unfinished lane sits on more than a pair or carries a near.  The two
+                // forms are two `if`s in a row, not if / else, and the compiler must not see that one flag decides both: as
+                // alternatives that meet at the loop's end, the general form keeps the lanes' state in registers of its own and
+                // eleven of them are copied across on each side of every vote (profiles/pair_step_asm.txt)
+                uint64_t wide = ~0ull;
+                if constexpr (kPairStep != 0) {
+                    wide = __builtin_amdgcn_ballot_w64((t.phase != PH_DONE) & (((t.cur >> 29) > 2) | (t.near_e != kNoNear)));
+                    if (wide == 0) {
+                        if constexpr (kLeanStep == 1) {
+                            if (lean) quad_vote_steps<PF, ANY, 1, true>(p, r, t, go, true);
+                            else quad_vote_steps<PF, ANY, 0, true>(p, r, t, go, false);
+                        } else quad_vote_steps<PF, ANY, kLeanStep, true>(p, r, t, go, lean);
+                    }
+                    asm volatile("" : "+s"(wide));
+                }
+                if (wide != 0) {
+                    if constexpr (kLeanStep == 1) {
+                        if (lean) quad_vote_steps<PF, ANY, 1>(p, r, t, go, true);
+                        else quad_vote_steps<PF, ANY, 0>(p, r, t, go, false);
+                    } else quad_vote_steps<PF, ANY, kLeanStep>(p, r, t, go, lean);
+                }
                 continue;
             }
             stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);

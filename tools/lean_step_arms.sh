@@ -7,6 +7,7 @@
 #   hv     -DRT_TRACE_HOLD_VECTOR=1                      lean + quad_hold's combine in vector operations
 #   leanr / siter  -DRT_TRACE_QUAD_WAIT_SECOND=1         lean / site + the hold rule before both steps of a vote
 #   pad8 / pad16  -DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=8|16   the parent's loop with N more vector instructions per box step
+#   pair0 / pair  -DRT_TRACE_PAIR_STEP=0|1                     every vote runs the general box step / narrow votes run the pair-local one (shipped)
 # A library built elsewhere (the parent commit's) joins as arm NAME when copied to csrc/librt_amd_exp_NAME.so.
 # Build the arms first (where hipcc is):   bash tools/lean_step_arms.sh build
 # Run (on the GPU, from the repo root):    ARMS="lean0 lean sel" bash tools/lean_step_arms.sh run <out dir> <runs> [bench.py arguments]
@@ -20,6 +21,7 @@ flags() {
     lean0) echo "-DRT_TRACE_LEAN_STEP=0";; lean) echo "-DRT_TRACE_LEAN_STEP=1";; site) echo "-DRT_TRACE_LEAN_STEP=2";; sel) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_LEAN_SELECT=1";;
     hv) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_HOLD_VECTOR=1";; leanr) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_QUAD_WAIT_SECOND=1";;
     siter) echo "-DRT_TRACE_LEAN_STEP=2 -DRT_TRACE_QUAD_WAIT_SECOND=1";;
+    pair0) echo "-DRT_TRACE_PAIR_STEP=0";; pair) echo "-DRT_TRACE_PAIR_STEP=1";;
     pad8) echo "-DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=8";; pad16) echo "-DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=16";;
     *) return 1;;
   esac

@@ -16,6 +16,11 @@ lane requests of the lanes that step.
 kParkNum / kParkDen, two box steps per vote (the rule is evaluated before the first; "hold, 2nd too": before both).  It predicts the wave's box-phase and
 leaf-phase iteration counts (counters 2 and 3 of rt_trace) and the requests per wave load instruction.
 
+run_wave(pair=1|2) adds the two forms of a box step (RT_TRACE_PAIR_STEP, csrc/rt_traverse.hpp): a NARROW vote -- no lane that
+counts sits on more than a pair or carries a near -- runs both of its steps as Ray.pair_step, which asserts what the form
+relies on (no carried near; no node of more than two slots in the first step); any other vote runs Ray.box_step.  pair=1
+counts every unfinished lane (the kernel's rule); pair=2 leaves the parked lanes out (the arm that was measured beside it).
+
 The arithmetic is float64 on the float32 inputs: a model of the schedule, not a second oracle.
 
   python3 tools/quad_wait_model.py --grid 708 --camera a --tree lbvh --samples 40
@@ -77,7 +82,7 @@ def _inv(a):
 
 class Ray:
     """One lane of the kernel: Trav (rt_traverse.hpp) plus its ray.  `visits` records the ray's own sequence of tests:
-    ("b", pair) per box step, ("t", leaf) per leaf test."""
+    ("b", pair) per box step, ("t", leaf) per leaf test; `pushes` every entry handed to push(), dropped ones included."""
     def __init__(self, tree, org, d, tmin, tmax, active=True):
         self.t = tree
         self.o, self.d, self.tmin, self.tmax = org, d, tmin, tmax
@@ -93,10 +98,12 @@ class Ray:
         self.e1 = self.t1 = 0
         self.box_tests = self.tri_tests = 0
         self.visits = []
+        self.pushes = []
         self.hit = False
 
     # ---- Trav
     def push(self, e):
+        self.pushes.append((len(self.visits), e))
         if self.sp < STACK_MAX:
             self.stack[self.sp] = e
         self.sp = min(self.sp + 1, STACK_MAX)
@@ -170,6 +177,58 @@ class Ray:
             self.second_slot()
             if self.phase == STEP:
                 self.advance()
+
+    def pair_step(self, tail):
+        """pair_step_on: the box step of a pair entered without a carried near, decided from values of the step alone.
+        Returns what the step wrote of near_e: None, "leaf1" (parked with the near kept for the leaf phase) or "tail" (the
+        first pair of a node of more than two slots: near kept, cur on the node's next pair)."""
+        assert self.phase == STEP
+        assert self.near_e == NO_NEAR and self.near_d == INF, "a pair-local step starts without a carried near"
+        cnt = self.cur >> 29
+        assert tail or cnt <= 2, "the first step of a narrow vote never sits on a node of more than two slots"
+        self.popped = False
+        n = self.cur & INDEX_MASK
+        two = cnt > 1
+        self.visits.append(("b", n))
+        n1 = n + 1 if two else n
+        f0, k0 = self.slab(n)
+        f1, k1 = self.slab(n1)
+        w12, w28 = self.t.w12, self.t.w28
+        e0 = (w28[n] & INDEX_MASK) | (w12[n] & ~INDEX_MASK & 0xFFFFFFFF)
+        e1 = (w28[n1] & INDEX_MASK) | (w12[n1] & ~INDEX_MASK & 0xFFFFFFFF)
+        type0, type1 = w28[n] >> 29, (w28[n1] >> 29) if two else CHILD_NONE
+        hit0 = type0 != CHILD_NONE and k0 >= f0 and f0 <= self.tmax and k0 >= self.tmin
+        self.box_tests += 1 if type0 != CHILD_NONE else 0
+        self.f1, self.k1, self.e1, self.t1 = f1, k1, e1, type1
+        if hit0 and type0 == CHILD_TRI:
+            self.leaf, self.phase = e0, LEAF0
+            return None
+        hit1 = type1 != CHILD_NONE and k1 >= f1 and f1 <= self.tmax and k1 >= self.tmin
+        self.box_tests += 1 if type1 != CHILD_NONE else 0
+        leaf1 = hit1 and type1 == CHILD_TRI
+        box1 = hit1 and not leaf1
+        closer = f1 < f0 or (f1 == f0 and (e1 & INDEX_MASK) > (e0 & INDEX_MASK))
+        if hit0 and box1:
+            self.push(e0 if closer else e1)
+        second = box1 and (closer or not hit0)
+        near, nd = (e1, f1) if second else ((e0, f0) if hit0 else (NO_NEAR, INF))
+        if leaf1:
+            self.near_e, self.near_d = near, nd
+            self.leaf, self.phase = e1, LEAF1
+            return "leaf1"
+        if tail and cnt > 2:
+            self.near_e, self.near_d = near, nd
+            self.cur = ((self.cur & INDEX_MASK) + 2) | ((cnt - 2) << 29)
+            return "tail"
+        if near != NO_NEAR and self.sp < STACK_MAX:
+            self.cur = near
+        elif self.sp == 0:
+            self.phase = DONE
+        else:
+            self.sp -= 1
+            self.cur = self.stack[self.sp]
+            self.popped = True
+        return None
 
     def _tri(self, a, b, c):
         eps = 0.000000001
@@ -250,19 +309,25 @@ def run_quad(rays, hold):
                 longest=max(sum(1 for v in r.visits if v[0] == "b") for r in rays))
 
 
-def run_wave(rays, hold, second=False):
+def run_wave(rays, hold, second=False, pair=0):
     """The kernel's loop (trace_ray) over the 64 lanes of a tile, lanes 4q .. 4q+3 = quad q.  Returns dict(nbox, nleaf,
     box_instr, lane_steps, requests): nbox / nleaf are the wave's counters 2 / 3, box_instr the box steps that ran with at
     least one lane, req_* the lane requests (quad_requests) summed over those steps.  second: the second box step under a
-    vote evaluates the rule again (RT_TRACE_QUAD_WAIT_SECOND = 1); the shipped kernel steps every lane in PH_STEP there."""
+    vote evaluates the rule again (RT_TRACE_QUAD_WAIT_SECOND = 1); the shipped kernel steps every lane in PH_STEP there.
+    pair: 0 every vote runs the general step; 1 / 2 a narrow vote (1, RT_TRACE_PAIR_STEP = 1: no unfinished lane; 2, the arm
+    measured beside it: no lane in PH_STEP -- sits on more than a pair or carries a near) runs both steps in the pair-local form.  narrow / general count the
+    votes of each form, tails / carried the pair-local steps that left a near behind for a wider node / across a leaf phase
+    (of those, wide_carried on the first pair of a node of more than two slots).  Raises if a pass of the loop neither steps
+    a lane nor runs a leaf phase."""
     quads = [rays[q:q + 4] for q in range(0, len(rays), 4)]
     nbox = nleaf = box_instr = lane_steps = 0
     requests = [0, 0, 0]
+    forms = dict(narrow=0, general=0, tails=0, carried=0, wide_carried=0)
 
     def going():
         return [r for qd in quads for k, r in enumerate(qd) if r.phase == STEP and not (hold and holds(qd, k))]
 
-    def step(go):
+    def step(go, narrow=False, tail=False):
         nonlocal box_instr, lane_steps
         if not go:
             return
@@ -273,7 +338,14 @@ def run_wave(rays, hold, second=False):
             for j, q in enumerate(quad_requests([r.cur & INDEX_MASK for r in qd if id(r) in ids])):
                 requests[j] += q
         for r in go:
-            r.box_step()
+            if narrow:
+                wide = (r.cur >> 29) > 2
+                left = r.pair_step(tail)
+                forms["tails"] += left == "tail"
+                forms["carried"] += left == "leaf1" and r.near_e != NO_NEAR
+                forms["wide_carried"] += left == "leaf1" and r.near_e != NO_NEAR and wide
+            else:
+                r.box_step()
 
     while True:
         while True:
@@ -282,18 +354,23 @@ def run_wave(rays, hold, second=False):
             if not go or len(go) * PARK_DEN < parked * PARK_NUM:
                 break
             nbox += 2
-            step(go)
-            step(going() if second else [r for r in rays if r.phase == STEP])
+            counts = [r for r in rays if (r.phase != DONE if pair == 1 else r.phase == STEP)]
+            narrow = pair != 0 and not any((r.cur >> 29) > 2 or r.near_e != NO_NEAR for r in counts)
+            forms["narrow" if narrow else "general"] += 1
+            step(go, narrow, False)
+            step(going() if second else [r for r in rays if r.phase == STEP], narrow, True)
         if not go and parked == 0:
             if any(r.phase != DONE for r in rays):
                 raise AssertionError("the wave ends with an unfinished lane")
             break
+        if parked == 0:
+            raise AssertionError("a pass of the loop steps no lane and has no parked lane to free")
         nleaf += 1
         for r in rays:
             if r.phase in (LEAF0, LEAF1):
                 r.leaf_step()
     return dict(nbox=nbox, nleaf=nleaf, box_instr=box_instr, lane_steps=lane_steps, req_any=requests[0], req_on=requests[1],
-                req_full=requests[2])
+                req_full=requests[2], **forms)
 
 
 def quad_rays(tree, cam, w, h, qx, qy):
@@ -327,6 +404,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--wave", action="store_true", help="the kernel's schedule over whole 8 x 8 tiles")
+    ap.add_argument("--pair", type=int, choices=[0, 1, 2], default=0, help="with --wave: narrow votes run the pair-local step (1: the kernel's rule, 2: parked lanes left out)")
     a = ap.parse_args()
     scenes = importlib.import_module("gpu-raytracing_amd.scenes")
     from oracle import oracle_py as ora
@@ -343,7 +421,7 @@ def main():
         for _ in range(a.samples):
             if a.wave:
                 rays = tile_rays(tree, cam, w, h, rng.randrange((w + 7) // 8), rng.randrange((h + 7) // 8))
-                res = run_wave(rays, hold, second)
+                res = run_wave(rays, hold, second, a.pair)
             else:
                 rays = quad_rays(tree, cam, w, h, rng.randrange((w + 1) // 2), rng.randrange((h + 1) // 2))
                 res = run_quad(rays, hold)
@@ -356,6 +434,8 @@ def main():
                     f"box instructions {tot['box_instr'] / n:.1f}  lanes per instruction {tot['lane_steps'] / max(tot['box_instr'], 1):.1f}  "
                     f"requests per lane step any/on/full {req}  "
                     f"requests per box instruction any/on/full " + " / ".join(f"{tot[k] / max(tot['box_instr'], 1):.1f}" for k in ("req_any", "req_on", "req_full")))
+            if a.pair:
+                line += f"  narrow votes {100.0 * tot['narrow'] / max(tot['narrow'] + tot['general'], 1):.1f} %"
         else:
             line = (f"{name:12s} requests per lane step any/on/full {req}   rounds per quad {tot['rounds'] / n:.1f}   "
                     f"lane steps per quad {tot['lane_steps'] / n:.1f}   longest ray {tot['longest']}")
