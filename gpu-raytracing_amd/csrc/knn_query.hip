@@ -134,11 +134,8 @@ __global__ __launch_bounds__(kTraceWaves * 64) void knn_query_kernel(KnnParams p
     };
     auto leaf_step = [&]() {
         tri_tests++;
-        const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + (cur & kIndexMask));
-        uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-        // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (rt_traverse.hpp)
-        asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
-                          "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
+        uint4 l0, l1, l2, l3;
+        load_leaf_wide(p.leaves + (cur & kIndexMask), l0, l1, l2, l3);
         offer(range_tri_d2(px, py, pz, leaf_tri_a(l0, l1, l2)), l0.w);
         if (l1.w == l0.w + 1u)                // a pair record: B = (v2, v1, v3) with rotations[1]
             offer(range_tri_d2(px, py, pz, leaf_tri_b(l1, l2, l3)), l1.w);

@@ -143,11 +143,8 @@ __global__ __launch_bounds__(kTraceWaves * 64, RT_TRACE_MIN_WAVES + RT_TRACE_LEA
     };
     auto leaf_step = [&]() {
         tri_tests++;
-        const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + (cur & kIndexMask));
-        uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-        // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (rt_traverse.hpp)
-        asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
-                          "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
+        uint4 l0, l1, l2, l3;
+        load_leaf_wide(p.leaves + (cur & kIndexMask), l0, l1, l2, l3);
         if (rg.match(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
                      __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
                      __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z), l2.w & 0xFFFFu))

@@ -253,10 +253,8 @@ __device__ __forceinline__ bool trace_instanced(const InstParams& p, uint64_t ri
             prefetch_pair<PF>(ln, t);
         }
     }
-#ifndef RT_TRACE_NO_STEPS
     steps[0] += nbox;
     steps[1] += nleaf;
-#endif
     return tri_hit;
 }
 

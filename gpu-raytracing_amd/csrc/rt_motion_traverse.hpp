@@ -79,13 +79,12 @@ __device__ __forceinline__ bool motion_leaf_test(const MotionParams& p, Ray& r, 
     const uint4* t1 = reinterpret_cast<const uint4*>(p.leaves1 + li);
     uint4 l00 = t0[0], l10 = t0[1], l20 = t0[2], l30 = t0[3];
     uint4 l01 = t1[0], l11 = t1[1], l21 = t1[2], l31 = t1[3];
-#if RT_TRACE_LEAF_WIDE
-    // (as trace_ray: the eight loads stay eight 16-byte requests issued together)
+    // (as load_leaf_wide: the eight loads stay eight 16-byte requests issued together.  Not two calls of it: those interleave
+    // loads and barriers differently)
     asm volatile("" : "+v"(l00.x), "+v"(l00.y), "+v"(l00.z), "+v"(l00.w), "+v"(l10.x), "+v"(l10.y), "+v"(l10.z), "+v"(l10.w),
                       "+v"(l20.x), "+v"(l20.y), "+v"(l20.z), "+v"(l20.w), "+v"(l30.x), "+v"(l30.y), "+v"(l30.z), "+v"(l30.w));
     asm volatile("" : "+v"(l01.x), "+v"(l01.y), "+v"(l01.z), "+v"(l01.w), "+v"(l11.x), "+v"(l11.y), "+v"(l11.z), "+v"(l11.w),
                       "+v"(l21.x), "+v"(l21.y), "+v"(l21.z), "+v"(l21.w), "+v"(l31.x), "+v"(l31.y), "+v"(l31.z), "+v"(l31.w));
-#endif
     const uint4 l0 = lerp.word(l00, l01), l1 = lerp.word(l10, l11), l2 = lerp.word(l20, l21), l3 = lerp.word(l30, l31);
     bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
                                  __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
@@ -149,10 +148,8 @@ __device__ __forceinline__ bool trace_ray_motion(const MotionParams& p, Ray& r, 
             }
         }
     }
-#ifndef RT_TRACE_NO_STEPS
     steps[0] += nbox;
     steps[1] += nleaf;
-#endif
     return tri_hit;
 }
 

@@ -20,39 +20,17 @@ constexpr int kTraceWaves = RT_TRACE_WAVES;   // waves (8x8 tiles) per workgroup
 #define RT_TRACE_MIN_WAVES 7   // waves per SIMD the register allocator must fit (72 VGPRs: no spills; 8 -> 64 VGPRs spills)
 #endif
 // kernels without shading (trace_kernel's kDepth / kBoxtests / kTriangleTests, ray_query_kernel) fit 64 VGPRs: one wave more
-// per SIMD.  (RT_TRACE_LEAN_EXTRA = 0 and RT_TRACE_NO_STEPS are the compile-time arms of tools/trace_spill_experiment.sh, which
-// priced the spills of the 64-VGPR instantiations: see DESIGN section 5)
+// per SIMD.  (RT_TRACE_LEAN_EXTRA = 0 is the compile-time arm of tools/trace_spill_experiment.sh, which priced the spills of
+// the 64-VGPR instantiations: see DESIGN section 5)
 #ifndef RT_TRACE_LEAN_EXTRA
 #define RT_TRACE_LEAN_EXTRA 1
 #endif
 #ifndef RT_TRACE_PF_WAVES
 #define RT_TRACE_PF_WAVES 5    // waves per SIMD of the pair-prefetch (PF) instantiations
 #endif
-
-// Wave-shared pairs, an EXPERIMENT ARM of the non-PF instantiations (csrc/Makefile librt_amd_exp.so, -DRT_TRACE_UNIFORM_MAX=1|2|4):
-// when the stepping lanes of a box step sit on at most kUniformMax distinct pairs, each pair is fetched ONCE per wave through the
-// scalar path (wave-uniform loads into SGPRs) instead of 4 vector requests per lane: box_step_wave / box_step_shared below.
-// Shipped: 0, every step takes the vector path -- the best arm (1, sticky) is +0.9 % on the 1M LBVH frame and -3 % on the SAH
-// tree, 2 and 4 lose everywhere (profiles/r05_trace_fetch_arms.txt).
-#ifndef RT_TRACE_UNIFORM_MAX
-#define RT_TRACE_UNIFORM_MAX 0
-#endif
-constexpr int kUniformMax = RT_TRACE_UNIFORM_MAX;
-// 1: the 64 rays of a tile share their path from the root down and rarely meet again once they have parted, so the first vote
-// of a traversal whose last step finds more than kUniformMax pairs ends the looking: later steps pay nothing for it.  0: every
-// step looks.
-#ifndef RT_TRACE_UNIFORM_STICKY
-#define RT_TRACE_UNIFORM_STICKY 1
-#endif
-constexpr bool kUniformSticky = RT_TRACE_UNIFORM_STICKY != 0;
-// 1: a scheduling barrier behind the four loads of a pair (box_step)
-#ifndef RT_TRACE_PAIR_BARRIER
-#define RT_TRACE_PAIR_BARRIER 0
-#endif
-// the leaf phase's four 16-byte loads stay four 16-byte requests (0: the compiler narrows them to the components it uses)
-#ifndef RT_TRACE_LEAF_WIDE
-#define RT_TRACE_LEAF_WIDE 1
-#endif
+// (The experiment arms this loop once carried -- wave-shared pairs through the scalar path, a narrowed leaf fetch, a second
+// hold test per vote and others -- lost their measurements and were retired; numbers, and the commit that still builds
+// them: DESIGN section 5.)
 
 // the wave runs a box step while  stepping * park_den >= parked * park_num  (else one leaf phase)
 constexpr int kParkNum = 8, kParkDen = 1;   // (round-2 sweep under the chunked XCD order, tools/sweep_park.sh: 4..8 equal on the 1080p LBVH frame; 4 is +5 % on the SAH tree but -4 % on the 4K x 16 spp frame)
@@ -128,54 +106,31 @@ __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, f
 // Hold at pop (trace_ray<.., QW = true>; 0 here builds every kernel without it, the parent arm of tools/quad_wait_arms.sh):
 // a lane that has just popped entry E from level s of its stack takes no box step while a quad-mate still holds E at level s
 // of its own stack -- the mate is deeper in the subtree both took first, and when it pops E the two step on E with one
-// address, which the address path charges as one request (quad_hold below).
+// address, which the address path charges as one request (quad_hold below).  The rule is evaluated once per
+// vote: the second box step under the vote steps every lane in PH_STEP.  (Which kernels take it at 1 and 2: trace_kernel.hip.)
 #ifndef RT_TRACE_QUAD_WAIT
 #define RT_TRACE_QUAD_WAIT 1
 #endif
 
-// 0 (shipped): the rule is evaluated once per vote -- the second box step under the vote steps every lane in PH_STEP, so a
-// lane that popped in the first step is not held until the next vote.  1: the second step evaluates the rule again: more
-// merged requests (TA busy -19 %), but the LDS read and the DPP moves then sit in front of every step's loads and
-// the waves wait longer than the address path gains: -2.4 % where 0 is +5 %.
-#ifndef RT_TRACE_QUAD_WAIT_SECOND
-#define RT_TRACE_QUAD_WAIT_SECOND 0
-#endif
-
 // The lean vote (trace_ray<.., QW = true> only).  A vote under which no unfinished lane has more than kStackLds - kLeanMargin
-// entries on its stack is LEAN: the pushes and pops of its box steps -- and of the leaf phase that follows it, if the vote ends
-// the box phase -- go straight to the LDS column, with no sp < kStackLds ladder, no private array and no kStackMax clamp.  Any
-// other vote runs the full ladders.  The test is one compare and one ballot per vote, wave-uniform; stack content and sp are
-// the same object either way, so a wave may change arm at every vote, and no ray's sequence of tests depends on the arm.
+// entries on its stack is LEAN: every push / pop site of its box steps -- and of the leaf phase that follows it, if the vote
+// ends the box phase -- takes a scalar branch on the vote's wave-uniform flag (`lean`) straight to the LDS column, with no
+// sp < kStackLds ladder, no private array and no kStackMax clamp.  Any other vote runs the full ladders.  One stack, one sp: a
+// wave may change arm at every vote, and no ray's sequence of tests depends on the arm.
 // The margin: a lean push at sp writes lds[sp * 64], so every push under the vote must find sp <= kStackLds - 1.  A box step
-// on a pair of a fresh node has no near child yet: the first Box hit becomes `near`, the second is pushed -- at most ONE
-// push.  A pair of a node of more than two slots may start with `near` set: both hits push -- at most TWO.  advance() only
-// pops.  A vote runs two box steps, so a lane that starts it at sp pushes at levels sp .. sp + 3 at most: sp + 3 <=
-// kStackLds - 1.  A vote that ends the box phase runs no box step; the leaf phase's second_slot pushes at most one entry, at
-// level sp: covered by the same bound.  Hence kLeanMargin = 2 steps x 2 pushes = 4, and a lean vote never sees sp above
-// kStackLds (< kStackMax: its pops always read LDS).
-// RT_TRACE_LEAN_STEP picks how the two arms are compiled (profiles/lean_step_bench.txt):
-//   2 (shipped)  ONE loop; each push / pop site takes a scalar branch on the vote's flag (`lean`) to its LDS-only form
-//                or to its ladder: -3.1 % issued instructions, +1.6 % on the headline;
-//   1            TWO copies of the vote's steps, one all-lean (no `keep` term either), one all-full, chosen per vote: the
-//                lean copy is 19 % shorter, but the compiler keeps the lanes' state in different registers in the two copies
-//                and moves it across at every vote (26 v_mov): +5.8 % issued instructions, -1.9 %;
-//   0            every vote runs the full ladders: the loop before this knob.
+// pushes at most TWO entries (a pair entered with `near` set, inside a node of more than two slots; else one), advance() only
+// pops, and a vote runs two box steps: a lane that starts it at sp pushes at levels sp .. sp + 3 at most.  A vote that ends
+// the box phase runs no box step; the leaf phase's second_slot pushes at most one entry, at level sp.  Hence kLeanMargin =
+// 2 steps x 2 pushes = 4, and a lean vote never sees sp above kStackLds (< kStackMax: its pops always read LDS).
+// RT_TRACE_LEAN_STEP: 2 (shipped) as above, -3.1 % issued instructions, +1.6 % on the headline; 0 every vote runs the full
+// ladders (`lean` is never set and folds away).  DESIGN section 5, profiles/lean_step_bench.txt.
 #ifndef RT_TRACE_LEAN_STEP
 #define RT_TRACE_LEAN_STEP 2
 #endif
 constexpr int kLeanStep = RT_TRACE_LEAN_STEP;
+// (1 was the two-copy arm, -1.9 %: retired, its numbers are in profiles/lean_step_bench.txt)
+static_assert(kLeanStep == 0 || kLeanStep == 2, "RT_TRACE_LEAN_STEP is 0 (full ladders) or 2 (shipped); arm 1 was retired");
 constexpr int kLeanMargin = 4;
-// Trims, each its own compile-time arm (tools/lean_step_arms.sh), both measured on RT_TRACE_LEAN_STEP = 1 and left off:
-// RT_TRACE_LEAN_SELECT = 1: the lean copy's advance() as selects instead of branches that re-materialise cur / near_e /
-// near_d / phase at their joins (-0.9 %).  RT_TRACE_HOLD_VECTOR = 1: quad_hold's combine in vector operations instead of
-// 64-bit scalar masks (no difference: four v_cmp -> v_cndmask pairs cost what the scalar ladder did).
-#ifndef RT_TRACE_LEAN_SELECT
-#define RT_TRACE_LEAN_SELECT 0
-#endif
-constexpr bool kLeanSelect = RT_TRACE_LEAN_SELECT != 0;
-#ifndef RT_TRACE_HOLD_VECTOR
-#define RT_TRACE_HOLD_VECTOR 0
-#endif
 static_assert(kLeanMargin <= kStackLds, "the lean vote's threshold is a stack level");
 
 // The pair-local step (trace_ray<.., QW = true> only; pair_step_on below).  near_e / near_d are carried from box step to box
@@ -231,24 +186,35 @@ struct Trav {
     // loads, issued as soon as advance() has picked it -- before the wave's next vote -- and carried in registers
     uint4 pf0, pf1, pf2, pf3;
 
-    // LEAN (here and below; kLeanMargin): 0 the full ladders, 1 the lean form, 2 the site picks by `lean`, the vote's wave-uniform flag
-    template <int LEAN = 0>
+    // `lean` (here and below): the vote's wave-uniform flag (kLeanMargin); a site takes its LDS-only form under it, else its ladder
     __device__ __forceinline__ void push(uint32_t e, bool lean = false)
     {
-        if constexpr (LEAN == 1) { lds[sp * 64] = e; sp++; return; }
-        if (LEAN == 2 && lean) { lds[sp * 64] = e; sp++; return; }
-        if (sp < kStackLds) lds[sp * 64] = e;
-        else if (sp < kStackMax) spill[sp - kStackLds] = e;
-        sp = min(sp + 1, kStackMax);  // a push onto a full stack is dropped (the reference overruns its array, Tracer.cu:353-369)
+        if (lean) { lds[sp * 64] = e; sp++; }
+        else {
+            if (sp < kStackLds) lds[sp * 64] = e;
+            else if (sp < kStackMax) spill[sp - kStackLds] = e;
+            sp = min(sp + 1, kStackMax);  // a push onto a full stack is dropped (the reference overruns its array, Tracer.cu:353-369)
+        }
+    }
+    // the pop ladder: an empty stack ends the ray, else the top entry becomes cur.  QW: a popped cur is marked (PH_STEP_POP).
+    template <bool QW>
+    __device__ __forceinline__ void pop_or_done(bool lean)
+    {
+        if (sp == 0) phase = PH_DONE;
+        else {
+            --sp;
+            if (lean) cur = lds[sp * 64];
+            else cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds];
+            if constexpr (QW) phase = PH_STEP_POP;
+        }
     }
     // A Box child (Tracer.cu:338-363), predicated on `in`: the first hit becomes `near`; a closer one (ties:
     // larger child index) displaces `near` onto the stack; otherwise it is pushed itself.  Bitwise logic on
     // purpose (no short-circuit branches); with no near yet near_d = +inf makes every hit "closer".
-    template <int LEAN = 0>
     __device__ __forceinline__ void inner_hit(bool in, uint32_t e, float front, bool lean = false)
     {
         const bool closer = (front < near_d) | ((front == near_d) & ((e & kIndexMask) > (near_e & kIndexMask)));
-        if (in & (near_e != kNoNear)) push<LEAN>(closer ? near_e : e, lean);
+        if (in & (near_e != kNoNear)) push(closer ? near_e : e, lean);
         const bool take = in & closer;
         near_e = take ? e : near_e;
         near_d = take ? front : near_d;
@@ -256,45 +222,26 @@ struct Trav {
     // the current pair is finished: remaining slots of the same node (count > 2 only, never in an LBVH), else
     // the nearest child (the reference pushes it last and pops it first -- so on a FULL stack that push is dropped
     // like any other and the entry below it is popped instead: same rule as the oracle), else a popped entry, else done
-    // QW: a popped cur is marked (PH_STEP_POP); the lane is in PH_STEP when it gets here.
-    template <bool QW = false, int LEAN = 0>
+    // (pop_or_done).  The lane is in PH_STEP when it gets here.
+    template <bool QW = false>
     __device__ __forceinline__ void advance(bool lean = false)
     {
         const uint32_t cnt = cur >> 29;
-        if constexpr (LEAN == 1 && kLeanSelect) {
-            // the same four-way choice as selects on cur / near_e / near_d / phase, which are live anyway; only the pop,
-            // which reads LDS, stays a branch
-            const bool more = cnt > 2, keep = near_e != kNoNear;
-            const bool pop = !more & !keep & (sp != 0);
-            cur = more ? ((cur & kIndexMask) + 2) | ((cnt - 2) << 29) : (keep ? near_e : cur);
-            phase = (more | keep | pop) ? phase : (uint32_t)PH_DONE;
-            near_e = more ? near_e : kNoNear;
-            near_d = more ? near_d : __builtin_inff();
-            if (pop) { --sp; cur = lds[sp * 64]; if constexpr (QW) phase = PH_STEP_POP; }
-            return;
-        }
         if (cnt > 2) { cur = ((cur & kIndexMask) + 2) | ((cnt - 2) << 29); return; }
-        const bool keep = LEAN == 1 ? near_e != kNoNear : (near_e != kNoNear) & (sp < kStackMax);
+        const bool keep = (near_e != kNoNear) & (sp < kStackMax);
         if (keep) cur = near_e;
-        else if (sp == 0) phase = PH_DONE;
-        else {
-            --sp;
-            if (LEAN == 1 || (LEAN == 2 && lean)) cur = lds[sp * 64];
-            else cur = sp < kStackLds ? lds[sp * 64] : spill[sp - kStackLds];
-            if constexpr (QW) phase = PH_STEP_POP;
-        }
+        else pop_or_done<QW>(lean);
         near_e = kNoNear;
         near_d = __builtin_inff();
     }
     // second slot of the pair, evaluated with the CURRENT tmax (after any leaf hit of the first slot)
-    template <int LEAN = 0>
     __device__ __forceinline__ void second_slot(float tmin, float tmax, bool lean = false)
     {
         const bool valid = t1 != RT_CHILD_NONE;
         const bool hit = valid & (k1 >= f1) & (f1 <= tmax) & (k1 >= tmin);
         box_tests += valid ? 1u : 0u;
         const bool is_leaf = hit & (t1 == RT_CHILD_TRI);
-        inner_hit<LEAN>(hit & !is_leaf, e1, f1, lean);
+        inner_hit(hit & !is_leaf, e1, f1, lean);
         if (is_leaf) { leaf = e1; phase = PH_LEAF1; }
     }
 };
@@ -327,7 +274,7 @@ __device__ __forceinline__ void prefetch_pair(const Params& p, Trav& t)
 // The tests of one box step on a fetched pair (Tracer.cu:323-352 for one pair): both slabs are computed before the ordered
 // tmax compares; a leaf in the first slot parks the lane with the second slot's slab kept.  `two`: the pair has a second slot
 // (else a1 / b1 repeat the first).
-template <bool PF, bool QW = false, int LEAN = 0, class Params>
+template <bool PF, bool QW = false, class Params>
 __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0,
                                             const uint4& a1, const uint4& b1, bool lean = false)
 {
@@ -343,11 +290,11 @@ __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav&
     const bool hit0 = valid0 & (k0 >= f0) & (f0 <= r.tmax) & (k0 >= r.tmin);
     t.box_tests += valid0 ? 1u : 0u;
     const bool leaf0 = hit0 & (type0 == RT_CHILD_TRI);
-    t.template inner_hit<LEAN>(hit0 & !leaf0, e0, f0, lean);
+    t.inner_hit(hit0 & !leaf0, e0, f0, lean);
     if (leaf0) { t.leaf = e0; t.phase = PH_LEAF0; }
     else {
-        t.template second_slot<LEAN>(r.tmin, r.tmax, lean);
-        if (t.phase == PH_STEP) { t.template advance<QW, LEAN>(lean); prefetch_pair<PF>(p, t); }
+        t.second_slot(r.tmin, r.tmax, lean);
+        if (t.phase == PH_STEP) { t.template advance<QW>(lean); prefetch_pair<PF>(p, t); }
     }
 }
 
@@ -360,7 +307,7 @@ __device__ __forceinline__ void box_step_on(const Params& p, const Ray& r, Trav&
 // which no camera ray has, and the `<` against +inf that would keep even that is not spent here.)  Then advance(), inline
 // on the local near.  TAIL: the pair may be the first of a node of more than two slots (the second step of a narrow vote;
 // never its first): near and its front go to near_e / near_d and cur moves on to the node's next pair.
-template <int LEAN, bool TAIL>
+template <bool TAIL>
 __device__ __forceinline__ void pair_step_on(const Ray& r, Trav& t, bool two, const uint4& a0, const uint4& b0, const uint4& a1,
                                              const uint4& b1, bool lean)
 {
@@ -384,7 +331,7 @@ __device__ __forceinline__ void pair_step_on(const Ray& r, Trav& t, bool two, co
     t.box_tests += valid1 ? 1u : 0u;
     const bool leaf1 = hit1 & (type1 == RT_CHILD_TRI), box1 = hit1 & !leaf1;
     const bool closer = (f1 < f0) | ((f1 == f0) & ((e1 & kIndexMask) > (e0 & kIndexMask)));
-    if (hit0 & box1) t.template push<LEAN>(closer ? e0 : e1, lean);
+    if (hit0 & box1) t.push(closer ? e0 : e1, lean);
     const bool second = box1 & (closer | !hit0);
     const uint32_t near = second ? e1 : (hit0 ? e0 : kNoNear);
     const float nd = second ? f1 : (hit0 ? f0 : __builtin_inff());
@@ -402,40 +349,25 @@ __device__ __forceinline__ void pair_step_on(const Ray& r, Trav& t, bool two, co
         }
     }
     // advance(): the near under the keep rule, else a popped entry, else done; near_e / near_d stay kNoNear / +inf
-    const bool keep = LEAN == 1 ? near != kNoNear : (near != kNoNear) & (t.sp < kStackMax);
+    const bool keep = (near != kNoNear) & (t.sp < kStackMax);
     if (keep) t.cur = near;
-    else if (t.sp == 0) t.phase = PH_DONE;
-    else {
-        --t.sp;
-        if (LEAN == 1 || (LEAN == 2 && lean)) t.cur = t.lds[t.sp * 64];
-        else t.cur = t.sp < kStackLds ? t.lds[t.sp * 64] : t.spill[t.sp - kStackLds];
-        t.phase = PH_STEP_POP;
-    }
+    else t.template pop_or_done<true>(lean);
 }
 
 // One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
 // PAIR (QW only): 0 the general tests, 1 / 2 the pair-local ones of a narrow vote (1: its first step, no TAIL; 2: its second).
-template <bool PF, bool QW = false, int LEAN = 0, int PAIR = 0, class Params>
+template <bool PF, bool QW = false, int PAIR = 0, class Params>
 __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t, bool lean = false)
 {
     const uint32_t cnt = t.cur >> 29;
     const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
-#ifdef RT_EXP_BOX_PAD   // experiment arm (csrc/Makefile librt_amd_exp.so): N extra VALU instructions per box step -- which pipe bounds the kernel?
-#pragma unroll
-    for (int q = 0; q < RT_EXP_BOX_PAD; q++) asm volatile("v_mov_b32 %0, %0" : "+v"(t.box_tests));
-#endif
     const bool two = cnt > 1;
     const int o1 = two ? 2 : 0;  // all four loads issue together; a lone slot is simply read twice
     uint4 a0, b0, a1, b1;
     if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
-    else {
-        a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1];
-#if RT_TRACE_PAIR_BARRIER   // nothing is scheduled across: the first slab's arithmetic cannot slip between the second and third load
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-    }
-    if constexpr (QW && PAIR != 0) pair_step_on<LEAN, PAIR == 2>(r, t, two, a0, b0, a1, b1, lean);
-    else box_step_on<PF, QW, LEAN>(p, r, t, two, a0, b0, a1, b1, lean);
+    else { a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1]; }
+    if constexpr (QW && PAIR != 0) pair_step_on<PAIR == 2>(r, t, two, a0, b0, a1, b1, lean);
+    else box_step_on<PF, QW>(p, r, t, two, a0, b0, a1, b1, lean);
 }
 
 // Hold at pop, evaluated by the WHOLE wave (it reads its quad-mates' registers through DPP, and a switched-off lane's registers
@@ -466,80 +398,30 @@ __device__ __forceinline__ bool quad_hold(const Trav& t)
         typedef __attribute__((address_space(3))) lds_u32x4 lds_quad;
         // (the stack array is 16-byte aligned and a quad's four columns share one 16-byte group: rounding the lane's own column down finds it)
         const lds_u32x4 e = *(const lds_quad*)(((uintptr_t)t.lds & ~(uintptr_t)15) + (uintptr_t)t.sp * 256u);
-#if RT_TRACE_HOLD_VECTOR
-        // (a key is an sp, never negative: a mate without the entry counts as key 0, which no sp is below)
-        hold = max(max(e.x == t.cur ? k0 : 0, e.y == t.cur ? k1 : 0), max(e.z == t.cur ? k2 : 0, e.w == t.cur ? k3 : 0)) > t.sp;
-#else
         hold = ((k0 > t.sp) & (e.x == t.cur)) | ((k1 > t.sp) & (e.y == t.cur)) | ((k2 > t.sp) & (e.z == t.cur)) |
                ((k3 > t.sp) & (e.w == t.cur));
-#endif
     }
     return hold;
 }
 
-// The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held).  LEAN / lean: the vote's arm;
-// NARROW: both steps in the pair-local form (RT_TRACE_PAIR_STEP).
-template <bool PF, bool ANY, int LEAN, bool NARROW = false, class Params>
+// The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held); the second steps
+// every lane in PH_STEP, held ones included.  lean: the vote's arm; NARROW: both steps in the pair-local form (RT_TRACE_PAIR_STEP).
+template <bool PF, bool ANY, bool NARROW = false, class Params>
 __device__ __forceinline__ void quad_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
 {
-    if (go) box_step<PF, true, LEAN, NARROW ? 1 : 0>(p, r, t, lean);
-    // second step under the same vote
-#if RT_TRACE_QUAD_WAIT_SECOND
-    if (((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t)) box_step<PF, true, LEAN, NARROW ? 2 : 0>(p, r, t, lean);
-#else
-    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, LEAN, NARROW ? 2 : 0>(p, r, t, lean);
-#endif
+    if (go) box_step<PF, true, NARROW ? 1 : 0>(p, r, t, lean);
+    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, NARROW ? 2 : 0>(p, r, t, lean);
 }
 
-// The same step for the lanes that sit on the pair `c` (packed like Trav::cur), c WAVE-UNIFORM: the pair's 64 bytes are read
-// once per wave through the constant address space -- scalar loads into SGPRs, no vector-memory request -- and every such lane
-// runs the unchanged tests on them.  The tree is read-only for the whole launch, which is what that address space asks.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) u32x4* const_u4_ptr;
-template <class Params>
-__device__ __forceinline__ void box_step_shared(const Params& p, const Ray& r, Trav& t, uint32_t c)
+// The leaf phase's fetch: a leaf (64 bytes) in four 16-byte requests issued together.  The empty asm "uses" all sixteen dwords:
+// left alone the compiler narrows the loads to dwordx3 + overlapping dwordx2 pieces and fetches the primitive ids on a hit,
+// seven or more requests, and the address path charges per request (+3 % on the headline).
+__device__ __forceinline__ void load_leaf_wide(const rt_triangle_pair* leaf, uint4& l0, uint4& l1, uint4& l2, uint4& l3)
 {
-    // (readfirstlane: every lane here has cur == c, and the compiler knows it -- without it the address is formed from the
-    // lane's own cur again and the loads are vector loads)
-    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-    const const_u4_ptr np = (const_u4_ptr)(uintptr_t)(p.nodes + (c & kIndexMask));
-    const bool two = (c >> 29) > 1;
-    const int o1 = two ? 2 : 0;
-    const u32x4 a0 = np[0], b0 = np[1], a1 = np[o1], b1 = np[o1 + 1];
-    box_step_on<false>(p, r, t, two, make_uint4(a0.x, a0.y, a0.z, a0.w), make_uint4(b0.x, b0.y, b0.z, b0.w),
-                       make_uint4(a1.x, a1.y, a1.z, a1.w), make_uint4(b1.x, b1.y, b1.z, b1.w));
-}
-
-// One box step of the wave, `st` = ballot(phase == PH_STEP) != 0.  Up to kUniformMax distinct pairs are peeled off the stepping
-// lanes (the first stepping lane's cur, the lanes that share it, the next lane left ...); if that covers them all, each pair
-// takes box_step_shared (returns true), otherwise every lane takes box_step.  Any lane in PH_STEP whose cur is c may step on
-// pair c at any time: only the interleaving across lanes differs between the two paths, a lane's own sequence of tests does not.
-template <bool PF, class Params>
-__device__ __forceinline__ bool box_step_wave(const Params& p, const Ray& r, Trav& t, uint64_t st)
-{
-    if constexpr (!PF && kUniformMax > 0) {
-        constexpr int K = kUniformMax > 0 ? kUniformMax : 1;   // (no zero-length arrays in the arm that compiles this out)
-        uint32_t cs[K];
-        uint64_t ms[K];
-        uint64_t rest = st;
-#pragma unroll
-        for (int k = 0; k < kUniformMax; k++) {
-            cs[k] = 0; ms[k] = 0;
-            if (rest) {
-                cs[k] = (uint32_t)__builtin_amdgcn_readlane((int)t.cur, __ffsll((unsigned long long)rest) - 1);
-                ms[k] = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP && t.cur == cs[k]);
-                rest &= ~ms[k];
-            }
-        }
-        if (rest == 0) {
-#pragma unroll
-            for (int k = 0; k < kUniformMax; k++)
-                if (ms[k]) { if (t.phase == PH_STEP && t.cur == cs[k]) box_step_shared(p, r, t, cs[k]); }
-            return true;
-        }
-    }
-    if (t.phase == PH_STEP) box_step<PF>(p, r, t);
-    return false;
+    const uint4* tp = reinterpret_cast<const uint4*>(leaf);
+    l0 = tp[0]; l1 = tp[1]; l2 = tp[2]; l3 = tp[3];
+    asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
+                      "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
 }
 
 // Tracer.cu:308-374, restructured as described in trace_kernel.hip's header.  Returns tri_hit.
@@ -570,10 +452,6 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
     bool tri_hit = false;
     uint32_t nbox = 0, nleaf = 0;
     bool lean = false;    // wave-uniform, QW only: the last vote was a lean one (kLeanMargin)
-    bool shared = true;   // wave-uniform; kUniformSticky: the ray's steps look for shared pairs until one step finds too many
-#ifdef RT_EXP_UNIFORM_STATS
-    uint32_t ustat[4] = {0, 0, 0, 0};
-#endif
 
     while (true) {
         // ---------------------------------------------------- box phase: step while enough lanes want to
@@ -597,48 +475,16 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 uint64_t wide = ~0ull;
                 if constexpr (kPairStep != 0) {
                     wide = __builtin_amdgcn_ballot_w64((t.phase != PH_DONE) & (((t.cur >> 29) > 2) | (t.near_e != kNoNear)));
-                    if (wide == 0) {
-                        if constexpr (kLeanStep == 1) {
-                            if (lean) quad_vote_steps<PF, ANY, 1, true>(p, r, t, go, true);
-                            else quad_vote_steps<PF, ANY, 0, true>(p, r, t, go, false);
-                        } else quad_vote_steps<PF, ANY, kLeanStep, true>(p, r, t, go, lean);
-                    }
+                    if (wide == 0) quad_vote_steps<PF, ANY, true>(p, r, t, go, lean);
                     asm volatile("" : "+s"(wide));
                 }
-                if (wide != 0) {
-                    if constexpr (kLeanStep == 1) {
-                        if (lean) quad_vote_steps<PF, ANY, 1>(p, r, t, go, true);
-                        else quad_vote_steps<PF, ANY, 0>(p, r, t, go, false);
-                    } else quad_vote_steps<PF, ANY, kLeanStep>(p, r, t, go, lean);
-                }
+                if (wide != 0) quad_vote_steps<PF, ANY>(p, r, t, go, lean);
                 continue;
             }
             stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
             parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
             if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
             nbox += 2;   // two box steps per vote (below)
-#ifdef RT_EXP_UNIFORM_STATS   // experiment: how often do the stepping lanes of a wave sit on <= 1 / 2 / 4 distinct pairs?  (steps[1] = histogram packed 16 bits each)
-            {
-                uint64_t rest = stepping;
-                int distinct = 0;
-                while (rest && distinct < 5) {
-                    const int l0 = __ffsll((unsigned long long)rest) - 1;
-                    const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)t.cur, l0);
-                    rest &= ~__builtin_amdgcn_ballot_w64(t.phase == PH_STEP && t.cur == c0);
-                    distinct++;
-                }
-                ustat[distinct <= 1 ? 0 : (distinct == 2 ? 1 : (distinct <= 4 ? 2 : 3))]++;
-            }
-#endif
-            if constexpr (!PF && kUniformMax > 0) {
-                // second step under the same vote: the detection is redone on the lanes still stepping
-                if (!kUniformSticky || shared) {
-                    shared = box_step_wave<PF>(p, r, t, stepping);
-                    const uint64_t again = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-                    if (again) shared = box_step_wave<PF>(p, r, t, again);
-                    continue;
-                }
-            }
             if (t.phase == PH_STEP) box_step<PF>(p, r, t);
             // second step under the same vote: halves the per-step loop overhead (ballots, branch, copies)
             if (t.phase == PH_STEP) box_step<PF>(p, r, t);
@@ -649,14 +495,8 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
         if ((t.phase - 1u) < 2u) {
             t.tri_tests++;
             const uint32_t li = t.leaf & kIndexMask;
-            const uint4* tp = reinterpret_cast<const uint4*>(p.leaves + li);
-            uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-#if RT_TRACE_LEAF_WIDE
-            // all sixteen dwords are "used" here: the four loads stay four 16-byte requests issued together (left alone the
-            // compiler narrows them to dwordx3 + overlapping dwordx2 pieces and fetches the primitive ids on a hit: 7+ requests)
-            asm volatile("" : "+v"(l0.x), "+v"(l0.y), "+v"(l0.z), "+v"(l0.w), "+v"(l1.x), "+v"(l1.y), "+v"(l1.z), "+v"(l1.w),
-                              "+v"(l2.x), "+v"(l2.y), "+v"(l2.z), "+v"(l2.w), "+v"(l3.x), "+v"(l3.y), "+v"(l3.z), "+v"(l3.w));
-#endif
+            uint4 l0, l1, l2, l3;
+            load_leaf_wide(p.leaves + li, l0, l1, l2, l3);
             bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
                                          __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
                                          __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
@@ -674,27 +514,14 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
             } else {
                 const bool was_first = t.phase == PH_LEAF0;
                 t.phase = PH_STEP;
-                if (QW && kLeanStep == 1 && lean) {   // (the vote that ended the box phase was lean: a parked lane is outside the margin)
-                    if (was_first) t.template second_slot<1>(r.tmin, r.tmax);
-                    if (t.phase == PH_STEP) t.template advance<QW, 1>();
-                } else if constexpr (QW && kLeanStep == 2) {
-                    if (was_first) t.template second_slot<2>(r.tmin, r.tmax, lean);
-                    if (t.phase == PH_STEP) t.template advance<QW, 2>(lean);
-                } else {
-                    if (was_first) t.second_slot(r.tmin, r.tmax);
-                    if (t.phase == PH_STEP) { t.template advance<QW>(); prefetch_pair<PF>(p, t); }
-                }
+                // (lean: the vote that ended the box phase was lean, so a parked lane is outside the margin)
+                if (was_first) t.second_slot(r.tmin, r.tmax, lean);
+                if (t.phase == PH_STEP) { t.template advance<QW>(lean); prefetch_pair<PF>(p, t); }
             }
         }
     }
-#ifdef RT_EXP_UNIFORM_STATS
-    steps[0] += ustat[RT_EXP_UNIFORM_STATS == 1 ? 0 : 2];   // votes whose stepping lanes sit on 1 (arm 1) / 3-4 (arm 2) distinct pairs
-    steps[1] += ustat[RT_EXP_UNIFORM_STATS == 1 ? 1 : 3];   // ... 2 (arm 1) / more than 4 (arm 2)
-    (void)nbox; (void)nleaf;
-#elif !defined(RT_TRACE_NO_STEPS)
     steps[0] += nbox;
     steps[1] += nleaf;
-#endif
     return tri_hit;
 }
 

@@ -78,11 +78,8 @@ constexpr int kRenderDebugBoxCount = 100;
 constexpr int kRenderDebugBoxCount = -1;   // matches no render type: every use below folds away
 #endif
 // (the park threshold kParkNum / kParkDen: rt_traverse.hpp)
-// A workgroup's four tiles: 4 x 1 (32 x 8 px, consecutive in row-major tile order); 1 = the 2 x 2 experiment arm (16 x 16 px),
-// measured no faster
-#ifndef RT_TRACE_TILE_2X2
-#define RT_TRACE_TILE_2X2 0
-#endif
+// A workgroup's four tiles: 4 x 1 (32 x 8 px, consecutive in row-major tile order).  (A 2 x 2 arrangement, 16 x 16 px, was
+// measured no faster and retired: DESIGN section 5)
 
 
 // ---- publication of the test counters (see the end of trace_kernel).  The caller's four counters are ONE 32-byte target
@@ -326,14 +323,8 @@ void trace_kernel(TraceParams p)
 
     // XCD-aware remap (xcd_chunk_block, rt_traverse.hpp): an XCD takes runs of 8 consecutive workgroups = 8 x 4 tiles
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-#if RT_TRACE_TILE_2X2   // experiment arm: the workgroup's four tiles as a 2 x 2 block (16 x 16 px) of a grid of such blocks
-    const uint32_t blocks_x = (p.tiles_x + 1) / 2;
-    const uint32_t tx = (vb % blocks_x) * 2 + (wave & 1), ty = (vb / blocks_x) * 2 + (wave >> 1);
-    const uint32_t tile = tx < p.tiles_x ? ty * p.tiles_x + tx : p.num_tiles;   // (a block's second column may lie outside the frame)
-#else
     const uint32_t tile = vb * kTraceWaves + wave;
     const uint32_t tx = tile % p.tiles_x, ty = tile / p.tiles_x;
-#endif
 
     // lane -> pixel inside the 8x8 tile, Morton order
     const uint32_t lx = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4);
@@ -467,12 +458,7 @@ hipError_t launch_trace(const TraceLaunch& t, hipStream_t st)
     p.park_num = park[0];
     p.park_den = park[1];
 #endif
-#if RT_TRACE_TILE_2X2
-    static_assert(kTraceWaves == 4, "a 2 x 2 block of tiles per workgroup");
-    const uint32_t blocks = ((p.tiles_x + 1) / 2) * ((tiles_y + 1) / 2);
-#else
     const uint32_t blocks = (p.num_tiles + kTraceWaves - 1) / kTraceWaves;
-#endif
     const dim3 grid(blocks), block(kTraceWaves * 64);
     // scene size (DeviceScene::num_attributes, filled by the caller as main.cu:166 does; 0 = unknown): a tree of kPrefetchMinPrims
     // primitives is 1 GB of nodes + leaves, four times the Infinity Cache

@@ -3,7 +3,7 @@ a vote under which no unfinished lane has more than kStackLds - kLeanMargin = 12
 the leaf phase that follows it, with pushes and pops that go straight to the LDS column; under any other vote the same sites
 take the full ladders (LDS / private / dropped).  A wave may change arm at every vote and both arms work on one stack, so
 nothing a ray computes may change: every comparison here is exact -- frame bytes and sum(box tests) / sum(triangle tests)
-against the oracle.  (The cases hold for every value of RT_TRACE_LEAN_STEP: 2, as shipped, and the two-copy arm 1.)
+against the oracle.  (The cases hold for every value of RT_TRACE_LEAN_STEP: 2, as shipped, and 0, every vote on the full ladders.)
 
 The oracle's counters say which path a case takes: oc[2] is the deepest stack of any ray of the frame, counted as the
 reference counts it (the nearest child's push included, which the kernel keeps in a register: the kernel's deepest sp is

@@ -1,16 +1,16 @@
 """GPU parity on the two fetch paths of the tracer's hot loop (csrc/rt_traverse.hpp), on the frames that stress them:
 
-* the leaf phase reads a leaf as four 16-byte requests issued together (all sixteen dwords, the unused ones included);
-* box_step_wave / box_step_shared (the -DRT_TRACE_UNIFORM_MAX experiment arm; not in the shipped library, which these tests
-  run against unless the library path is pointed at an arm): while every stepping lane of a wave sits on the same node pair, the
-  pair is read once per wave through the scalar path; the first step that finds the lanes apart sends the rest of that
-  traversal down the per-lane vector path.
+* the box phase reads a node pair as four 16-byte requests per lane, a lone slot twice;
+* the leaf phase reads a leaf as four 16-byte requests issued together (all sixteen dwords, the unused ones included).
+
+(The cases were written when the loop also carried an arm that read a pair shared by a whole wave once, through the scalar
+path; that arm is retired, DESIGN section 5, and the cases remain as parity cases of the plain and leaf fetch paths.)
 
 Neither may change a ray's own sequence of tests, so every comparison here is exact: frame bytes and sum(box tests) /
 sum(triangle tests) against the oracle, through the public rt.Trace / rt.IntersectRays.
 
 * frames whose rays all share one path: one large triangle, 1- and 2-triangle trees, root count 1 (SAH) and 2 (LBVH);
-* a SAH tree re-packed into nodes of more than two slots (shared steps through advance()'s count > 2 branch and the lone slot);
+* a SAH tree re-packed into nodes of more than two slots (steps through advance()'s count > 2 branch and the lone slot);
 * a top-down frame (shared upper tree, then divergence) as a whole, in row bands, at 4 spp and in interleaved strips;
 * any-hit queries (a lane leaves the traversal at its first hit while its neighbours go on);
 * the counters of 7 frames traced concurrently on 7 streams."""
@@ -75,9 +75,9 @@ def test_every_ray_shares_one_path(rt, scenes, ora, tree, ntris):
 
 @pytest.mark.parametrize("width", [3, 4, 7])
 def test_sah_tree_with_nodes_wider_than_a_pair(rt, scenes, ora, width):
-    """A SAH tree re-packed into nodes of up to `width` slots under a top-down camera: the shared steps at the top of the
-    tree walk such nodes two slots at a time (cur advances inside the node, identically in every lane) and end in a lone slot
-    for odd counts."""
+    """A SAH tree re-packed into nodes of up to `width` slots under a top-down camera: the steps at the top of the
+    tree, which all rays of a tile share, walk such nodes two slots at a time (cur advances inside the node, identically in
+    every lane) and end in a lone slot for odd counts."""
     G = 24
     tris = scenes.grid_mesh(G, 3)
     s = ora.build_sah(tris)

@@ -1,34 +1,27 @@
 #!/bin/bash
-# The lean vote of the hold-at-pop traversal (rt_traverse.hpp kLeanMargin) and its trims, alternating on one GPU:
-#   lean0  -DRT_TRACE_LEAN_STEP=0                        every vote runs the full push / pop ladders: the parent's loop
-#   lean   -DRT_TRACE_LEAN_STEP=1                        two loops: a vote with every lane outside the margin runs the LDS-only arm
-#   site   -DRT_TRACE_LEAN_STEP=2                        one loop; every push / pop site branches on the vote's wave-uniform flag
-#   sel    -DRT_TRACE_LEAN_SELECT=1                      lean + advance() as selects
-#   hv     -DRT_TRACE_HOLD_VECTOR=1                      lean + quad_hold's combine in vector operations
-#   leanr / siter  -DRT_TRACE_QUAD_WAIT_SECOND=1         lean / site + the hold rule before both steps of a vote
-#   pad8 / pad16  -DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=8|16   the parent's loop with N more vector instructions per box step
-#   pair0 / pair  -DRT_TRACE_PAIR_STEP=0|1                     every vote runs the general box step / narrow votes run the pair-local one (shipped)
+# The lean vote (rt_traverse.hpp kLeanMargin) and the pair-local step of the hold-at-pop traversal, alternating on one GPU:
+#   lean0  -DRT_TRACE_LEAN_STEP=0                        every vote runs the full push / pop ladders
+#   site   -DRT_TRACE_LEAN_STEP=2                        every push / pop site branches on the vote's wave-uniform flag (shipped)
+#   pair0 / pair  -DRT_TRACE_PAIR_STEP=0|1               every vote runs the general box step / narrow votes run the pair-local one (shipped)
+# (The arms lean, sel, hv, leanr, siter, pad8 and pad16 of profiles/lean_step_bench.txt were retired with their knobs: DESIGN section 5.)
 # A library built elsewhere (the parent commit's) joins as arm NAME when copied to csrc/librt_amd_exp_NAME.so.
 # Build the arms first (where hipcc is):   bash tools/lean_step_arms.sh build
-# Run (on the GPU, from the repo root):    ARMS="lean0 lean sel" bash tools/lean_step_arms.sh run <out dir> <runs> [bench.py arguments]
+# Run (on the GPU, from the repo root):    ARMS="lean0 site pair0" bash tools/lean_step_arms.sh run <out dir> <runs> [bench.py arguments]
 #   every run is bench.py's own line; the last line of a run block is min - max per arm
 set -o pipefail
 cd "$(dirname "$0")/.." || exit 1
 C=gpu-raytracing_amd/csrc
-ARMS=(${ARMS:-lean0 lean})
+ARMS=(${ARMS:-lean0 site})
 flags() {
   case $1 in
-    lean0) echo "-DRT_TRACE_LEAN_STEP=0";; lean) echo "-DRT_TRACE_LEAN_STEP=1";; site) echo "-DRT_TRACE_LEAN_STEP=2";; sel) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_LEAN_SELECT=1";;
-    hv) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_HOLD_VECTOR=1";; leanr) echo "-DRT_TRACE_LEAN_STEP=1 -DRT_TRACE_QUAD_WAIT_SECOND=1";;
-    siter) echo "-DRT_TRACE_LEAN_STEP=2 -DRT_TRACE_QUAD_WAIT_SECOND=1";;
+    lean0) echo "-DRT_TRACE_LEAN_STEP=0";; site) echo "-DRT_TRACE_LEAN_STEP=2";;
     pair0) echo "-DRT_TRACE_PAIR_STEP=0";; pair) echo "-DRT_TRACE_PAIR_STEP=1";;
-    pad8) echo "-DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=8";; pad16) echo "-DRT_TRACE_LEAN_STEP=0 -DRT_EXP_BOX_PAD=16";;
     *) return 1;;
   esac
 }
 if [ "$1" = build ]; then
   shift
-  for a in ${@:-lean0 lean site sel hv leanr siter pad8 pad16}; do
+  for a in ${@:-lean0 site pair0 pair}; do
     f=$(flags $a) || { echo "unknown arm $a"; exit 2; }
     make -s -j8 -C $C librt_amd_exp.so EXPFLAGS="$f" EXPNAME=librt_amd_exp_$a.so || exit 1
   done

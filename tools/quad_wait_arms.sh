@@ -3,8 +3,7 @@
 #   qw0  -DRT_TRACE_QUAD_WAIT=0   no instantiation holds: the parent's kernels
 #   qw1  -DRT_TRACE_QUAD_WAIT=1   the 64-VGPR instantiations (render types 0 - 2) of cache-resident scenes hold
 #   qw2  -DRT_TRACE_QUAD_WAIT=2   the shaded instantiations as well (measure with tools/shade_bench.py)
-#   qw1r qw1 with -DRT_TRACE_QUAD_WAIT_SECOND=1: the rule is evaluated before the second step of a vote as well
-# ARMS="qw0 qw1r" bash tools/quad_wait_arms.sh run ...   picks the arms of a run (default: qw0 qw1)
+# ARMS="qw0 qw2" bash tools/quad_wait_arms.sh run ...   picks the arms of a run (default: qw0 qw1)
 # Build the arms first (where hipcc is):   bash tools/quad_wait_arms.sh build
 # Run (on the GPU, from the repo root):    bash tools/quad_wait_arms.sh run <out dir> <runs> [bench.py arguments]
 #   every run is bench.py's own line: `value` with the frames in flight it was asked for, serial_mrays beside it
@@ -16,7 +15,6 @@ if [ "$1" = build ]; then
   for a in qw0 qw1 qw2; do
     make -s -j8 -C $C librt_amd_exp.so EXPFLAGS="-DRT_TRACE_QUAD_WAIT=${a#qw}" EXPNAME=librt_amd_exp_$a.so || exit 1
   done
-  make -s -j8 -C $C librt_amd_exp.so EXPFLAGS="-DRT_TRACE_QUAD_WAIT=1 -DRT_TRACE_QUAD_WAIT_SECOND=1" EXPNAME=librt_amd_exp_qw1r.so || exit 1
 elif [ "$1" = run ]; then
   O=$2; N=$3; shift 3; mkdir -p $O
   for r in $(seq 1 $N); do

@@ -313,7 +313,8 @@ def run_wave(rays, hold, second=False, pair=0):
     """The kernel's loop (trace_ray) over the 64 lanes of a tile, lanes 4q .. 4q+3 = quad q.  Returns dict(nbox, nleaf,
     box_instr, lane_steps, requests): nbox / nleaf are the wave's counters 2 / 3, box_instr the box steps that ran with at
     least one lane, req_* the lane requests (quad_requests) summed over those steps.  second: the second box step under a
-    vote evaluates the rule again (RT_TRACE_QUAD_WAIT_SECOND = 1); the shipped kernel steps every lane in PH_STEP there.
+    vote evaluates the rule again; the shipped kernel steps every lane in PH_STEP there.  (The kernel arm of it,
+    RT_TRACE_QUAD_WAIT_SECOND = 1, was retired: TA busy -19 %, but -2.4 % in time where the shipped form is +5 %)
     pair: 0 every vote runs the general step; 1 / 2 a narrow vote (1, RT_TRACE_PAIR_STEP = 1: no unfinished lane; 2, the arm
     measured beside it: no lane in PH_STEP -- sits on more than a pair or carries a near) runs both steps in the pair-local form.  narrow / general count the
     votes of each form, tails / carried the pair-local steps that left a near behind for a wider node / across a leaf phase
