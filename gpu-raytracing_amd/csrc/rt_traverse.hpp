@@ -154,12 +154,38 @@ static_assert(kLeanMargin <= kStackLds, "the lean vote's threshold is a stack le
 // The lean margin is untouched: the pair-local form pushes at most once per step.  Nothing in either form makes a lane wait
 // (quad_hold's progress argument holds word for word); one traversal state and one sp, so a wave may change form at every
 // vote.  How the two forms are laid out in the loop, and why: at the vote in trace_ray and profiles/pair_step_asm.txt.
-//   1 (shipped)  narrow votes run the pair-local form: -7.8 % issued instructions, +3.6 % on the headline;
+//   2 (shipped)  the EXACT vote below replaces the narrow one as the condition of the pair-local form: two forms, no TAIL, no
+//                lone slot, the pair fetched at a 32-bit offset: +1.0 % on the headline over 1, +6 % at 16 spp (DESIGN section 5,
+//                profiles/exact_pair_bench.txt);
+//   1            narrow votes run the pair-local form: -7.8 % issued instructions, +3.6 % on the headline over 0;
 //   0            every vote runs the general step: the loop before this knob, instruction for instruction.
 #ifndef RT_TRACE_PAIR_STEP
-#define RT_TRACE_PAIR_STEP 1
+#define RT_TRACE_PAIR_STEP 2
 #endif
 constexpr int kPairStep = RT_TRACE_PAIR_STEP;
+static_assert(kPairStep >= 0 && kPairStep <= 2, "RT_TRACE_PAIR_STEP is 0 (general step), 1 (narrow vote) or 2 (exact vote)");
+
+// The exact vote (kPairStep == 2).  launch_trace gets a node pointer, not a node count, so the kernel cannot know at launch
+// that every pair lies within 4 GiB of p.nodes; the vote establishes it from the data.  A cur is EXACT when its count is 2
+// and its index is at most 2^27 - 2: then cur << 5 is the pair's byte offset without wrapping 32 bits, the pair's 64 bytes
+// end below 4 GiB, and the four loads are scalar base + one 32-bit lane offset + 0 / 16 / 32 / 48 -- no 64-bit arithmetic, no
+// `two`, no second address.  One compare on the packed word: count 2 is bit 30 alone, so cur - 2^30 is the index.
+// A vote is exact iff no unfinished lane carries a near and every unfinished lane's cur is exact (the lane set the narrow
+// rule counts).  An exact vote runs both steps in the pair-local form on the short address; any other vote the general step.
+// The vote has only seen the cur a lane brought to it.  After the first step cur is a popped entry or the near child: anything.
+// The second step's lane mask is therefore PH_STEP && exact_cur(cur): a lane whose new cur is a lone slot, a node of more
+// than two slots or a pair beyond the edge sits the step out, as a held lane sits out the first.  So the form has no TAIL
+// and no lone slot, and no lane of an exact vote starts a step with a carried near: the first step ends in advance (near_e
+// untouched) or a park, and the second writes near_e only when it parks.  Each ray's sequence of tests, pushes and pops is
+// the general form's; only the interleaving across lanes changes.
+// Progress (beside quad_hold's argument): a lane that sits out is in PH_STEP / PH_STEP_POP with an inexact cur, so it is
+// unfinished and makes the NEXT vote a general one.  A general vote steps every lane in PH_STEP that is not held, and for
+// those the hold rule's own argument is unchanged: the unfinished lane of a quad with the greatest sp never holds.  An exact
+// vote itself steps every lane of `stepping` in its first step (all exact, and a vote is taken only with stepping != 0), so
+// every pass of the loop still steps a lane or runs a leaf phase, and no lane sits out two votes in a row for this rule.
+constexpr uint32_t kExactIndices = 0x07FFFFFFu;   // 2^27 - 1: the pair indices whose 64 bytes end at or below 4 GiB
+static_assert(((uint64_t)(kExactIndices - 1) << 5) + 64 <= (1ull << 32), "the last exact pair ends at 4 GiB");
+__device__ __forceinline__ bool exact_cur(uint32_t cur) { return (cur - (2u << 29)) < kExactIndices; }
 
 // per-lane traversal state.  PH_STEP_POP (QW traversals only): PH_STEP whose cur was popped from the stack, from level sp.
 enum : uint32_t { PH_STEP = 0, PH_LEAF0 = 1, PH_LEAF1 = 2, PH_DONE = 3, PH_STEP_POP = 4 };
@@ -356,9 +382,19 @@ __device__ __forceinline__ void pair_step_on(const Ray& r, Trav& t, bool two, co
 
 // One box step of a lane: both slots of the current pair are loaded (four 16-byte vector loads issued together), then tested.
 // PAIR (QW only): 0 the general tests, 1 / 2 the pair-local ones of a narrow vote (1: its first step, no TAIL; 2: its second).
+// 3 (QW only): a step of an exact vote (kPairStep == 2) -- cur is a pair below kExactIndices: one 32-bit offset off p.nodes, four
+// loads at 0 / 16 / 32 / 48 from it, slot 1 always there, no TAIL.
 template <bool PF, bool QW = false, int PAIR = 0, class Params>
 __device__ __forceinline__ void box_step(const Params& p, const Ray& r, Trav& t, bool lean = false)
 {
+    if constexpr (QW && PAIR == 3) {
+        static_assert(!PF, "the exact form loads its pair itself");
+        // cur << 5 drops the count (2: bit 30) and index bits 28 / 27 (zero: exact_cur): the pair's byte offset, below 4 GiB
+        const uint4* np = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(p.nodes) + (uint64_t)(uint32_t)(t.cur << 5));
+        const uint4 a0 = np[0], b0 = np[1], a1 = np[2], b1 = np[3];
+        pair_step_on<false>(r, t, true, a0, b0, a1, b1, lean);
+        return;
+    }
     const uint32_t cnt = t.cur >> 29;
     const uint4* np = reinterpret_cast<const uint4*>(p.nodes + (t.cur & kIndexMask));
     const bool two = cnt > 1;
@@ -411,6 +447,15 @@ __device__ __forceinline__ void quad_vote_steps(const Params& p, const Ray& r, T
 {
     if (go) box_step<PF, true, NARROW ? 1 : 0>(p, r, t, lean);
     if ((t.phase & 3u) == PH_STEP) box_step<PF, true, NARROW ? 2 : 0>(p, r, t, lean);
+}
+
+// The two box steps of an EXACT vote (kPairStep == 2): the first as above -- the vote has seen every unfinished lane's cur --
+// the second steps the lanes in PH_STEP whose NEW cur is exact as well; the others sit it out (progress: at exact_cur).
+template <bool PF, bool ANY, class Params>
+__device__ __forceinline__ void exact_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
+{
+    if (go) box_step<PF, true, 3>(p, r, t, lean);
+    if (((t.phase & 3u) == PH_STEP) & exact_cur(t.cur)) box_step<PF, true, 3>(p, r, t, lean);
 }
 
 // The leaf phase's fetch: a leaf (64 bytes) in four 16-byte requests issued together.  The empty asm "uses" all sixteen dwords:
@@ -468,12 +513,20 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
                 // (held lanes counted on the stepping side of this threshold instead: measured, no different -- DESIGN section 5)
                 if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
                 nbox += 2;
-                // the narrow vote (RT_TRACE_PAIR_STEP): no unfinished lane sits on more than a pair or carries a near.  The two
+                // the vote's form (RT_TRACE_PAIR_STEP).  2, shipped: exact -- no unfinished lane carries a near or sits on anything
+                // but an exact pair; 1: narrow -- none sits on more than a pair or carries a near.  Either way the two
                 // forms are two `if`s in a row, not if / else, and the compiler must not see that one flag decides both: as
                 // alternatives that meet at the loop's end, the general form keeps the lanes' state in registers of its own and
                 // eleven of them are copied across on each side of every vote (profiles/pair_step_asm.txt)
                 uint64_t wide = ~0ull;
-                if constexpr (kPairStep != 0) {
+                if constexpr (kPairStep == 2) {
+                    // the exact vote (exact_cur): the same ballot, over the same lanes, on the stricter test
+                    // (as three ballots of plain compares combined in scalar the flag loses its v_cndmask / v_cmp_ne pair, but
+                    // the allocator renumbers the whole kernel: not taken, profiles/exact_pair_asm.txt section 5)
+                    wide = __builtin_amdgcn_ballot_w64((t.phase != PH_DONE) & (!exact_cur(t.cur) | (t.near_e != kNoNear)));
+                    if (wide == 0) exact_vote_steps<PF, ANY>(p, r, t, go, lean);
+                    asm volatile("" : "+s"(wide));
+                } else if constexpr (kPairStep != 0) {
                     wide = __builtin_amdgcn_ballot_w64((t.phase != PH_DONE) & (((t.cur >> 29) > 2) | (t.near_e != kNoNear)));
                     if (wide == 0) quad_vote_steps<PF, ANY, true>(p, r, t, go, lean);
                     asm volatile("" : "+s"(wide));

@@ -37,14 +37,19 @@
 //   * TWO FORMS OF A BOX STEP (the same instantiations; RT_TRACE_PAIR_STEP / pair_step_on, rt_traverse.hpp): the nearest
 //     Box child is carried from step to step only inside a node of more than two slots -- advance() resets it at the end of
 //     every other pair, so in an LBVH, a pairs tree or a hybrid tree every pair is entered without one.  One more ballot per
-//     vote asks whether any unfinished lane sits on more than a pair or carries a near.  If none does, the vote is NARROW:
-//     both of its steps decide slot 0, slot 1, the one possible push and the advance from values of the step alone -- no push
-//     site for slot 0, no compare against a carried front, near_e / near_d written only where they outlive the step (a leaf
-//     in slot 1; the first pair of a wider node, which a lane can reach in the second step).  Any other vote runs the general
-//     step.  One traversal state; a wave may change form at every vote, a ray's sequence of tests is the same in both.  The
-//     forms stand one after the other in the loop, each behind its own scalar branch, so that neither moves the lanes' state
-//     between registers.  The bench tree runs narrow on 99 % of its votes: 7.8 % fewer issued instructions per launch,
-//     +3.6 %;
+//     vote asks whether any unfinished lane carries a near or sits on anything but a pair below index 2^27 - 1 (exact_cur:
+//     one compare on the packed word).  If none does, the vote is EXACT: both of its steps decide slot 0, slot 1, the one
+//     possible push and the advance from values of the step alone -- no push site for slot 0, no compare against a carried
+//     front, near_e / near_d written only where they outlive the step (a leaf in slot 1) -- and fetch the pair at scalar
+//     base + (cur << 5) as a 32-bit lane offset, four loads off one register with no 64-bit arithmetic (the launch gets a
+//     node pointer, not a node count: the vote establishes from the data that the offset fits).  A lane whose cur is not
+//     exact after the first step -- a lone slot, a wider node, a pair beyond 4 GiB -- sits the second step out and makes the
+//     next vote a general one.  Any other vote runs the general step.  One traversal state; a wave may change form at every
+//     vote, a ray's sequence of tests is the same in both.  The forms stand one after the other in the loop, each behind its
+//     own scalar branch, so that neither moves the lanes' state between registers.  The bench tree has only exact entries:
+//     every vote the narrow rule ran narrow is exact, 98 - 99 % of them (profiles/exact_pair_model.txt), and no lane sits
+//     out.  The pair-local tests: 7.8 % fewer issued instructions per launch, +3.6 %; the short address on top of them:
+//     5.8 % fewer, +1.0 % at 1 spp, +6 % at 16 spp, where the four loads of a pair now issue together;
 //   * a leaf (64 bytes) is fetched with four 16-byte loads issued together, the words no test reads included: left to
 //     itself the compiler narrows them to seven smaller requests, and the address path charges per request;
 //   * the traversal stack is a lane-interleaved LDS column addressed through an address_space(3)

@@ -16,7 +16,7 @@ tmp=$(mktemp -d)
 trap 'git -C "$here" worktree remove --force "$tmp/other" 2>/dev/null; rm -rf "$tmp"' EXIT
 git -C "$here" worktree add --quiet --detach "$tmp/other" "$rev" || exit 2
 
-ARMS="-DRT_TRACE_PAIR_STEP=0 -DRT_TRACE_LEAN_STEP=0 -DRT_TRACE_QUAD_WAIT=0 -DRT_TRACE_QUAD_WAIT=2 -DRT_TRACE_TUNING"
+ARMS="-DRT_TRACE_PAIR_STEP=0 -DRT_TRACE_PAIR_STEP=1 -DRT_TRACE_LEAN_STEP=0 -DRT_TRACE_QUAD_WAIT=0 -DRT_TRACE_QUAD_WAIT=2 -DRT_TRACE_TUNING"
 srcs=$(make -s --no-print-directory -C "$here/$csrc" --eval='_p: ; @echo $(SRCS)' _p)
 cases=()
 for f in $srcs; do cases+=("default||$f"); done

@@ -2,7 +2,8 @@
 # The lean vote (rt_traverse.hpp kLeanMargin) and the pair-local step of the hold-at-pop traversal, alternating on one GPU:
 #   lean0  -DRT_TRACE_LEAN_STEP=0                        every vote runs the full push / pop ladders
 #   site   -DRT_TRACE_LEAN_STEP=2                        every push / pop site branches on the vote's wave-uniform flag (shipped)
-#   pair0 / pair  -DRT_TRACE_PAIR_STEP=0|1               every vote runs the general box step / narrow votes run the pair-local one (shipped)
+#   pair0 / pair  -DRT_TRACE_PAIR_STEP=0|1               every vote runs the general box step / narrow votes run the pair-local one
+#   exact         -DRT_TRACE_PAIR_STEP=2                 exact votes run the pair-local step on a 32-bit pair offset (shipped)
 # (The arms lean, sel, hv, leanr, siter, pad8 and pad16 of profiles/lean_step_bench.txt were retired with their knobs: DESIGN section 5.)
 # A library built elsewhere (the parent commit's) joins as arm NAME when copied to csrc/librt_amd_exp_NAME.so.
 # Build the arms first (where hipcc is):   bash tools/lean_step_arms.sh build
@@ -15,13 +16,13 @@ ARMS=(${ARMS:-lean0 site})
 flags() {
   case $1 in
     lean0) echo "-DRT_TRACE_LEAN_STEP=0";; site) echo "-DRT_TRACE_LEAN_STEP=2";;
-    pair0) echo "-DRT_TRACE_PAIR_STEP=0";; pair) echo "-DRT_TRACE_PAIR_STEP=1";;
+    pair0) echo "-DRT_TRACE_PAIR_STEP=0";; pair) echo "-DRT_TRACE_PAIR_STEP=1";; exact) echo "-DRT_TRACE_PAIR_STEP=2";;
     *) return 1;;
   esac
 }
 if [ "$1" = build ]; then
   shift
-  for a in ${@:-lean0 site pair0 pair}; do
+  for a in ${@:-lean0 site pair0 pair exact}; do
     f=$(flags $a) || { echo "unknown arm $a"; exit 2; }
     make -s -j8 -C $C librt_amd_exp.so EXPFLAGS="$f" EXPNAME=librt_amd_exp_$a.so || exit 1
   done

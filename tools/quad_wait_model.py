@@ -19,7 +19,10 @@ leaf-phase iteration counts (counters 2 and 3 of rt_trace) and the requests per 
 run_wave(pair=1|2) adds the two forms of a box step (RT_TRACE_PAIR_STEP, csrc/rt_traverse.hpp): a NARROW vote -- no lane that
 counts sits on more than a pair or carries a near -- runs both of its steps as Ray.pair_step, which asserts what the form
 relies on (no carried near; no node of more than two slots in the first step); any other vote runs Ray.box_step.  pair=1
-counts every unfinished lane (the kernel's rule); pair=2 leaves the parked lanes out (the arm that was measured beside it).
+counts every unfinished lane (the rule of RT_TRACE_PAIR_STEP = 1); pair=2 leaves the parked lanes out (the arm that was measured
+beside it).  pair=3 is the EXACT vote (RT_TRACE_PAIR_STEP = 2, exact_cur): no unfinished lane carries a near and every unfinished
+lane sits on a pair below index 2^27 - 1; both steps run as Ray.pair_step without a tail, and a lane whose cur is not exact
+after the first step sits the second out.
 
 The arithmetic is float64 on the float32 inputs: a model of the schedule, not a second oracle.
 
@@ -43,8 +46,14 @@ NO_NEAR = 0xFFFFFFFF
 STACK_LDS, STACK_MAX = 16, 64            # kStackLds, kStackMax
 PARK_NUM, PARK_DEN = 8, 1                # kParkNum, kParkDen
 STEP, LEAF0, LEAF1, DONE = 0, 1, 2, 3
+EXACT_INDICES = 0x07FFFFFF               # kExactIndices: a pair (count 2) whose index is below this is exact
 CHILD_NONE, CHILD_BOX, CHILD_TRI = 0, 1, 2
 INF = float("inf")
+
+
+def exact_cur(cur):
+    """rt_traverse.hpp exact_cur, on the packed word as the kernel does it (32-bit wrap-around)"""
+    return ((cur - (2 << 29)) & 0xFFFFFFFF) < EXACT_INDICES
 
 
 class Tree:
@@ -178,14 +187,17 @@ class Ray:
             if self.phase == STEP:
                 self.advance()
 
-    def pair_step(self, tail):
+    def pair_step(self, tail, exact=False):
         """pair_step_on: the box step of a pair entered without a carried near, decided from values of the step alone.
         Returns what the step wrote of near_e: None, "leaf1" (parked with the near kept for the leaf phase) or "tail" (the
-        first pair of a node of more than two slots: near kept, cur on the node's next pair)."""
+        first pair of a node of more than two slots: near kept, cur on the node's next pair).  exact: a step of an exact
+        vote, whose loads take cur << 5 as the pair's byte offset."""
         assert self.phase == STEP
         assert self.near_e == NO_NEAR and self.near_d == INF, "a pair-local step starts without a carried near"
         cnt = self.cur >> 29
         assert tail or cnt <= 2, "the first step of a narrow vote never sits on a node of more than two slots"
+        assert not exact or (not tail and exact_cur(self.cur) and ((self.cur << 5) & 0xFFFFFFFF) == (self.cur & INDEX_MASK) * 32), \
+            "a step of an exact vote sits on a pair whose byte offset is cur << 5 in 32 bits"
         self.popped = False
         n = self.cur & INDEX_MASK
         two = cnt > 1
@@ -318,17 +330,19 @@ def run_wave(rays, hold, second=False, pair=0):
     pair: 0 every vote runs the general step; 1 / 2 a narrow vote (1, RT_TRACE_PAIR_STEP = 1: no unfinished lane; 2, the arm
     measured beside it: no lane in PH_STEP -- sits on more than a pair or carries a near) runs both steps in the pair-local form.  narrow / general count the
     votes of each form, tails / carried the pair-local steps that left a near behind for a wider node / across a leaf phase
-    (of those, wide_carried on the first pair of a node of more than two slots).  Raises if a pass of the loop neither steps
-    a lane nor runs a leaf phase."""
+    (of those, wide_carried on the first pair of a node of more than two slots).  pair = 3: the exact vote (RT_TRACE_PAIR_STEP = 2);
+    exact counts its votes, sat_out the lanes in PH_STEP that sat out a second step because their new cur was not exact, by what
+    it was: sat_wide (more than two slots), sat_lone (a lone slot), sat_far (a pair from index 2^27 - 1 up).  Raises if a pass of
+    the loop neither steps a lane nor runs a leaf phase."""
     quads = [rays[q:q + 4] for q in range(0, len(rays), 4)]
     nbox = nleaf = box_instr = lane_steps = 0
     requests = [0, 0, 0]
-    forms = dict(narrow=0, general=0, tails=0, carried=0, wide_carried=0)
+    forms = dict(narrow=0, general=0, tails=0, carried=0, wide_carried=0, exact=0, sat_out=0, sat_wide=0, sat_lone=0, sat_far=0)
 
     def going():
         return [r for qd in quads for k, r in enumerate(qd) if r.phase == STEP and not (hold and holds(qd, k))]
 
-    def step(go, narrow=False, tail=False):
+    def step(go, narrow=False, tail=False, exact=False):
         nonlocal box_instr, lane_steps
         if not go:
             return
@@ -341,7 +355,7 @@ def run_wave(rays, hold, second=False, pair=0):
         for r in go:
             if narrow:
                 wide = (r.cur >> 29) > 2
-                left = r.pair_step(tail)
+                left = r.pair_step(tail, exact)
                 forms["tails"] += left == "tail"
                 forms["carried"] += left == "leaf1" and r.near_e != NO_NEAR
                 forms["wide_carried"] += left == "leaf1" and r.near_e != NO_NEAR and wide
@@ -355,6 +369,22 @@ def run_wave(rays, hold, second=False, pair=0):
             if not go or len(go) * PARK_DEN < parked * PARK_NUM:
                 break
             nbox += 2
+            if pair == 3:
+                if any(r.phase != DONE and (not exact_cur(r.cur) or r.near_e != NO_NEAR) for r in rays):
+                    forms["general"] += 1
+                    step(go)
+                    step(going() if second else [r for r in rays if r.phase == STEP])
+                else:
+                    forms["exact"] += 1
+                    step(go, True, False, True)        # (never empty: the vote is taken with a lane that steps)
+                    nxt = going() if second else [r for r in rays if r.phase == STEP]
+                    for r in nxt:
+                        if not exact_cur(r.cur):
+                            cnt = r.cur >> 29
+                            forms["sat_out"] += 1
+                            forms["sat_wide" if cnt > 2 else "sat_lone" if cnt < 2 else "sat_far"] += 1
+                    step([r for r in nxt if exact_cur(r.cur)], True, False, True)
+                continue
             counts = [r for r in rays if (r.phase != DONE if pair == 1 else r.phase == STEP)]
             narrow = pair != 0 and not any((r.cur >> 29) > 2 or r.near_e != NO_NEAR for r in counts)
             forms["narrow" if narrow else "general"] += 1
@@ -405,7 +435,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--wave", action="store_true", help="the kernel's schedule over whole 8 x 8 tiles")
-    ap.add_argument("--pair", type=int, choices=[0, 1, 2], default=0, help="with --wave: narrow votes run the pair-local step (1: the kernel's rule, 2: parked lanes left out)")
+    ap.add_argument("--pair", type=int, choices=[0, 1, 2, 3], default=0, help="with --wave: narrow votes run the pair-local step (1: every unfinished lane counts, 2: parked lanes left out); 3: the exact vote of RT_TRACE_PAIR_STEP = 2")
     a = ap.parse_args()
     scenes = importlib.import_module("gpu-raytracing_amd.scenes")
     from oracle import oracle_py as ora
@@ -435,7 +465,9 @@ def main():
                     f"box instructions {tot['box_instr'] / n:.1f}  lanes per instruction {tot['lane_steps'] / max(tot['box_instr'], 1):.1f}  "
                     f"requests per lane step any/on/full {req}  "
                     f"requests per box instruction any/on/full " + " / ".join(f"{tot[k] / max(tot['box_instr'], 1):.1f}" for k in ("req_any", "req_on", "req_full")))
-            if a.pair:
+            if a.pair == 3:
+                line += f"  exact votes {100.0 * tot['exact'] / max(tot['exact'] + tot['general'], 1):.1f} %  lanes that sat out a second step {tot['sat_out']}"
+            elif a.pair:
                 line += f"  narrow votes {100.0 * tot['narrow'] / max(tot['narrow'] + tot['general'], 1):.1f} %"
         else:
             line = (f"{name:12s} requests per lane step any/on/full {req}   rounds per quad {tot['rounds'] / n:.1f}   "
