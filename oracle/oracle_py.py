@@ -560,3 +560,88 @@ def ref_trace(leaves, nodes, root, count, camera, w, h, *, render_type=0, attrib
                             None if table is None else ctypes.cast(table, ctypes.c_void_p), len(textures or ()),
                             _p(lt), w, h, render_type, _p(rgba), _p(tests))
     return rgba, tests
+
+
+# ---------------------------------------------------------------- the reference's SAH task builder, run on the CPU
+# oracle/_ref/libref_sah.so: SharedTaskBuilder.cu from the reference tree, #included by oracle/ref_sah_driver.cpp, which
+# runs a block with one host thread per CUDA thread and hands the turn round in threadIdx.x order between barriers;
+# and ExtractDepth of BottomUpBuilder.cu (oracle/ref_extract_depth_driver.cpp).  Nothing here loads libref_kernels.so.
+REF_SAH_PATH = os.path.join(_HERE, "_ref", "libref_sah.so")
+AABB6 = np.dtype(("<f4", 6))
+_refs = None
+
+CHILD_BOX, CHILD_TRI = 1, 2     # ChildType (Common.cuh:36-42)
+
+
+def ref_sah_available() -> bool:
+    return os.path.exists(REF_SAH_PATH)
+
+
+def _refsah():
+    global _refs
+    if _refs is None:
+        R = ctypes.CDLL(REF_SAH_PATH)
+        vp, u32, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+        R.ref_shared_task_build.argtypes = [u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, u32, vp]
+        R.ref_shared_task_build.restype = ci
+        R.ref_extract_depth.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32]
+        R.ref_extract_depth.restype = ci
+        _refs = R
+    return _refs
+
+
+def ref_shared_task_build(blocks: int, width: int, c_aabbs, p_aabbs, nodes: np.ndarray, aabbs, prim_ids, ids,
+                          block_counts, block_scan, num_leaves: int, top_of_tree: bool, leaf_type: int,
+                          base_write_offset: int) -> np.ndarray:
+    """SharedTaskBuild<<<blocks, width>>> (SharedTaskBuilder.cu:909-995) of the reference, run on the CPU; arguments as
+    the kernel names them.  nodes (NODE records) is written in place.  ids: the first id buffer (`scratch`): position
+    block_scan[b] + i holds the i-th item of block b; the second buffer and the task queue are allocated here.
+    c_aabbs / p_aabbs: one box (6 floats) per block; aabbs: one box per item id; prim_ids: (id, count) per item id.
+    Returns the kernel's `error` flag per block."""
+    _refsah()
+    counts = np.ascontiguousarray(block_counts, np.int32)
+    scan = np.ascontiguousarray(block_scan, np.int32)
+    ids = np.ascontiguousarray(ids, np.int32)
+    c = np.ascontiguousarray(c_aabbs, np.float32).reshape(-1, 6)
+    p = np.ascontiguousarray(p_aabbs, np.float32).reshape(-1, 6)
+    boxes = np.ascontiguousarray(aabbs, np.float32).reshape(-1, 6)
+    prims = np.ascontiguousarray(prim_ids, np.uint32).reshape(-1, 2)
+    assert nodes.dtype == NODE and nodes.flags.c_contiguous and nodes.flags.writeable
+    assert counts.shape[0] >= blocks and c.shape[0] >= blocks and p.shape[0] >= blocks
+    ends = [int(scan[b]) + int(counts[b]) for b in range(blocks) if counts[b]]
+    span = max(ends, default=0)
+    assert span <= num_leaves and ids.shape[0] >= span
+    used = np.concatenate([ids[int(scan[b]):int(scan[b]) + int(counts[b])] for b in range(blocks)] or [ids[:0]])
+    if top_of_tree:      # the items are block indices: their boxes, and their scan for the sub-root slot
+        assert used.size == 0 or (0 <= used.min() and used.max() < min(boxes.shape[0], scan.shape[0]))
+        assert nodes.shape[0] >= 128 + 2 * (int(scan[used].max()) if used.size else 0) + 1
+    else:
+        assert used.size == 0 or (0 <= used.min() and used.max() < min(boxes.shape[0], prims.shape[0]))
+    first = base_write_offset if top_of_tree else base_write_offset + 2 * int(min(scan[:blocks]))
+    assert nodes.shape[0] >= first + 2 * span + 2, "every task claims at most two slots per item"
+    scratch = np.zeros(2 * max(num_leaves, 1), np.int32)
+    scratch[:span] = ids[:span]
+    tasks = np.zeros(max(num_leaves, 1) + 64, np.dtype(("<u4", 16)))
+    nl = np.array([num_leaves], np.int32)
+    errors = np.zeros(blocks, np.int32)
+    rc = _refsah().ref_shared_task_build(blocks, width, _p(tasks), _p(c), _p(p), _p(nodes), _p(boxes), _p(prims),
+                                         _p(scratch), _p(counts), _p(scan), _p(nl), int(bool(top_of_tree)),
+                                         int(leaf_type), base_write_offset, _p(errors))
+    assert rc == 0, "ref_shared_task_build: width outside [64, 1024] or a thread could not be started"
+    return errors
+
+
+def ref_extract_depth(nodes: np.ndarray, aabb_ordered: np.ndarray, num_leaves: int):
+    """ExtractDepth<<<1, 256>>>(nodes, ..., root 0, depth 8, num_leaves) (BottomUpBuilder.cu:314-371), threads in tid
+    order (oracle/ref_extract_depth_driver.cpp, part of libref_sah.so).  Returns (sub-root pair slots [K], their boxes [K, 6], c_aabb: the union of those boxes grown from the empty
+    float box, p_aabb: the scene box as floats)."""
+    _refsah()
+    nd = np.ascontiguousarray(nodes).copy()
+    idx = np.zeros((256, 2), np.uint32)
+    boxes = np.zeros((256, 6), np.float32)
+    fmax = np.finfo(np.float32).max
+    c = np.array([fmax] * 3 + [-fmax] * 3, np.float32)          # empty_float_aabb (BuildWrapper.cu:290-291)
+    p = np.ascontiguousarray(aabb_ordered, np.int32).copy()
+    k = int(_refsah().ref_extract_depth(_p(nd), _p(idx), _p(boxes), _p(c), _p(p), 0, 8, num_leaves))
+    assert (idx[:k, 1] == 2).all()
+    return idx[:k, 0].copy(), boxes[:k].copy(), c, p.view(np.float32)

@@ -5,7 +5,9 @@
 // - launch coordinates are thread_local, so a driver may run rows of one launch on several host threads;
 // - atomics are the GCC __atomic builtins (sequentially consistent), templated on (pointer type, operand type)
 //   because the reference calls e.g. atomicAdd(unsigned*, int);
-// - a fence or barrier is a no-op: the driver only emulates kernels that do not synchronise within a block;
+// - a fence or barrier is a no-op: ref_kernels_driver.cpp only emulates kernels that do not synchronise within a block.
+//   ref_sah_driver.cpp (SharedTaskBuilder.cu: __shared__ variables, __syncthreads(), integer atomics) is compiled with
+//   -DREF_BLOCK_BARRIER, under which __syncthreads() is a function that driver supplies;
 // - surf2Dwrite writes into a RefSurface (ours), whose address is passed in place of a cudaSurfaceObject_t.
 #ifndef REF_CUDA_HOST_H
 #define REF_CUDA_HOST_H
@@ -103,7 +105,11 @@ template <class T, class U, class V> inline T atomicCAS(T* a, U expected, V desi
     return e;
 }
 
+#ifdef REF_BLOCK_BARRIER
+void __syncthreads();   // ref_sah_driver.cpp: a real block barrier (one host thread per CUDA thread, run in turn)
+#else
 inline void __syncthreads() {}
+#endif
 inline void __threadfence() {}
 
 struct RefSurface {
