@@ -64,6 +64,10 @@ RT_MOTION_TOPOLOGY_MISMATCH = 1    # rt_motion_validate's status flag
 # instancing (rt_prepare_instances / rt_intersect_rays_instanced)
 INSTANCE = np.dtype([("object_to_world", "<f4", (3, 4)), ("blas", "<u4"), ("pad", "<u4", 3)])                # 64 B
 INSTANCE_RECORD = np.dtype([("world_to_object", "<f4", (3, 4)), ("blas", "<u4"), ("flags", "<u4"), ("spare", "<u4", 2)])
+MOTION_INSTANCE = np.dtype([("object_to_world0", "<f4", (3, 4)), ("object_to_world1", "<f4", (3, 4)), ("blas", "<u4"),
+                            ("pad", "<u4", 7)])                                                                 # 128 B
+MOTION_INSTANCE_RECORD = np.dtype([("object_to_world0", "<f4", (3, 4)), ("object_to_world1", "<f4", (3, 4)), ("blas", "<u4"),
+                                   ("flags", "<u4"), ("spare", "<u4", 6)])                                      # 128 B
 ACCEL = np.dtype([("triangles", "<u8"), ("nodes", "<u8"), ("root", "<u4"), ("count", "<u4")])                # 24 B
 assert INSTANCE.itemsize == 64 and INSTANCE_RECORD.itemsize == 64 and ACCEL.itemsize == 24
 RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
@@ -187,6 +191,16 @@ class _MotionAccel(ctypes.Structure):  # rt_motion_accel
                 ("nodes1", ctypes.c_void_p), ("root", ctypes.c_uint32), ("count", ctypes.c_uint32)]
 
 
+class _MotionInstance(ctypes.Structure):  # rt_motion_instance (MOTION_INSTANCE's mirror)
+    _fields_ = [("object_to_world0", ctypes.c_float * 12), ("object_to_world1", ctypes.c_float * 12),
+                ("blas", ctypes.c_uint32), ("pad", ctypes.c_uint32 * 7)]
+
+
+class _MotionInstanceRecord(ctypes.Structure):  # rt_motion_instance_record (MOTION_INSTANCE_RECORD's mirror)
+    _fields_ = [("object_to_world0", ctypes.c_float * 12), ("object_to_world1", ctypes.c_float * 12),
+                ("blas", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("spare", ctypes.c_uint32 * 6)]
+
+
 class _RefitPlanLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_size_t), ("parents", ctypes.c_size_t), ("arrivals", ctypes.c_size_t),
                 ("leaves", ctypes.c_size_t), ("total", ctypes.c_size_t)]
@@ -198,7 +212,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_radix_sort_u32_pairs", "rt_radix_sort_u32_pairs_bits", "rt_radix_sort_input_in_tmp", "rt_trace", "rt_trace_strips",
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
-           "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_closest_points",
+           "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_prepare_motion_instances",
+           "rt_intersect_rays_instanced_motion", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
@@ -278,6 +293,11 @@ def lib() -> ctypes.CDLL:
     L.rt_prepare_instances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp]
     L.rt_intersect_rays_instanced.restype = i32
     L.rt_intersect_rays_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32, vp, vp]
+    L.rt_prepare_motion_instances.restype = i32
+    L.rt_prepare_motion_instances.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.rt_intersect_rays_instanced_motion.restype = i32
+    L.rt_intersect_rays_instanced_motion.argtypes = [ctypes.POINTER(_MotionAccel), vp, u32, vp, u32, vp, vp, vp, vp, u32, i32, vp,
+                                                     vp]
     L.rt_closest_points.restype = i32
     L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
     L.rt_range_scratch_bytes.restype = ctypes.c_size_t
@@ -725,6 +745,47 @@ def IntersectRaysInstanced(tlas_triangles, tlas_nodes, root: int, count: int, re
                                              int(num_blas), _ptr(rays), _ptr(hits), _ptr(instance_ids), n,
                                              kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
                                              _stream_ptr(stream)), "rt_intersect_rays_instanced")
+
+
+def PrepareMotionInstances(instances, num_instances: int, blas_table, num_blas: int, proxies0, proxies1, records, status,
+                           stream=None) -> None:
+    """rt_prepare_motion_instances: `instances` (MOTION_INSTANCE records, device: two key matrices per instance), the BLAS table
+    (accel_table) -> `proxies0` / `proxies1` (num_instances TRIANGLE records each: the TLAS build input of pose 0 and the refit
+    input of pose 1, e.g. MotionPose's moved_triangles), `records` (MOTION_INSTANCE_RECORD, the query's input) and `status` (a
+    device uint32 the call clears; RT_INSTANCE_* flags, see instance_status).  Asynchronous on `stream`."""
+    n = int(num_instances)
+    for name, buf, size in (("instances", instances, 128), ("proxies0", proxies0, 36), ("proxies1", proxies1, 36),
+                            ("records", records, 128)):
+        if n and (not buf.is_contiguous() or _nbytes(buf) < size * n):
+            raise ValueError(f"{name} must be a contiguous device buffer of {n} {size}-byte records")
+    _check(lib().rt_prepare_motion_instances(_ptr(instances), n, _ptr(blas_table), int(num_blas), _ptr(proxies0), _ptr(proxies1),
+                                             _ptr(records), _ptr(status), _stream_ptr(stream)), "rt_prepare_motion_instances")
+
+
+def IntersectRaysInstancedMotion(tlas_pose0, tlas_pose1, root: int, count: int, records, num_instances: int, blas_table,
+                                 num_blas: int, rays, times, hits, instance_ids, *, any_hit: bool = False, counters=None,
+                                 stream=None) -> None:
+    """rt_intersect_rays_instanced_motion: IntersectRaysInstanced with a time per ray over two key transforms of every instance.
+    tlas_pose0 / tlas_pose1: (triangles, nodes) pairs or BuildInputs -- pose 0 the TLAS built over PrepareMotionInstances's
+    proxies0, pose 1 from MotionPose(tlas, root, count, proxies1).  `records`: PrepareMotionInstances's.  `times`: a contiguous
+    device float32 tensor, one value in [0, 1] per ray (NaN or outside: a miss).  hits / instance_ids / any_hit / counters as for
+    IntersectRaysInstanced.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or not times.is_contiguous() \
+            or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, times / hits / instance_ids contiguous "
+                         "device buffers")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n or _nbytes(times) < 4 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records, instance_ids {n} words and times {n} floats")
+    if num_instances and (not records.is_contiguous() or _nbytes(records) < 128 * int(num_instances)):
+        raise ValueError(f"records must be a contiguous device buffer of {int(num_instances)} 128-byte records")
+    if n == 0:
+        return
+    a = _motion_accel(tlas_pose0, tlas_pose1, root, count)
+    _check(lib().rt_intersect_rays_instanced_motion(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                    int(num_blas), _ptr(rays), _ptr(times), _ptr(hits), _ptr(instance_ids), n,
+                                                    kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_motion")
 
 
 def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, counters=None, status=None, stream=None) -> None:

@@ -34,6 +34,7 @@
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
 #include "rt_instance_filter.hpp"
+#include "rt_instance_proxy.hpp"
 #include "rt_instance_traverse.hpp"
 #include "rt_traverse.hpp"
 
@@ -49,8 +50,6 @@ namespace rt {
 
 namespace {
 
-constexpr float kInstancePad = 1.0f / 4096.0f;      // 2^-12 of the box's largest |bound| (rt_abi.h)
-
 // ---------------------------------------------------------------- prepare
 __global__ __launch_bounds__(256) void prepare_instances_kernel(const rt_instance* instances, uint32_t num_instances,
                                                                 const rt_accel* blas_table, uint32_t num_blas,
@@ -63,27 +62,9 @@ __global__ __launch_bounds__(256) void prepare_instances_kernel(const rt_instanc
     const float* m = in.object_to_world;
     uint32_t flags = 0;
 
-    // the object box: ordered min / max over the non-NONE slots of the root run
+    // the object box: ordered min / max over the non-NONE slots of the root run (rt_instance_proxy.hpp)
     int lo_i[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, hi_i[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    bool any = false;
-    if (in.blas >= num_blas) flags |= RT_INSTANCE_BAD_BLAS;
-    else {
-        const rt_accel a = blas_table[in.blas];
-        if (a.count == 0 || a.count > 7 || !a.nodes || !a.triangles) flags |= RT_INSTANCE_BAD_BLAS;
-        else {
-            for (uint32_t s = 0; s < a.count; s++) {
-                const rt_node nd = a.nodes[(a.root & kIndexMask) + s];
-                if ((nd.w28 >> 29) == RT_CHILD_NONE) continue;
-                any = true;
-                const float mn[3] = {nd.min.x, nd.min.y, nd.min.z}, mx[3] = {nd.max.x, nd.max.y, nd.max.z};
-                for (int k = 0; k < 3; k++) {
-                    lo_i[k] = min(lo_i[k], float_to_ordered_int(mn[k]));
-                    hi_i[k] = max(hi_i[k], float_to_ordered_int(mx[k]));
-                }
-            }
-            if (!any) flags |= RT_INSTANCE_BAD_BLAS;
-        }
-    }
+    instance_object_box(blas_table, num_blas, in.blas, lo_i, hi_i, flags);
 
     // world_to_object in double: adjugate / det of the 3x3 part, translation -W3 * t
     bool finite = true;
@@ -118,26 +99,9 @@ __global__ __launch_bounds__(256) void prepare_instances_kernel(const rt_instanc
 
     rt_triangle px = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};   // flagged: a point proxy at the origin
     if (!flags) {
-        // corners through object_to_world; their ordered min / max (-0 below +0: no dependence on fminf's zero rule)
-        float lo[3], hi[3], b0[3], b1[3];
-        int clo[3] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, chi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-        for (int k = 0; k < 3; k++) { b0[k] = ordered_int_to_float(lo_i[k]); b1[k] = ordered_int_to_float(hi_i[k]); }
-        for (int c = 0; c < 8; c++) {
-            const float x = (c & 1) ? b1[0] : b0[0], y = (c & 2) ? b1[1] : b0[1], z = (c & 4) ? b1[2] : b0[2];
-            for (int k = 0; k < 3; k++) {
-                const float v = ((m[4 * k] * x + m[4 * k + 1] * y) + m[4 * k + 2] * z) + m[4 * k + 3];
-                clo[k] = min(clo[k], float_to_ordered_int(v));
-                chi[k] = max(chi[k], float_to_ordered_int(v));
-            }
-        }
-        for (int k = 0; k < 3; k++) { lo[k] = ordered_int_to_float(clo[k]); hi[k] = ordered_int_to_float(chi[k]); }
-        float e = 0.0f;
-        for (int k = 0; k < 3; k++) e = fmaxf(e, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
-        const float pad = e * kInstancePad;
-        for (int k = 0; k < 3; k++) { lo[k] = lo[k] - pad; hi[k] = hi[k] + pad; }
-        px.v0 = {lo[0], lo[1], lo[2]};
-        px.v1 = {hi[0], hi[1], hi[2]};
-        px.v2 = {lo[0] * 0.5f + hi[0] * 0.5f, lo[1] * 0.5f + hi[1] * 0.5f, lo[2] * 0.5f + hi[2] * 0.5f};
+        Affine34 mm;
+        for (int k = 0; k < 12; k++) mm.m[k] = m[k];
+        px = proxy_triangle(instance_proxy(mm, lo_i, hi_i));   // corners through object_to_world, ordered min / max, the pad
     }
     proxies[i] = px;
     if (flags) atomicOr(status, flags);

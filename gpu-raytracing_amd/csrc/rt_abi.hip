@@ -477,6 +477,38 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
                                                 num_rays, mode, num_primitives, nullptr, counters, stream);
 }
 
+int rt_prepare_motion_instances(const rt_motion_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
+                                uint32_t num_blas, rt_triangle* proxies0, rt_triangle* proxies1,
+                                rt_motion_instance_record* records, uint32_t* status, void* stream)
+{
+    if (!status || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances) {
+        if (!instances || !proxies0 || !proxies1 || !records || !blas_table || num_blas == 0) return RT_ERR_INVALID_ARGUMENT;
+        if (misaligned(instances, 16) || misaligned(proxies0, 16) || misaligned(proxies1, 16) || misaligned(records, 16) ||
+            misaligned(blas_table, 8))
+            return RT_ERR_INVALID_ARGUMENT;
+    }
+    return hip_rc(launch_prepare_motion_instances(instances, num_instances, blas_table, num_blas, proxies0, proxies1, records,
+                                                  status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
+                                       uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                                       const rt_ray* rays, const float* times, rt_hit* hits, uint32_t* instance_ids,
+                                       uint32_t num_rays, int mode, uint64_t* counters, void* stream)
+{
+    if (!motion_tree_args(tlas) || !rays || !times || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(times, 4) || misaligned(instance_ids, 4) ||
+        misaligned(records, 16) || misaligned(blas_table, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_instance_motion_query(*tlas, records, num_instances, blas_table, num_blas, rays, times, hits,
+                                               instance_ids, num_rays, mode == RT_RAY_ANY_HIT, counters,
+                                               static_cast<hipStream_t>(stream)));
+}
+
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream)
 {
@@ -729,6 +761,10 @@ const char* rt_version_string(void)
            "ray query's loop and tests | "
            "instances: proxy boxes + double inverse per instance (one launch), TLAS by the existing builders, two-level query "
            "on one 64-entry stack, TLAS leaves as stack entries, per-lane BLAS base pointers, world ray reloaded on exit | "
+           "instance_motion: a time per ray over two key transforms of each instance, proxies of both keys by the instances' "
+           "own arithmetic (one launch), TLAS pose 1 by refit, TLAS steps interpolated as the motion query's (eight 16-byte "
+           "requests), the record's two matrices interpolated and inverted in float32 at the ray's time on entry, static BLAS "
+           "steps on stored bits | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
            "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
            "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "

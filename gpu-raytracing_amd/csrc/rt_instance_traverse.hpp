@@ -65,17 +65,11 @@ __device__ __forceinline__ void inst_second_slot(Trav& t, float tmin, float tmax
     if (is_leaf) { t.leaf = t.e1; t.phase = PH_LEAF1; }
 }
 
-// box_step of rt_traverse.hpp on the lane's own node array, TLAS leaves as entries
+// box_step_on of rt_traverse.hpp on a fetched pair of the lane's own node array, TLAS leaves as entries
 template <bool PF>
-__device__ __forceinline__ void inst_box_step(const LaneNodes& ln, const Ray& r, Trav& t, int base, bool top)
+__device__ __forceinline__ void inst_box_step_on(const LaneNodes& ln, const Ray& r, Trav& t, int base, bool top, bool two,
+                                                 const uint4& a0, const uint4& b0, const uint4& a1, const uint4& b1)
 {
-    const uint32_t cnt = t.cur >> 29;
-    const uint4* np = reinterpret_cast<const uint4*>(ln.nodes + (t.cur & kIndexMask));
-    const bool two = cnt > 1;
-    const int o1 = two ? 2 : 0;
-    uint4 a0, b0, a1, b1;
-    if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
-    else { a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1]; }
     float f0, k0;
     slab(a0, b0, r, f0, k0);
     slab(a1, b1, r, t.f1, t.k1);
@@ -94,6 +88,20 @@ __device__ __forceinline__ void inst_box_step(const LaneNodes& ln, const Ray& r,
         inst_second_slot(t, r.tmin, r.tmax, top);
         if (t.phase == PH_STEP) { inst_advance(t, base, top); prefetch_pair<PF>(ln, t); }
     }
+}
+
+// the fetch of the pair (from the prefetch registers under PF) and the step on it
+template <bool PF>
+__device__ __forceinline__ void inst_box_step(const LaneNodes& ln, const Ray& r, Trav& t, int base, bool top)
+{
+    const uint32_t cnt = t.cur >> 29;
+    const uint4* np = reinterpret_cast<const uint4*>(ln.nodes + (t.cur & kIndexMask));
+    const bool two = cnt > 1;
+    const int o1 = two ? 2 : 0;
+    uint4 a0, b0, a1, b1;
+    if constexpr (PF) { a0 = t.pf0; b0 = t.pf1; a1 = t.pf2; b1 = t.pf3; }
+    else { a0 = np[0]; b0 = np[1]; a1 = np[o1]; b1 = np[o1 + 1]; }
+    inst_box_step_on<PF>(ln, r, t, base, top, two, a0, b0, a1, b1);
 }
 
 __device__ __forceinline__ void load_world_ray(const InstParams& p, uint64_t i, Ray& r)

@@ -223,6 +223,17 @@ hipError_t launch_motion_query(const rt_motion_accel& as, const rt_ray* rays, co
                                bool any_hit, uint64_t* counters, hipStream_t st);
 hipError_t launch_motion_validate(const rt_motion_accel& as, uint32_t num_triangles, uint32_t* status, hipStream_t st);
 
+// instance_motion_query.hip: rt_prepare_motion_instances / rt_intersect_rays_instanced_motion (num_rays > 0) after their
+// argument checks
+hipError_t launch_prepare_motion_instances(const rt_motion_instance* instances, uint32_t num_instances,
+                                           const rt_accel* blas_table, uint32_t num_blas, rt_triangle* proxies0,
+                                           rt_triangle* proxies1, rt_motion_instance_record* records, uint32_t* status,
+                                           hipStream_t st);
+hipError_t launch_instance_motion_query(const rt_motion_accel& tlas, const rt_motion_instance_record* records,
+                                        uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays,
+                                        const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool any_hit,
+                                        uint64_t* counters, hipStream_t st);
+
 // ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
 struct RaySortLayout {
     size_t box;         // float lo[4], hi[4] at the start of the 256-byte header

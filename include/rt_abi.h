@@ -358,7 +358,7 @@ int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* p
  * Argument errors: RT_ERR_INVALID_ARGUMENT for a null as / status, a null tree pointer with count > 0, count > 7, a status not
  * 4-byte or a tree pointer not 16-byte aligned; RT_ERR_TOO_LARGE for num_triangles > RT_REFIT_MAX_TRIANGLES.
  *
- * Out of scope: more than two key poses; motion of instance transforms; filtered, indexed, all-hit and first-K motion forms;
+ * Out of scope: more than two key poses (motion of instance transforms: the instance-motion block below); filtered, indexed, all-hit and first-K motion forms;
  * the pair-prefetch traversal; shading of motion hits; the C++ host mirror and rt_cli. */
 typedef struct rt_motion_accel {
     const rt_triangle_pair* triangles0; const rt_node* nodes0;   /* key pose at time 0 */
@@ -437,6 +437,74 @@ int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* 
                                 const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
                                 uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
                                 uint64_t* counters, void* stream);
+
+/* ---- instance motion (no reference counterpart).  The instanced query with a time per ray over TWO key transforms of every
+ * instance: motion blur of rigid (or affinely deforming) placed meshes.  The BLASes are static trees, as in the instancing
+ * block; what moves is object_to_world, and with it the TLAS.
+ *
+ * rt_motion_instance (caller input, 128 bytes): object_to_world0 / object_to_world1, row-major 3x4, the placement at time 0
+ * and at time 1; blas as in rt_instance.  At time tau the instance is placed by the entrywise interpolated matrix
+ *       w0 = 1 - tau  (once per ray);   M(tau)[k] = fl(fl(w0 * M0[k]) + fl(tau * M1[k])),  k = 0 .. 11
+ * in float32, no fused multiply-add: a world point of the instance moves on the straight line between its two key positions.
+ * Rotations are NOT interpolated as rotations; callers subdivide large rotations, as with any matrix-motion interface.
+ * rt_motion_instance_record (128 bytes, written by rt_prepare_motion_instances, read by the query): the validated copy of the
+ * input -- both matrices, blas, flags (RT_INSTANCE_*; non-zero: never entered), six spare words (0).  It holds no inverse:
+ * the inverse depends on the ray's time.
+ *
+ * rt_prepare_motion_instances, one launch after a clear of *status, one thread per instance:
+ *   - proxies0[i] / proxies1[i] are byte for byte what rt_prepare_instances writes for object_to_world0 / object_to_world1:
+ *     the same object box, corner order, ordered min / max and 2^-12 pad (one copy of the arithmetic serves both calls);
+ *   - RT_INSTANCE_BAD_BLAS as in rt_prepare_instances;
+ *   - RT_INSTANCE_SINGULAR: a non-finite entry in either matrix, a 3x3 determinant (in double) that is 0 at either key, or
+ *     determinants of opposite sign (such a motion passes through a singular matrix);
+ *   - a flagged instance gets the point proxy at the origin in BOTH poses, and its flags in its record and in *status.
+ *
+ * TLAS: no new builder.  Build any TLAS kind over proxies0 (as in the instancing block), byte-copy its nodes_out /
+ * triangles_out, rt_refit the copy with proxies1 through a plan of its own, and hand the two poses to the query as an
+ * rt_motion_accel (motion block); rt_motion_validate applies as it is.  The interpolated proxy boxes bound the moving instance
+ * at every time (DESIGN section 23 has the argument).
+ *
+ * rt_intersect_rays_instanced_motion: rt_intersect_rays_instanced with times[i] for rays[i].
+ *   A ray the instanced query would not trace, and a ray whose time is NaN or outside [0, 1], is not traced: the miss record,
+ *   instance id RT_MISS, no tests counted.
+ *   TLAS steps read each node pair from both TLAS poses and interpolate the six bounds as the motion block does
+ *   (fl(fl(w0 * a) + fl(tau * b)), w12 / w28 from pose 0).  TLAS leaves are entries as in rt_intersect_rays_instanced; the
+ *   instance index is primitive_id_0 of pose 0's leaf.  An instance is not entered in the cases listed there.  Otherwise,
+ *   with m = M(tau) as above, A its 3x3 part and T its translation column, all in float32 and without contraction:
+ *       c00 = a11*a22 - a12*a21, c01 = a12*a20 - a10*a22, c02 = a10*a21 - a11*a20;  det = (a00*c00 + a01*c01) + a02*c02
+ *       (and the other six cofactors as rt_prepare_instances's adjugate);  inv_det = 1.0f / det
+ *       the instance is NOT ENTERED BY THIS RAY when det == 0, or det or inv_det is not finite
+ *       W[k][j] = adj[k][j] * inv_det;   q = o - T;   o' = W*q, d' = W*d, each row (w0*x + w1*y) + w2*z;   1/d' by IEEE division
+ *   Inside a BLAS the walk is rt_intersect_rays_instanced's on the static tree: stored bounds and corners (never multiplied
+ *   by a weight), the one 64-entry stack, the world ray reloaded on exit, t preserved, RT_RAY_ANY_HIT ending the ray at its
+ *   first accepted triangle.  Identity at both keys and a time in {0, 1/4, 1/2, 1}: W is the identity exactly.
+ *   hits, instance_ids, counters, alignments and argument errors are rt_intersect_rays_instanced's, plus: times is non-null
+ *   and 4-byte aligned; the four TLAS pointers are non-null when tlas->count > 0.  All argument errors are returned before
+ *   any GPU work; errors win over num_rays = 0, which runs nothing.  Both calls are asynchronous and hipGraph-capturable.
+ *   Cost: DESIGN section 23 has the measured ratio to rt_intersect_rays_instanced.
+ *
+ * Out of scope: a deforming BLAS inside a moving instance; filters; the pair-prefetch traversal; more than two key poses;
+ * rotations interpolated as rotations; the C++ host mirror and rt_cli. */
+typedef struct rt_motion_instance {
+    float    object_to_world0[12];  /* row-major 3x4, time 0 */
+    float    object_to_world1[12];  /* row-major 3x4, time 1 */
+    uint32_t blas;                  /* index into the BLAS table */
+    uint32_t pad[7];
+} rt_motion_instance;
+typedef struct rt_motion_instance_record {
+    float    object_to_world0[12];
+    float    object_to_world1[12];
+    uint32_t blas;
+    uint32_t flags;                 /* RT_INSTANCE_* of the instance; non-zero: never entered */
+    uint32_t spare[6];
+} rt_motion_instance_record;
+int rt_prepare_motion_instances(const rt_motion_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
+                                uint32_t num_blas, rt_triangle* proxies0, rt_triangle* proxies1,
+                                rt_motion_instance_record* records, uint32_t* status, void* stream);
+int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
+                                       uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                                       const rt_ray* rays, const float* times, rt_hit* hits, uint32_t* instance_ids,
+                                       uint32_t num_rays, int mode, uint64_t* counters, void* stream);
 
 /* ---- closest-point queries (no reference counterpart).  For each caller point: which triangle is nearest, where on it, and
  * how far away -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and
