@@ -7,7 +7,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 ``src/BuildWrapper.cuh:6-20``, ``src/RadixSort.cuh:6-7``, ``src/main.cu:125-127``), plus ray queries over any built
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
-``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), and closest-point queries
+``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), sphere primitives
+(``PrepareSpheres``, ``IntersectRaysSpheres``: ray queries over a tree built on spheres), and closest-point queries
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
@@ -71,6 +72,10 @@ MOTION_INSTANCE_RECORD = np.dtype([("object_to_world0", "<f4", (3, 4)), ("object
 ACCEL = np.dtype([("triangles", "<u8"), ("nodes", "<u8"), ("root", "<u4"), ("count", "<u4")])                # 24 B
 assert INSTANCE.itemsize == 64 and INSTANCE_RECORD.itemsize == 64 and ACCEL.itemsize == 24
 RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
+# sphere primitives (rt_prepare_spheres / rt_intersect_rays_spheres)
+SPHERE = np.dtype([("center", "<f4", 3), ("radius", "<f4")])                                                 # 16 B
+assert SPHERE.itemsize == 16
+RT_SPHERE_BAD = 1
 # ray sorting (rt_sort_rays): a dead ray's key; every live key is below it
 RAY_KEY_BITS, RAY_KEY_DEAD = 30, 1 << 29
 # closest-point queries (rt_closest_points)
@@ -213,7 +218,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
            "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_prepare_motion_instances",
-           "rt_intersect_rays_instanced_motion", "rt_closest_points",
+           "rt_intersect_rays_instanced_motion", "rt_prepare_spheres", "rt_intersect_rays_spheres", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
@@ -298,6 +303,10 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays_instanced_motion.restype = i32
     L.rt_intersect_rays_instanced_motion.argtypes = [ctypes.POINTER(_MotionAccel), vp, u32, vp, u32, vp, vp, vp, vp, u32, i32, vp,
                                                      vp]
+    L.rt_prepare_spheres.restype = i32
+    L.rt_prepare_spheres.argtypes = [vp, u32, vp, vp, vp]
+    L.rt_intersect_rays_spheres.restype = i32
+    L.rt_intersect_rays_spheres.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, i32, vp, vp]
     L.rt_closest_points.restype = i32
     L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
     L.rt_range_scratch_bytes.restype = ctypes.c_size_t
@@ -786,6 +795,57 @@ def IntersectRaysInstancedMotion(tlas_pose0, tlas_pose1, root: int, count: int, 
                                                     int(num_blas), _ptr(rays), _ptr(times), _ptr(hits), _ptr(instance_ids), n,
                                                     kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
            "rt_intersect_rays_instanced_motion")
+
+
+def PrepareSpheres(spheres, num_spheres: int, proxies, status, stream=None) -> None:
+    """rt_prepare_spheres: `spheres` (SPHERE records, device, e.g. float32 [N, 4]: centre, radius) -> `proxies` (num_spheres
+    TRIANGLE records: the build input of any builder with pairs and splits off, e.g. a BuildInput's triangles_in; prepare into
+    them again and Refit for moving spheres) and `status` (a device uint32 the call clears; RT_SPHERE_BAD when a sphere is not
+    valid, see sphere_status).  Asynchronous on `stream`."""
+    n = int(num_spheres)
+    for name, buf, size in (("spheres", spheres, 16), ("proxies", proxies, 36)):
+        if n and (not buf.is_contiguous() or _nbytes(buf) < size * n):
+            raise ValueError(f"{name} must be a contiguous device buffer of {n} {size}-byte records")
+    _check(lib().rt_prepare_spheres(_ptr(spheres), n, _ptr(proxies), _ptr(status), _stream_ptr(stream)), "rt_prepare_spheres")
+
+
+def sphere_status(status) -> int:
+    """The RT_SPHERE_* flags of the last PrepareSpheres (copies the word back: waits for the work queued before it)."""
+    return _status_word(status)
+
+
+def IntersectRaysSpheres(triangles, nodes, root: int, count: int, spheres, num_spheres: int, rays, hits, *,
+                         any_hit: bool = False, order=None, num_indices: Optional[int] = None, counters=None,
+                         stream=None) -> None:
+    """rt_intersect_rays_spheres: IntersectRays over a tree built on PrepareSpheres's proxies (`triangles` / `nodes`: its
+    triangles_out / nodes_out, root / count of its root) and the `spheres` it was prepared from.  A HIT record carries t, the
+    sphere index as primitive_id, u = 1 when the ray began inside the sphere (its far root was taken) else 0, v = 0; a miss is
+    {+inf, MISS, 0, 0}.  `order` (optional): a contiguous device tensor of uint32 / int32 words -- SortRays's output on this
+    tree, or any list of ray indices -- used as by IntersectRaysIndexed; num_indices: how many of its words (default: all).
+    counters: optional int64[4] device tensor (box tests, sphere tests, wave steps).  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    ns = int(num_spheres)
+    if ns and (not spheres.is_contiguous() or _nbytes(spheres) < 16 * ns):
+        raise ValueError(f"spheres must be a contiguous device buffer of {ns} 16-byte records")
+    k = 0
+    if order is not None:
+        if not order.is_contiguous():
+            raise ValueError("order must be a contiguous device buffer")
+        k = _nbytes(order) // 4 if num_indices is None else int(num_indices)
+        if _nbytes(order) < 4 * k:
+            raise ValueError(f"order must hold {k} words")
+        if k == 0:
+            return
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_intersect_rays_spheres(ctypes.byref(a), _ptr(spheres), ns, _ptr(rays), n, _ptr(order), k, _ptr(hits),
+                                           kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_spheres")
 
 
 def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, counters=None, status=None, stream=None) -> None:

@@ -509,6 +509,32 @@ int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_mot
                                                static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_sphere) == 16, "rt_abi.h: rt_sphere is one 16-byte record");
+
+int rt_prepare_spheres(const rt_sphere* spheres, uint32_t num_spheres, rt_triangle* proxies, uint32_t* status, void* stream)
+{
+    if (!status || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(spheres, 16) || misaligned(proxies, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_spheres && (!spheres || !proxies)) return RT_ERR_INVALID_ARGUMENT;
+    return hip_rc(launch_prepare_spheres(spheres, num_spheres, proxies, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint32_t num_spheres, const rt_ray* rays,
+                              uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
+                              uint64_t* counters, void* stream)
+{
+    if (!tree_args(as)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(spheres, 16) || misaligned(rays, 16) || misaligned(hits, 16) || misaligned(order, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_spheres && !spheres) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays && (!rays || !hits)) return RT_ERR_INVALID_ARGUMENT;
+    // nothing to launch: no ray, or an index list without an entry
+    if (num_rays == 0 || (order && num_indices == 0)) return RT_OK;
+    return hip_rc(launch_sphere_query(*as, spheres, num_spheres, rays, num_rays, order, num_indices, hits,
+                                      mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
+}
+
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream)
 {
@@ -765,6 +791,9 @@ const char* rt_version_string(void)
            "own arithmetic (one launch), TLAS pose 1 by refit, TLAS steps interpolated as the motion query's (eight 16-byte "
            "requests), the record's two matrices interpolated and inverted in float32 at the ray's time on entry, static BLAS "
            "steps on stored bits | "
+           "spheres: ray queries over a tree built on sphere proxies (one prepare launch, padded boxes, any builder, refit "
+           "for moving spheres), the ray query's box phase with a sphere test at the leaf (two dependent 16-byte loads, the "
+           "discriminant from the perpendicular offset), closest / any hit, direct or through an index list | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
            "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
            "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "

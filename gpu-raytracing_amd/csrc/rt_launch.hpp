@@ -234,6 +234,14 @@ hipError_t launch_instance_motion_query(const rt_motion_accel& tlas, const rt_mo
                                         const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool any_hit,
                                         uint64_t* counters, hipStream_t st);
 
+// sphere_query.hip: rt_prepare_spheres / rt_intersect_rays_spheres after their argument checks (the query: a launch of at
+// least one lane; order == null: lane j takes ray j)
+hipError_t launch_prepare_spheres(const rt_sphere* spheres, uint32_t num_spheres, rt_triangle* proxies, uint32_t* status,
+                                  hipStream_t st);
+hipError_t launch_sphere_query(const rt_accel& as, const rt_sphere* spheres, uint32_t num_spheres, const rt_ray* rays,
+                               uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, bool any_hit,
+                               uint64_t* counters, hipStream_t st);
+
 // ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
 struct RaySortLayout {
     size_t box;         // float lo[4], hi[4] at the start of the 256-byte header

@@ -506,6 +506,69 @@ int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_mot
                                        const rt_ray* rays, const float* times, rt_hit* hits, uint32_t* instance_ids,
                                        uint32_t num_rays, int mode, uint64_t* counters, void* stream);
 
+/* ---- sphere primitives (no reference counterpart: the reference knows triangles only).  Ray queries over a set of spheres --
+ * particles, atoms, splats, proxies -- through a tree any builder makes over one PROXY TRIANGLE per sphere, the construction
+ * of the instancing block with a cheaper leaf: one 16-byte record and a dozen float operations.
+ *
+ * rt_sphere (caller input, 16 bytes): centre, radius.  A sphere is VALID when its centre is finite and 0 <= radius < +inf.
+ *
+ * rt_prepare_spheres, one launch after a clear of *status, one thread per sphere.  For a valid sphere, in float32:
+ *   - per axis lo = fl(c - r), hi = fl(c + r);
+ *   - E = the largest |lo| or |hi| over the three axes; pad = fl(E * 2^-18); the box is [fl(lo - pad), fl(hi + pad)];
+ *   - why 2^-18: the query's slab test carries at most 1.5 ulp of relative error in (bound - o) * inv, which for an origin
+ *     within eight box magnitudes is about 2^-19.4 * E in space; the pad covers it with margin.  As in the instancing block,
+ *     the guarantee is for rays that start within a few box magnitudes of the sphere;
+ *   - proxies[i] = {v0 = lo, v1 = hi, v2 = lo*0.5f + hi*0.5f} of that box: its box is exactly the padded box and its centroid
+ *     lies inside it, so it is a valid input for every builder.
+ * An invalid sphere ORs RT_SPHERE_BAD into *status (a device uint32 the call clears; read it after the stream ran) and gets the
+ * point proxy at the origin (v0 = v1 = v2 = 0), as a flagged instance does.
+ *
+ * Tree: rt_run_bottom_up_build (plain or hybrid) or rt_run_sah_build over `proxies` (num_triangles = num_spheres) with
+ * enable_pairs = enable_splits = 0.  A leaf's primitive_id_0 is then the sphere index.  Pairs and splits are the caller's
+ * error: the query ignores a leaf's second primitive.  Moving spheres: rt_prepare_spheres into the same proxies again, then
+ * rt_refit through a plan of rt_build_refit_plan (refit block, unchanged: it refits whatever triangles_in holds), or a rebuild.
+ *
+ * rt_intersect_rays_spheres: rays, the [tmin, tmax] window, the NaN and empty-range rules, the miss record, the counters'
+ * layout, alignment and asynchrony are rt_intersect_rays's.
+ *   order == NULL: lane j takes ray j, j < num_rays; num_indices is ignored.
+ *   Otherwise lane j (j < num_indices) takes i = order[j] and does nothing when i >= num_rays: rt_intersect_rays_indexed's
+ *   rule, word for word (unlisted records are not written; a ray listed twice is traced twice).  rt_sort_rays reads only the
+ *   root run of the tree it is given, so its order is usable on a sphere tree as it is.
+ *   Box phase: the tracer's -- slab test, nearest child first, one 64-entry stack, pushes beyond 64 dropped.
+ *   At a leaf: id = primitive_id_0.  The leaf is skipped when id >= num_spheres or the sphere is not valid for the query
+ *   (!(r >= 0) || r == +inf; a non-finite centre rejects itself in the test).  Otherwise, with c, r the sphere, o, d the ray,
+ *   in float32, every operation rounded on its own, IEEE division, correctly rounded square root:
+ *       f  = o - c                                   (per axis)
+ *       a  = (dx*dx + dy*dy) + dz*dz
+ *       b  = -((fx*dx + fy*dy) + fz*dz)
+ *       s  = b / a                                   (the parameter of closest approach)
+ *       p  = f + s*d                                 (per axis fl(fx + fl(s*dx)): centre -> closest point of the line)
+ *       l2 = (px*px + py*py) + pz*pz
+ *       disc = r*r - l2;   !(disc >= 0): rejected (a NaN rejects)
+ *       h  = sqrt(disc / a)
+ *       t_near = s - h;   t_far = s + h
+ *       t = t_near if tmin <= t_near <= tmax, else t_far if tmin <= t_far <= tmax, else rejected
+ *   The discriminant is taken from the perpendicular offset p, not from b*b - a*c: the textbook form subtracts two numbers of
+ *   the size of |f|^2 and loses all precision for a small sphere far from the ray's origin.
+ *   An accepted t becomes the ray's tmax; an equal t is accepted, as for triangles, so ties go to the sphere tested later.
+ *   hits[i]: t, primitive_id = the sphere index, u = 1.0f when t_far was taken (the ray began inside the sphere) else 0.0f,
+ *   v = 0.  mode RT_RAY_ANY_HIT ends the ray at its first accepted sphere.
+ *   Counters (optional, added to): [0] box tests, [1] sphere tests (leaves whose sphere was tested), [2] / [3] wave steps.
+ * Both calls are asynchronous (no host copy, no synchronisation: hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null status or as; null spheres / proxies with
+ * num_spheres > 0; null rays / hits with num_rays > 0; spheres / proxies / rays / hits not 16-byte aligned; status / order not
+ * 4-byte aligned; as->count > 7 (or a null tree pointer with count > 0); a bad mode.  Zero counts run nothing, except that
+ * prepare still clears *status.
+ *
+ * Out of scope: spheres as a BLAS kind inside the instanced query; mixed triangle / sphere trees; motion, filters, all-hit and
+ * first-K forms; point queries against spheres; the C++ host mirror and rt_cli. */
+typedef struct rt_sphere { rt_float3 center; float radius; } rt_sphere;   /* 16 bytes */
+enum { RT_SPHERE_BAD = 1 };
+int rt_prepare_spheres(const rt_sphere* spheres, uint32_t num_spheres, rt_triangle* proxies, uint32_t* status, void* stream);
+int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint32_t num_spheres, const rt_ray* rays,
+                              uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
+                              uint64_t* counters, void* stream);
+
 /* ---- closest-point queries (no reference counterpart).  For each caller point: which triangle is nearest, where on it, and
  * how far away -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and
  * every query misses).
