@@ -229,6 +229,106 @@ def _trace(leaves, nodes, root, count, camera, w, h, render_type, attributes, ma
     return rgba, counters
 
 
+# ---------------------------------------------------------------- ordered per-ray walkers (rt_oracle.h, ora_walk_rays*)
+RAY = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("dir", "<f4", 3), ("tmax", "<f4")])
+HIT = np.dtype([("t", "<f4"), ("primitive_id", "<u4"), ("u", "<f4"), ("v", "<f4")])
+WALK_BOX, WALK_TRI, WALK_DEPTH, WALK_DROPPED, WALK_LOW_BASE_DEPTH, WALK_HIGH_BASE_DROPPED = range(6)   # columns of `stats`
+
+
+def _walk_fn(name):
+    f = getattr(lib(), name)
+    f.restype = None
+    f.argtypes = None
+    return f
+
+
+def _tree_args(leaves, nodes):
+    lv, nd = np.ascontiguousarray(leaves), np.ascontiguousarray(nodes)
+    assert lv.dtype.itemsize == 64 and nd.dtype.itemsize == 32
+    return lv, nd
+
+
+def _ray_args(rays):
+    r = np.ascontiguousarray(rays)
+    assert r.dtype.itemsize == 32, "RAY records"
+    return r, np.zeros(r.shape[0], HIT)
+
+
+def _u32(v):
+    return ctypes.c_uint32(int(v))
+
+
+def walk_rays(leaves, nodes, root, count, rays, any_hit=False, stack_limit=64):
+    """trace_ray over RAY records -> (HIT [n], stats uint32 [n, 4]: box tests, triangle tests, greatest stack depth, dropped
+    pushes).  stack_limit (every walker takes it): 64, the kernels'; up to 1024 to see what a walk that drops nothing does"""
+    lv, nd = _tree_args(leaves, nodes)
+    r, hits = _ray_args(rays)
+    stats = np.zeros((r.shape[0], 4), np.uint32)
+    _walk_fn("ora_walk_rays")(_p(lv), _p(nd), _u32(root), _u32(count), _p(r), _u32(r.shape[0]), int(bool(any_hit)),
+                              _u32(stack_limit), _p(hits), _p(stats))
+    return hits, stats
+
+
+def walk_rays_motion(leaves0, nodes0, leaves1, nodes1, root, count, rays, times, any_hit=False, stack_limit=64):
+    """the motion arm: two poses of one tree and a time per ray -> as walk_rays"""
+    l0, n0 = _tree_args(leaves0, nodes0)
+    l1, n1 = _tree_args(leaves1, nodes1)
+    assert l0.shape == l1.shape and n0.shape == n1.shape
+    r, hits = _ray_args(rays)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.float32), (r.shape[0],)))
+    stats = np.zeros((r.shape[0], 4), np.uint32)
+    _walk_fn("ora_walk_rays_motion")(_p(l0), _p(n0), _p(l1), _p(n1), _u32(root), _u32(count), _p(r), _p(t), _u32(r.shape[0]),
+                                     int(bool(any_hit)), _u32(stack_limit), _p(hits), _p(stats))
+    return hits, stats
+
+
+def walk_rays_spheres(leaves, nodes, root, count, spheres, rays, any_hit=False, num_spheres=None, stack_limit=64):
+    """the sphere arm: a leaf's primitive_id_0 indexes `spheres` (float32 [k, 4]) -> as walk_rays, records {t, index, far root, 0}"""
+    lv, nd = _tree_args(leaves, nodes)
+    s = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+    r, hits = _ray_args(rays)
+    stats = np.zeros((r.shape[0], 4), np.uint32)
+    _walk_fn("ora_walk_rays_spheres")(_p(lv), _p(nd), _u32(root), _u32(count), _p(s),
+                                      _u32(s.shape[0] if num_spheres is None else num_spheres), _p(r), _u32(r.shape[0]),
+                                      int(bool(any_hit)), _u32(stack_limit), _p(hits), _p(stats))
+    return hits, stats
+
+
+def walk_rays_instanced(tlas_leaves, tlas_nodes, root, count, blas, rays, object_rays, enterable, any_hit=False,
+                        tlas_nodes1=None, times=None, cull=None, stack_limit=64):
+    """the two-level arm.  blas[k] = (leaves, nodes, root, count) of instance k's BLAS; object_rays: float32 [n, K, 6] (origin,
+    direction of ray i inside instance k); enterable: bool [n, K]; cull: None or uint8 [K] (0, 1: a < 0 rejected, 2: a > 0);
+    tlas_nodes1 / times: the TLAS's second pose and a time per ray (both or neither).
+    -> (HIT [n], instance ids uint32 [n], stats uint32 [n, 6]: walk_rays's four, the greatest depth inside an instance entered
+    below depth 16, the pushes dropped inside instances entered above depth 16)"""
+    tl, tn = _tree_args(tlas_leaves, tlas_nodes)
+    r, hits = _ray_args(rays)
+    n, K = r.shape[0], len(blas)
+    keep = [_tree_args(b[0], b[1]) for b in blas]
+    ptr = ctypes.c_void_p * max(K, 1)
+    pl = ptr(*[k[0].ctypes.data for k in keep])
+    pn = ptr(*[k[1].ctypes.data for k in keep])
+    roots = np.array([b[2] for b in blas], np.uint32)
+    counts = np.array([b[3] for b in blas], np.uint32)
+    obj = np.ascontiguousarray(object_rays, np.float32)
+    ent = np.ascontiguousarray(enterable, np.uint8)
+    assert obj.shape == (n, K, 6) and ent.shape == (n, K)
+    assert (tlas_nodes1 is None) == (times is None)
+    tn1 = t = None
+    if times is not None:
+        tn1 = np.ascontiguousarray(tlas_nodes1)
+        assert tn1.shape == tn.shape and tn1.dtype.itemsize == 32
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.float32), (n,)))
+    cl = None if cull is None else np.ascontiguousarray(cull, np.uint8)
+    assert cl is None or cl.shape == (K,)
+    ids = np.zeros(n, np.uint32)
+    stats = np.zeros((n, 6), np.uint32)
+    _walk_fn("ora_walk_rays_instanced")(_p(tl), _p(tn), _p(tn1), _u32(root), _u32(count), _u32(K), pl, pn, _p(roots), _p(counts),
+                                        _p(cl), _p(r), _p(t), _u32(n), _p(obj), _p(ent), int(bool(any_hit)),
+                                        _u32(stack_limit), _p(hits), _p(ids), _p(stats))
+    return hits, ids, stats
+
+
 # ---------------------------------------------------------------- the reference's own checker (oracle/_ref)
 class _HierarchyStats(ctypes.Structure):  # Utilities.h:3-7
     _fields_ = [("numNodes", ctypes.c_int), ("numLeafNodes", ctypes.c_int), ("numTreeNodes", ctypes.c_int)]

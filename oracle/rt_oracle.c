@@ -1624,3 +1624,329 @@ int ora_box_intersection(const float a[6], const float b[6], float out[6])      
     box_intersection(a, b, out);
     return box_valid(out);
 }
+
+/* ================================================================== ordered per-ray walkers over RAY records
+ * trace_ray's state machine (one 64-entry stack, every push onto a full stack dropped, the nearest child's included)
+ * for caller rays, returning what the ray queries of include/rt_abi.h return -- one HIT record per ray -- and per ray
+ * box_tests, tri_tests, the greatest stack depth (entries, the nearest child's push included, as ora_trace's
+ * counters[2]) and the dropped pushes.  Four arms: static triangles, two key poses with a time per ray, sphere leaves,
+ * and a TLAS over instances' BLASes.  Closest hit, or any hit (the ray ends at its first accepted primitive; until then
+ * its tests are the closest-hit ones, in order).  float32, one rounding per operation (-ffp-contract=off).
+ * Nothing here is called by ora_trace: trace_ray above stays as it is. */
+typedef struct {
+    const ora_node* nodes;
+    const ora_node* nodes1;               /* pose 1 of the same slots, or NULL: bounds are fl(fl(w0*a) + fl(tau*b)) */
+    const ora_triangle_pair* leaves;
+    const ora_triangle_pair* leaves1;     /* pose 1 of the same records, or NULL: corners likewise, ids and rotations pose 0's */
+    const float* spheres;                 /* not NULL: a leaf's primitive_id_0 is a sphere index (centre, radius) */
+    uint32_t num_spheres;
+    float tau, w0;
+    int cull;                             /* 0; 1: a candidate with determinant a < 0 is rejected; 2: with a > 0 */
+    unsigned limit;                       /* the stack holds this many entries (walk_limit of the caller's stack_limit) */
+} walk_level_t;
+
+static inline float walk_lerp(const walk_level_t* lv, float a, float b) { return lv->w0 * a + lv->tau * b; }
+static inline ora_f3 walk_lerp3(const walk_level_t* lv, ora_f3 a, ora_f3 b)
+{
+    return f3(walk_lerp(lv, a.x, b.x), walk_lerp(lv, a.y, b.y), walk_lerp(lv, a.z, b.z));
+}
+
+/* intersect_ray_triangle with the hit filter's facing rule, asked after the window test and before tmax is written */
+static inline int walk_triangle(ora_f3 v0, ora_f3 v1, ora_f3 v2, ray_t* ray, ray_result_t* rr, uint32_t tri_id,
+                                uint32_t prim_id, int cull)
+{
+    const float epsilon = 0.000000001f;
+    ora_f3 edge1 = sub3(v1, v0);
+    ora_f3 edge2 = sub3(v2, v0);
+    ora_f3 h = cross3(ray->direction, edge2);
+    float a = dot3(edge1, h);
+    if (a > -epsilon && a < epsilon) return 0;
+    float f = 1.0f / a;
+    ora_f3 s = sub3(ray->origin, v0);
+    float u = f * dot3(s, h);
+    if (u < 0.0f || u > 1.0f) return 0;
+    ora_f3 q = cross3(s, edge1);
+    float v = f * dot3(ray->direction, q);
+    if (v < 0.0f || (u + v) > 1.0f) return 0;
+    float t = f * dot3(edge2, q);
+    if (t < ray->tmin || t > ray->tmax) return 0;
+    if (cull == 1 && a < 0.0f) return 0;
+    if (cull == 2 && a > 0.0f) return 0;
+    ray->tmax = t;
+    rr->primitive_id = prim_id;
+    rr->tri_id = tri_id;
+    rr->bu = u;
+    rr->bv = v;
+    return 1;
+}
+
+/* the sphere test of include/rt_abi.h (sphere block), operation by operation; rr->bu carries the far-root flag */
+static inline int walk_sphere(const float* sp, ray_t* ray, ray_result_t* rr, uint32_t id)
+{
+    const ora_f3 d = ray->direction;
+    const float fx = ray->origin.x - sp[0], fy = ray->origin.y - sp[1], fz = ray->origin.z - sp[2];
+    const float a = (d.x * d.x + d.y * d.y) + d.z * d.z;
+    const float b = -((fx * d.x + fy * d.y) + fz * d.z);
+    const float s = b / a;
+    const float px = fx + s * d.x, py = fy + s * d.y, pz = fz + s * d.z;
+    const float l2 = (px * px + py * py) + pz * pz;
+    const float disc = sp[3] * sp[3] - l2;
+    if (!(disc >= 0.0f)) return 0;
+    const float hh = sqrtf(disc / a);
+    const float t_near = s - hh, t_far = s + hh;
+    const int near_ok = (t_near >= ray->tmin) & (t_near <= ray->tmax);
+    const int far_ok = (t_far >= ray->tmin) & (t_far <= ray->tmax);
+    if (!(near_ok | far_ok)) return 0;
+    ray->tmax = near_ok ? t_near : t_far;
+    rr->primitive_id = id;
+    rr->tri_id = 0;
+    rr->bu = near_ok ? 0.0f : 1.0f;
+    rr->bv = 0.0f;
+    return 1;
+}
+
+/* a leaf that passed its slab test: the level's primitive test(s) */
+static int walk_leaf(const walk_level_t* lv, uint32_t child, uint32_t ncount, ray_t* ray, ray_result_t* rr, stats_t* stats)
+{
+    if (lv->spheres) {
+        const uint32_t id = lv->leaves[child].primitive_id_0;
+        if (id >= lv->num_spheres) return 0;                      /* no test counted */
+        const float* sp = lv->spheres + 4 * (size_t)id;
+        if (!(sp[3] >= 0.0f) || sp[3] == INFINITY) return 0;      /* a negative, NaN or infinite radius: likewise */
+        stats->tri_tests++;
+        return walk_sphere(sp, ray, rr, id);
+    }
+    stats->tri_tests++;
+    ora_triangle_pair tp = lv->leaves[child];
+    if (lv->leaves1) {
+        const ora_triangle_pair* q = &lv->leaves1[child];
+        tp.v0 = walk_lerp3(lv, tp.v0, q->v0);
+        tp.v1 = walk_lerp3(lv, tp.v1, q->v1);
+        tp.v2 = walk_lerp3(lv, tp.v2, q->v2);
+        tp.v3 = walk_lerp3(lv, tp.v3, q->v3);
+    }
+    int hit = walk_triangle(tp.v0, tp.v1, tp.v2, ray, rr, child << 1, tp.primitive_id_0, lv->cull);
+    /* B = (v2, v1, v3) is skipped when v3 == v2 bit for bit (a single's record; its a is exactly 0 anyway) */
+    if (ncount > 0 && memcmp(&tp.v3, &tp.v2, sizeof(ora_f3)) != 0)
+        hit |= walk_triangle(tp.v2, tp.v1, tp.v3, ray, rr, (child << 1) + 1, tp.primitive_id_1, lv->cull);
+    return hit;
+}
+
+/* the stack limit of one call: 0 means 64, the kernels' and trace_ray's.  A test may pass more (at most WALK_STACK_MAX) to
+ * see what a walk that drops nothing would have done. */
+#define WALK_STACK_MAX 1024
+static inline unsigned walk_limit(uint32_t n) { return n == 0 ? 64 : (n > WALK_STACK_MAX ? WALK_STACK_MAX : n); }
+#define WALK_DONE 1       /* an any-hit ray accepted a primitive: the ray is over */
+#define WALK_ACCEPTED 2   /* a leaf of this entry accepted a primitive */
+#define WALK_PUSH(e) do { if (sp < lv->limit) stack[sp++] = (e); else stats->dropped++; if (sp > stats->max_stack) stats->max_stack = sp; } while (0)
+/* One popped entry: trace_ray's loop body on the run [entry.index, entry.index + entry.count).  `top`: the run is a
+ * TLAS's -- a leaf slot that passes its slab test is an entry like a Box child, packed as (leaf index, count 0), ties
+ * on that index. */
+static int walk_entry(const walk_level_t* lv, int top, int any, stack_entry_t entry, ray_t* ray, ray_result_t* rr,
+                      stack_entry_t* stack, unsigned* psp, stats_t* stats)
+{
+    unsigned sp = *psp;
+    int out = 0;
+    unsigned num_hits = 0;
+    stack_entry_t child_buffer = {0, 0};
+    float child_dist = 0.0f;
+    for (unsigned i = 0; i < entry.count; i++) {
+        ora_node node = lv->nodes[entry.index + i];
+        if (lv->nodes1) {
+            const ora_node* m = &lv->nodes1[entry.index + i];
+            node.min = walk_lerp3(lv, node.min, m->min);
+            node.max = walk_lerp3(lv, node.max, m->max);
+        }
+        uint32_t type = node.w28 >> 29, child = node.w28 & NODE_PARENT_MASK, ncount = node.w12 >> 29;
+        if (type == ORA_TYPE_NONE) continue;
+        float dist;
+        int hit = intersect_ray_aabb(&node, ray, &dist);
+        int is_leaf = type == ORA_TYPE_TRI;
+        stats->box_tests++;
+        if (is_leaf && top) ncount = 0;
+        if (hit && is_leaf && !top) {
+            if (walk_leaf(lv, child, ncount, ray, rr, stats)) {
+                out |= WALK_ACCEPTED;
+                if (any) { *psp = sp; return out | WALK_DONE; }
+            }
+        } else if (hit && num_hits == 0) {
+            child_buffer.index = child;
+            child_buffer.count = ncount;
+            child_dist = dist;
+            num_hits++;
+        } else if (hit) {
+            if (dist < child_dist || (dist == child_dist && child > child_buffer.index)) {
+                stack_entry_t tmp = child_buffer;
+                child_buffer.index = child;
+                child_buffer.count = ncount;
+                child_dist = dist;
+                WALK_PUSH(tmp);
+            } else {
+                stack_entry_t e = {child, ncount};
+                WALK_PUSH(e);
+            }
+        }
+    }
+    if (num_hits > 0) WALK_PUSH(child_buffer);
+    *psp = sp;
+    return out;
+}
+
+static inline ray_t walk_load_ray(const float* r)
+{
+    ray_t ray = {f3(r[0], r[1], r[2]), r[3], f3(r[4], r[5], r[6]), r[7]};
+    return ray;
+}
+/* rt_intersect_rays's rule: tmin <= tmax (false for a NaN) and no NaN in origin or direction */
+static inline int walk_live(const ray_t* r)
+{
+    return r->tmin <= r->tmax && !(isnan(r->origin.x) || isnan(r->origin.y) || isnan(r->origin.z) ||
+                                   isnan(r->direction.x) || isnan(r->direction.y) || isnan(r->direction.z));
+}
+static void walk_record(float* out, int hit, int spheres, const ray_t* ray, const ray_result_t* rr, const ora_triangle_pair* leaves)
+{
+    const uint32_t miss = 0xFFFFFFFFu;
+    out[0] = INFINITY; memcpy(&out[1], &miss, 4); out[2] = 0.0f; out[3] = 0.0f;
+    if (!hit) return;
+    out[0] = ray->tmax;
+    memcpy(&out[1], &rr->primitive_id, 4);
+    if (spheres) { out[2] = rr->bu; return; }
+    /* (u, v) as the device stores them: leaf corner k is the caller's corner i_k (RotateAttributes) */
+    const ora_triangle_pair* tp = &leaves[rr->tri_id >> 1];
+    const uint32_t rot = (rr->tri_id & 1) ? tp->rot_y : tp->rot_x;
+    const float bu = rr->bu, bv = rr->bv, w0 = 1 - bu - bv;
+    out[2] = rot == 1 ? bv : (rot == 2 ? w0 : bu);
+    out[3] = rot == 1 ? w0 : (rot == 2 ? bu : bv);
+}
+
+/* one level: the static, motion and sphere arms.  times == NULL: no second pose */
+static void walk_one_level(walk_level_t lv, uint32_t root, uint32_t count, const float* rays, const float* times, uint32_t n,
+                           int any_hit, float* hits, uint32_t* stats_out)
+{
+#pragma omp parallel for num_threads(g_threads) schedule(dynamic, 16) firstprivate(lv)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        ray_t ray = walk_load_ray(rays + 8 * i);
+        stats_t st = {0, 0, 0, 0};
+        ray_result_t rr = {0, 0, 0.0f, 0.0f};
+        int live = walk_live(&ray) && count > 0, hit = 0;
+        if (times) {
+            lv.tau = times[i];
+            lv.w0 = 1.0f - lv.tau;
+            live = live && lv.tau >= 0.0f && lv.tau <= 1.0f;
+        }
+        if (live) {
+            stack_entry_t stack[WALK_STACK_MAX];
+            unsigned sp = 0;
+            stack_entry_t e = {root & NODE_PARENT_MASK, count};
+            for (;;) {
+                const int r = walk_entry(&lv, 0, any_hit, e, &ray, &rr, stack, &sp, &st);
+                hit |= (r & WALK_ACCEPTED) != 0;
+                if ((r & WALK_DONE) || sp == 0) break;
+                e = stack[--sp];
+            }
+        }
+        walk_record(hits + 4 * i, hit, lv.spheres != 0, &ray, &rr, lv.leaves);
+        stats_out[4 * i + 0] = st.box_tests; stats_out[4 * i + 1] = st.tri_tests;
+        stats_out[4 * i + 2] = st.max_stack; stats_out[4 * i + 3] = st.dropped;
+    }
+}
+
+void ora_walk_rays(const ora_triangle_pair* leaves, const ora_node* nodes, uint32_t root, uint32_t count, const float* rays,
+                   uint32_t n, int any_hit, uint32_t stack_limit, float* hits, uint32_t* stats)
+{
+    walk_level_t lv = {nodes, 0, leaves, 0, 0, 0, 0.0f, 1.0f, 0, walk_limit(stack_limit)};
+    walk_one_level(lv, root, count, rays, 0, n, any_hit, hits, stats);
+}
+
+void ora_walk_rays_motion(const ora_triangle_pair* leaves0, const ora_node* nodes0, const ora_triangle_pair* leaves1,
+                          const ora_node* nodes1, uint32_t root, uint32_t count, const float* rays, const float* times,
+                          uint32_t n, int any_hit, uint32_t stack_limit, float* hits, uint32_t* stats)
+{
+    walk_level_t lv = {nodes0, nodes1, leaves0, leaves1, 0, 0, 0.0f, 1.0f, 0, walk_limit(stack_limit)};
+    walk_one_level(lv, root, count, rays, times, n, any_hit, hits, stats);
+}
+
+void ora_walk_rays_spheres(const ora_triangle_pair* leaves, const ora_node* nodes, uint32_t root, uint32_t count,
+                           const float* spheres, uint32_t num_spheres, const float* rays, uint32_t n, int any_hit,
+                           uint32_t stack_limit, float* hits, uint32_t* stats)
+{
+    walk_level_t lv = {nodes, 0, leaves, 0, spheres, num_spheres, 0.0f, 1.0f, 0, walk_limit(stack_limit)};
+    walk_one_level(lv, root, count, rays, 0, n, any_hit, hits, stats);
+}
+
+void ora_walk_rays_instanced(const ora_triangle_pair* tlas_leaves, const ora_node* tlas_nodes0, const ora_node* tlas_nodes1,
+                             uint32_t root, uint32_t count, uint32_t num_instances, const void* const* inst_leaves,
+                             const void* const* inst_nodes, const uint32_t* inst_root, const uint32_t* inst_count,
+                             const uint8_t* inst_cull, const float* rays, const float* times, uint32_t n,
+                             const float* object_rays, const uint8_t* enterable, int any_hit, uint32_t stack_limit,
+                             float* hits, uint32_t* instance_ids, uint32_t* stats_out)
+{
+#pragma omp parallel for num_threads(g_threads) schedule(dynamic, 4)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        ray_t world = walk_load_ray(rays + 8 * i), ray = world;
+        stats_t st = {0, 0, 0, 0};
+        ray_result_t rr = {0, 0, 0.0f, 0.0f};
+        walk_level_t top_lv = {tlas_nodes0, 0, tlas_leaves, 0, 0, 0, 0.0f, 1.0f, 0, walk_limit(stack_limit)}, blas_lv = top_lv;
+        int live = walk_live(&world) && count > 0, hit = 0;
+        if (times) {
+            top_lv.nodes1 = tlas_nodes1;
+            top_lv.tau = times[i];
+            top_lv.w0 = 1.0f - top_lv.tau;
+            live = live && top_lv.tau >= 0.0f && top_lv.tau <= 1.0f;
+        }
+        uint32_t hit_inst = 0xFFFFFFFFu, inst = 0xFFFFFFFFu, low_base_max = 0, high_base_dropped = 0;
+        const ora_triangle_pair* hit_leaves = 0;
+        if (live) {
+            stack_entry_t stack[WALK_STACK_MAX];
+            unsigned sp = 0, base = 0;
+            uint32_t outer_max = 0, dropped_at_entry = 0;
+            int top = 1, done = 0;
+            stack_entry_t e = {root & NODE_PARENT_MASK, count};
+            for (;;) {
+                int entered = 0;
+                if (top && e.count == 0) {                     /* a TLAS leaf became current: enter its instance, or go on */
+                    const uint32_t id = tlas_leaves[e.index].primitive_id_0;
+                    if (id < num_instances && enterable[(size_t)i * num_instances + id]) {
+                        const float* o = object_rays + ((size_t)i * num_instances + id) * 6;
+                        ray.origin = f3(o[0], o[1], o[2]);
+                        ray.direction = f3(o[3], o[4], o[5]);
+                        blas_lv.nodes = (const ora_node*)inst_nodes[id];
+                        blas_lv.leaves = (const ora_triangle_pair*)inst_leaves[id];
+                        blas_lv.cull = inst_cull ? inst_cull[id] : 0;
+                        inst = id;
+                        top = 0;
+                        base = sp;                              /* the stack bottom is the current depth */
+                        e.index = inst_root[id] & NODE_PARENT_MASK;
+                        e.count = inst_count[id];
+                        outer_max = st.max_stack; st.max_stack = 0; dropped_at_entry = st.dropped;
+                        entered = 1;
+                    }
+                } else {
+                    const int r = walk_entry(top ? &top_lv : &blas_lv, top, any_hit, e, &ray, &rr, stack, &sp, &st);
+                    if (r & WALK_ACCEPTED) { hit = 1; hit_inst = inst; hit_leaves = blas_lv.leaves; }
+                    done = (r & WALK_DONE) != 0;
+                }
+                if (entered) continue;
+                if (!top && (done || sp == base)) {            /* the instance is left: what its walk did to the stack */
+                    if (base < 16 && st.max_stack > low_base_max) low_base_max = st.max_stack;
+                    if (base > 16) high_base_dropped += st.dropped - dropped_at_entry;
+                    if (outer_max > st.max_stack) st.max_stack = outer_max;
+                    if (!done) {                                /* back to the world ray, with the current tmax */
+                        world.tmax = ray.tmax;
+                        ray = world;
+                        top = 1;
+                        base = 0;
+                        inst = 0xFFFFFFFFu;
+                    }
+                }
+                if (done || sp == 0) break;
+                e = stack[--sp];
+            }
+        }
+        walk_record(hits + 4 * i, hit, 0, &ray, &rr, hit_leaves);
+        instance_ids[i] = hit ? hit_inst : 0xFFFFFFFFu;
+        uint32_t* so = stats_out + 6 * i;
+        so[0] = st.box_tests; so[1] = st.tri_tests; so[2] = st.max_stack; so[3] = st.dropped;
+        so[4] = low_base_max; so[5] = high_base_dropped;
+    }
+}

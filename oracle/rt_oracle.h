@@ -177,6 +177,45 @@ void ora_set_textures(const ora_texture* textures, uint32_t num_textures);
 uint32_t ora_lod_sizes(int32_t sx0, int32_t sy0, int32_t* size_x, int32_t* size_y);
 void ora_generate_lod(const uint32_t* src, int32_t sx, int32_t sy, uint32_t* dst);
 
+/* Ordered per-ray walkers: trace_ray's state machine (Tracer.cu:308-374 with this oracle's full-stack rule: every push onto
+ * 64 entries is dropped, the nearest child's included) over caller RAY records {origin, tmin, direction, tmax} (8 floats).
+ * hits: one HIT record {t, primitive_id, u, v} per ray (4 words), (u, v) mapped through TrianglePair::rotations to the
+ * caller's corners; a miss is {+inf, 0xFFFFFFFF, 0, 0}.  stats: per ray {box_tests, tri_tests, greatest stack depth (as
+ * ora_trace's counters[2]), dropped pushes}.  any_hit != 0: a ray ends at its first accepted primitive.  A ray with
+ * tmin > tmax or a NaN in its window, origin or direction (or a time outside [0, 1]) is a miss with no tests.  stack_limit:
+ * 0 for the kernels' 64 entries; a test may pass up to 1024 to see what a walk that drops nothing does.
+ *   ora_walk_rays           the static tree.
+ *   ora_walk_rays_motion    two poses of nodes and leaves and a time per ray: every bound and corner is
+ *                           fl(fl(w0*a) + fl(tau*b)), w0 = fl(1 - tau); the fourth words are pose 0's; B of a pair is skipped
+ *                           when the interpolated v3 == v2.
+ *   ora_walk_rays_spheres   a leaf's primitive_id_0 is a sphere index into spheres (centre, radius); an index >= num_spheres or
+ *                           a radius that is negative, NaN or infinite counts no test; the record is {t, index, far root, 0}.
+ *   ora_walk_rays_instanced a TLAS whose leaves name instances (primitive_id_0).  A TLAS leaf that passes its slab test is
+ *                           an entry like a Box child, packed (leaf index, count 0), ties on that index; when it becomes
+ *                           current and enterable[ray * num_instances + id] is set, the BLAS root run of the instance becomes
+ *                           current with the ray object_rays[(ray * num_instances + id) * 6 ..] (origin, direction) in the
+ *                           current window, and the stack bottom is the current depth; the 64-entry limit still counts
+ *                           from 0.  Back at the bottom the world ray goes on with the current tmax.  tlas_nodes1 / times
+ *                           (both or neither): the TLAS bounds are interpolated as in the motion arm.  inst_cull (may be
+ *                           NULL): per instance 0, 1 (a candidate with determinant a < 0 is rejected) or 2 (a > 0).
+ *                           instance_ids: the instance of each hit or 0xFFFFFFFF.  stats: SIX words per ray -- the four
+ *                           above, then the greatest depth reached inside an instance entered at a depth below 16, and the
+ *                           pushes dropped inside instances entered at a depth above 16. */
+void ora_walk_rays(const ora_triangle_pair* leaves, const ora_node* nodes, uint32_t root, uint32_t count, const float* rays,
+                   uint32_t n, int any_hit, uint32_t stack_limit, float* hits, uint32_t* stats);
+void ora_walk_rays_motion(const ora_triangle_pair* leaves0, const ora_node* nodes0, const ora_triangle_pair* leaves1,
+                          const ora_node* nodes1, uint32_t root, uint32_t count, const float* rays, const float* times,
+                          uint32_t n, int any_hit, uint32_t stack_limit, float* hits, uint32_t* stats);
+void ora_walk_rays_spheres(const ora_triangle_pair* leaves, const ora_node* nodes, uint32_t root, uint32_t count,
+                           const float* spheres, uint32_t num_spheres, const float* rays, uint32_t n, int any_hit,
+                           uint32_t stack_limit, float* hits, uint32_t* stats);
+void ora_walk_rays_instanced(const ora_triangle_pair* tlas_leaves, const ora_node* tlas_nodes0, const ora_node* tlas_nodes1,
+                             uint32_t root, uint32_t count, uint32_t num_instances, const void* const* inst_leaves,
+                             const void* const* inst_nodes, const uint32_t* inst_root, const uint32_t* inst_count,
+                             const uint8_t* inst_cull, const float* rays, const float* times, uint32_t n,
+                             const float* object_rays, const uint8_t* enterable, int any_hit, uint32_t stack_limit,
+                             float* hits, uint32_t* instance_ids, uint32_t* stats);
+
 /* analysis aid: when set, ora_trace adds 1 to p[first slot] for every sibling pair a ray visits */
 void ora_set_visit_counts(uint32_t* p);
 

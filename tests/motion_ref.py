@@ -20,6 +20,7 @@ import shade_ref
 F = np.float32
 TIMES = np.array([0.0, 0.25, 1.0 / 3.0, 0.7, 1.0], F)
 SCENES = ("grid", "soup", "cornell")
+ENDPOINT_SCENES = SCENES + ("fractal",)   # the endpoint test also runs the deep-stack scene (levels 26..48 of the traversal stack)
 CAP = {"grid": 0.01, "soup": 0.01, "cornell": 0.05}     # the unstable fraction _check_against_f64 allows (cornell: shared planes)
 
 
@@ -98,8 +99,8 @@ def ray_cases(name, tris0, tris1):
     """kind -> (rays, times): test_gpu_ray_queries._ray_sets aimed at the union of both poses (1200 rays per kind: outside,
     axis, window), each ray with one of TIMES"""
     import test_gpu_ray_queries as rq
-    sets = rq._ray_sets(np.concatenate([tris0, tris1]), seed=SCENES.index(name) + 301)
-    rng = np.random.default_rng(SCENES.index(name) + 77)
+    sets = rq._ray_sets(np.concatenate([tris0, tris1]), seed=ENDPOINT_SCENES.index(name) + 301)
+    rng = np.random.default_rng(ENDPOINT_SCENES.index(name) + 77)
     return {kind: (r, TIMES[rng.integers(0, len(TIMES), len(r))]) for kind, r in sets.items()}
 
 

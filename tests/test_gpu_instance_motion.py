@@ -3,7 +3,8 @@ rt_intersect_rays_instanced_motion), against tests/instance_motion_ref.py.
 
 1. prepare: both proxy sets byte-equal to the restatement and to rt_prepare_instances run per pose; flags; records; flagged
    instances never hit;
-2. identity at both poses, times in {0, 0.25, 0.5, 1}: records byte-equal to rt_intersect_rays, the same triangle tests;
+2. identity at both poses, times in {0, 0.25, 0.5, 1}: records byte-equal to rt_intersect_rays, the same triangle tests (grid,
+   soup and the deep-stack fractal);
 3. exact composition: the minimum over the instances of rt_intersect_rays on the restated float32 object rays, byte for byte,
    with the eight fixed times and with uniformly random ones;
 4. float64 brute force per time value (test_gpu_instances._check_world); 5. pose 1 == pose 0; 6. a motion that is singular in
@@ -239,7 +240,7 @@ def test_prepare_bit_exact_and_flags(world, comp):
 
 
 # ------------------------------------------------------------------ 2: identity at both poses == rt_intersect_rays
-@pytest.mark.parametrize("name", ("grid", "soup"))
+@pytest.mark.parametrize("name", ("grid", "soup", "fractal"))
 @pytest.mark.parametrize("tree", rq.TREES)
 def test_identity_instance_equals_intersect_rays(world, name, tree):
     rt = world.rt

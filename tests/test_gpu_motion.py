@@ -3,7 +3,8 @@ make (the eight of test_gpu_ray_queries.TREES) over grid_mesh(24, 5), soup(1500)
 displacement (a function of position alone, so pairs stay whole); the times are motion_ref.TIMES = {0, 0.25, 1/3, 0.7, 1}.
 
 1. endpoints: every time 0 (1) gives rt_intersect_rays's records over pose 0 (pose 1) -- primitive_id exactly, t / u / v with ==
-   (a zero's sign may differ) -- and its counters [0], [1]; closest-hit and any-hit;
+   (a zero's sign may differ) -- and its counters [0], [1]; closest-hit and any-hit; also on fractal_corner(4000), whose rays
+   reach the private half of the traversal stack;
 2. between the poses: one time per ray, the records against motion_ref's float64 brute force per time group with the
    assertions and bounds of test_gpu_ray_queries._check_against_f64; on non-pair trees the record is bit for bit the float32
    Moller-Trumbore of the float32-interpolated triangle;
@@ -73,19 +74,24 @@ def _squery(rt, pose, root, count, rays, any_hit=False):
     return rq._query(rt, (pose, root, count), np.ascontiguousarray(rays.astype(rt.RAY)), any_hit=any_hit, counters=True)
 
 
-def _assert_same_records(got, exp, what):
+def _assert_same_records(got, exp, what, nan_is_nan=False):
     for f in ("primitive_id", "t", "u", "v"):     # (the floats with ==: a zero's sign may differ)
-        assert (got[f] == exp[f]).all(), f"{what}: {f} differs on {(got[f] != exp[f]).sum()} rays"
+        same = got[f] == exp[f]
+        if nan_is_nan and f != "primitive_id":
+            # the fractal alone: a ray's determinant against a triangle of size 2^42 overflows (a = inf, f = 0, u = 0 * inf) and
+            # Moller-Trumbore's range tests let the NaN through, in the static query as here; there a NaN equals a NaN
+            same |= np.isnan(got[f]) & np.isnan(exp[f])
+        assert same.all(), f"{what}: {f} differs on {(~same).sum()} rays"
 
 
-def _check_endpoints(rt, mg, rays, what):
+def _check_endpoints(rt, mg, rays, what, nan_is_nan=False):
     pose0, pose1, _, root, count = mg
     for tau, pose in ((0.0, pose0), (1.0, pose1)):
         for any_hit in (False, True):
             got, gc = _mquery(rt, mg, rays, np.full(len(rays), tau, F), any_hit=any_hit)
             exp, ec = _squery(rt, pose, root, count, rays, any_hit=any_hit)
             w = f"{what} time {tau} any_hit={any_hit}"
-            _assert_same_records(got, exp, w)
+            _assert_same_records(got, exp, w, nan_is_nan)
             assert (gc[:2] == ec[:2]).all(), f"{w}: counters {gc[:2]} vs the static query's {ec[:2]}"
 
 
@@ -117,7 +123,8 @@ class World:
         return self._memo(("cases", name), make)
 
     def all_rays(self, name):
-        c = self.cases(name)
+        """the rays and times of cases(name), without its float64 references"""
+        c = self._memo(("rays", name), lambda: mr.ray_cases(name, *self.poses(name)))
         return np.concatenate([c[k][0] for k in c]), np.concatenate([c[k][1] for k in c])
 
     def gpu(self, name, tree):
@@ -139,11 +146,11 @@ def world(rt, scenes):
 
 
 # ------------------------------------------------------------------ 1
-@pytest.mark.parametrize("name", mr.SCENES)
+@pytest.mark.parametrize("name", mr.ENDPOINT_SCENES)
 @pytest.mark.parametrize("tree", TREES)
 def test_endpoints_are_the_static_query(world, name, tree):
     rays, _ = world.all_rays(name)
-    _check_endpoints(world.rt, world.gpu(name, tree), rays, f"{name}/{tree}")
+    _check_endpoints(world.rt, world.gpu(name, tree), rays, f"{name}/{tree}", nan_is_nan=name == "fractal")
 
 
 # ------------------------------------------------------------------ 2
