@@ -8,7 +8,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), sphere primitives
-(``PrepareSpheres``, ``IntersectRaysSpheres``: ray queries over a tree built on spheres), and closest-point queries
+(``PrepareSpheres``, ``IntersectRaysSpheres``: ray queries over a tree built on spheres), mixed instancing
+(``geometry_table``, ``IntersectRaysInstancedMixed``: triangle and sphere BLASes under one TLAS), and closest-point queries
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
@@ -76,6 +77,10 @@ RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
 SPHERE = np.dtype([("center", "<f4", 3), ("radius", "<f4")])                                                 # 16 B
 assert SPHERE.itemsize == 16
 RT_SPHERE_BAD = 1
+# mixed instancing (rt_intersect_rays_instanced_mixed): what the leaves of each BLAS hold, parallel to the ACCEL table
+GEOMETRY = np.dtype([("data", "<u8"), ("count", "<u4"), ("kind", "<u4")])                                    # 16 B
+RT_GEOM_TRIANGLES = 0
+RT_GEOM_SPHERES = 1
 # ray sorting (rt_sort_rays): a dead ray's key; every live key is below it
 RAY_KEY_BITS, RAY_KEY_DEAD = 30, 1 << 29
 # closest-point queries (rt_closest_points)
@@ -218,7 +223,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_intersect_rays", "rt_generate_camera_rays", "rt_refit_plan_bytes", "rt_refit_plan_layout_get",
            "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
            "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_prepare_motion_instances",
-           "rt_intersect_rays_instanced_motion", "rt_prepare_spheres", "rt_intersect_rays_spheres", "rt_closest_points",
+           "rt_intersect_rays_instanced_motion", "rt_prepare_spheres", "rt_intersect_rays_spheres",
+           "rt_intersect_rays_instanced_mixed", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
            "rt_ray_hits_scratch_bytes", "rt_ray_hits_count", "rt_ray_hits_collect",
@@ -307,6 +313,8 @@ def lib() -> ctypes.CDLL:
     L.rt_prepare_spheres.argtypes = [vp, u32, vp, vp, vp]
     L.rt_intersect_rays_spheres.restype = i32
     L.rt_intersect_rays_spheres.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, i32, vp, vp]
+    L.rt_intersect_rays_instanced_mixed.restype = i32
+    L.rt_intersect_rays_instanced_mixed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, vp, vp, u32, i32, vp, vp]
     L.rt_closest_points.restype = i32
     L.rt_closest_points.argtypes = [ctypes.POINTER(_Accel), vp, vp, u32, vp, vp, vp]
     L.rt_range_scratch_bytes.restype = ctypes.c_size_t
@@ -846,6 +854,46 @@ def IntersectRaysSpheres(triangles, nodes, root: int, count: int, spheres, num_s
     _check(lib().rt_intersect_rays_spheres(ctypes.byref(a), _ptr(spheres), ns, _ptr(rays), n, _ptr(order), k, _ptr(hits),
                                            kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
            "rt_intersect_rays_spheres")
+
+
+def geometry_table(entries, device="cuda"):
+    """The device geometry table of mixed instancing, parallel to accel_table's: one rt_geometry per BLAS.  An entry is None
+    for a triangle BLAS, or (spheres, num_spheres) for a sphere BLAS -- the device SPHERE buffer its tree was prepared from.
+    The caller keeps the sphere buffers alive."""
+    tab = np.zeros(len(entries), GEOMETRY)
+    for k, e in enumerate(entries):
+        if e is None:
+            tab[k] = (0, 0, RT_GEOM_TRIANGLES)
+            continue
+        spheres, ns = e
+        if int(ns) and (not spheres.is_contiguous() or _nbytes(spheres) < 16 * int(ns)):
+            raise ValueError(f"entry {k}: spheres must be a contiguous device buffer of {int(ns)} 16-byte records")
+        tab[k] = (_ptr(spheres), int(ns), RT_GEOM_SPHERES)
+    return to_device(tab, device)
+
+
+def IntersectRaysInstancedMixed(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                geom_table, num_blas: int, rays, hits, instance_ids, *, any_hit: bool = False, counters=None,
+                                stream=None) -> None:
+    """rt_intersect_rays_instanced_mixed: IntersectRaysInstanced over a BLAS table whose trees hold triangles or spheres;
+    `geom_table` (geometry_table, parallel to `blas_table`) says which.  A hit in a triangle BLAS is IntersectRaysInstanced's
+    record, a hit in a sphere BLAS is IntersectRaysSpheres's (t, the sphere index, u = 1 for the far root, v = 0); tell them
+    apart by instance_ids[i] -> records[].blas -> the table's kind.  geom_table=None: every BLAS holds triangles
+    (IntersectRaysInstanced with num_primitives = 0).  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits / instance_ids contiguous buffers")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records and instance_ids {n} words")
+    if geom_table is not None and (not geom_table.is_contiguous() or _nbytes(geom_table) < 16 * int(num_blas)):
+        raise ValueError(f"geom_table must be a contiguous device buffer of {int(num_blas)} 16-byte records")
+    if n == 0:
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced_mixed(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                   _ptr(geom_table), int(num_blas), _ptr(rays), _ptr(hits), _ptr(instance_ids),
+                                                   n, kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_mixed")
 
 
 def ClosestPoints(triangles, nodes, root: int, count: int, queries, hits, *, counters=None, status=None, stream=None) -> None:

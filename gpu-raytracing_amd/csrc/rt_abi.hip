@@ -535,6 +535,40 @@ int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint
                                       mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_geometry) == 16, "rt_abi.h: rt_geometry is one 16-byte record");
+
+int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                      const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                      const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, int mode,
+                                      uint64_t* counters, void* stream)
+{
+    // no table: every BLAS holds triangles (the sibling, without the pair-prefetch arm)
+    if (!geom_table)
+        return rt_intersect_rays_instanced(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays,
+                                           mode, 0u, counters, stream);
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
+        misaligned(blas_table, 8) || misaligned(geom_table, 16))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    InstanceQuery q;
+    q.tlas = *tlas;
+    q.records = records;
+    q.num_instances = num_instances;
+    q.blas_table = blas_table;
+    q.num_blas = num_blas;
+    q.rays = rays;
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    q.num_rays = num_rays;
+    q.any_hit = mode == RT_RAY_ANY_HIT;
+    q.num_primitives = 0;
+    q.counters = counters;
+    return hip_rc(launch_instance_mixed_query(q, geom_table, static_cast<hipStream_t>(stream)));
+}
+
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
                       uint64_t* counters, uint32_t* status, void* stream)
 {
@@ -794,6 +828,9 @@ const char* rt_version_string(void)
            "spheres: ray queries over a tree built on sphere proxies (one prepare launch, padded boxes, any builder, refit "
            "for moving spheres), the ray query's box phase with a sphere test at the leaf (two dependent 16-byte loads, the "
            "discriminant from the perpendicular offset), closest / any hit, direct or through an index list | "
+           "instance_mixed: the instanced ray query over triangle and sphere BLASes in one TLAS, a 16-byte geometry record per "
+           "BLAS read on entry (kind, sphere array, count kept per lane), the leaf phase tests a triangle pair or a sphere by "
+           "the lane's kind on the object-space ray, one tmax across both, the record shape by the hit instance's kind | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
            "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
            "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "

@@ -560,14 +560,69 @@ int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_mot
  * 4-byte aligned; as->count > 7 (or a null tree pointer with count > 0); a bad mode.  Zero counts run nothing, except that
  * prepare still clears *status.
  *
- * Out of scope: spheres as a BLAS kind inside the instanced query; mixed triangle / sphere trees; motion, filters, all-hit and
- * first-K forms; point queries against spheres; the C++ host mirror and rt_cli. */
+ * Spheres as a BLAS kind under a TLAS, beside triangle BLASes: the mixed-instancing block below.
+ * Out of scope: mixed triangle / sphere trees (both kinds of leaf inside ONE tree); motion, filters, all-hit and first-K
+ * forms; point queries against spheres; the C++ host mirror and rt_cli. */
 typedef struct rt_sphere { rt_float3 center; float radius; } rt_sphere;   /* 16 bytes */
 enum { RT_SPHERE_BAD = 1 };
 int rt_prepare_spheres(const rt_sphere* spheres, uint32_t num_spheres, rt_triangle* proxies, uint32_t* status, void* stream);
 int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint32_t num_spheres, const rt_ray* rays,
                               uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
                               uint64_t* counters, void* stream);
+
+/* ---- mixed instancing (no reference counterpart).  The instanced ray query over a BLAS table whose trees hold triangles OR
+ * spheres: a surface mesh with atoms, particles inside geometry, sphere-swept obstacles in a robot cell -- one TLAS, one walk,
+ * one tmax across both kinds, an any-hit ray that stops at the first primitive of either.  Nothing new is prepared or built:
+ * rt_prepare_instances reads only the root run's boxes of a BLAS, so a sphere tree (sphere block) is a valid BLAS for it as it
+ * is, and the TLAS is the instancing block's.
+ *
+ * rt_geometry (16 bytes; a DEVICE array parallel to the BLAS table, 16-byte aligned): what the leaves of blas_table[b] hold.
+ *   kind   RT_GEOM_TRIANGLES: any tree rt_intersect_rays_instanced takes; data and count are not read.
+ *          RT_GEOM_SPHERES: a tree built by any builder over rt_prepare_spheres's proxies with enable_pairs = enable_splits = 0
+ *          (sphere block); data = the const rt_sphere* array the proxies were made from (16-byte aligned: the caller's duty, it
+ *          is a device value no host check sees), count = num_spheres.
+ *
+ * rt_intersect_rays_instanced_mixed: everything rt_intersect_rays_instanced says holds word for word -- the records and the TLAS
+ * over rt_prepare_instances's proxies, rays, hits, instance_ids, mode, alignment, the NaN and empty-range rules, ONE 64-entry
+ * stack shared by both levels, the object-space ray (o' = W*(o, 1), d' = W3x3*d, row by row, 1/d' by IEEE division), the world
+ * ray reloaded from rays[i] on leaving an instance, the cases in which an instance is never entered, asynchronous execution and
+ * hipGraph capture.  There is NO num_primitives hint and no pair-prefetch arm, as in the sphere and instance-motion queries.
+ *   Entering an instance: its record, then blas_table[blas] (three 8-byte loads), then geom_table[blas] as ONE 16-byte load.
+ *   Besides rt_intersect_rays_instanced's cases an instance is NOT ENTERED when kind is neither RT_GEOM_* value, or kind ==
+ *   RT_GEOM_SPHERES and data is null.  count == 0 enters the instance and tests nothing.
+ *   Triangle BLAS: the walk, the leaf test and the record are rt_intersect_rays_instanced's: t, primitive_id, (u, v) for the
+ *   caller's corners through the leaf's rotations.
+ *   Sphere BLAS: the box phase is the same, on the object-space ray.  At a leaf, with the object-space ray, the sphere
+ *   block's steps in its order: id = the leaf's primitive_id_0 (its first 16 bytes); the leaf is skipped when id >= count;
+ *   data[id] as one 16-byte load; the sphere is skipped when !(r >= 0) || r == +inf; one test is counted; the sphere block's
+ *   test, operation by operation.  An affine map preserves t and the test never assumes a unit direction (a = |d'|^2), so t is
+ *   the world-space distance in units of |dir|; under a non-uniform object_to_world the sphere is an ellipsoid in the world.
+ *   The record is rt_intersect_rays_spheres's: t, primitive_id = the sphere index, u = 1.0f when t_far was taken else 0.0f,
+ *   v = 0.  The caller tells the two record shapes apart by instance_ids[i] -> records[].blas -> geom_table[].kind.
+ *   One tmax runs across all instances of both kinds; an equal t is accepted, so ties go to the primitive tested later.
+ *   mode RT_RAY_ANY_HIT ends the ray at the first accepted primitive of either kind.
+ *   Counters (optional, added to): [0] box tests of both levels together, [1] triangle-leaf tests plus sphere tests, each
+ *   counted as rt_intersect_rays_instanced / rt_intersect_rays_spheres counts them, [2] / [3] wave steps.
+ *   Identity instance over a sphere tree: the same hit records and sphere tests as rt_intersect_rays_spheres on that tree for
+ *   rays without -0 components.  A table of RT_GEOM_TRIANGLES only: the same hits, instance ids, box and triangle tests as
+ *   rt_intersect_rays_instanced with num_primitives = 0.
+ * geom_table == NULL: every BLAS holds triangles -- the call IS rt_intersect_rays_instanced with num_primitives = 0 (its
+ * argument checks, its kernel), as filter == NULL in the filtered calls.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): rt_intersect_rays_instanced's, and geom_table not
+ * 16-byte aligned.  Errors win over num_rays = 0, which runs nothing.
+ *
+ * Out of scope: filtered, motion, indexed, all-hit and first-K mixed forms; triangles and spheres inside one BLAS; the C++ host
+ * mirror and rt_cli. */
+enum { RT_GEOM_TRIANGLES = 0, RT_GEOM_SPHERES = 1 };
+typedef struct rt_geometry {      /* 16 bytes; DEVICE array parallel to the BLAS table */
+    const void* data;             /* RT_GEOM_SPHERES: const rt_sphere*, 16-byte aligned (caller's duty); TRIANGLES: not read */
+    uint32_t    count;            /* RT_GEOM_SPHERES: num_spheres; TRIANGLES: not read */
+    uint32_t    kind;             /* RT_GEOM_* */
+} rt_geometry;
+int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                      const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                      const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays,
+                                      int mode, uint64_t* counters, void* stream);
 
 /* ---- closest-point queries (no reference counterpart).  For each caller point: which triangle is nearest, where on it, and
  * how far away -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and
