@@ -8,7 +8,8 @@ This module binds that C ABI with ctypes and mirrors the reference's entry point
 tree (``GenerateCameraRays``, ``IntersectRays``: rays tensor in, hits tensor out) and refit of a built tree after its
 vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instancing (``accel_table``,
 ``PrepareInstances``, ``IntersectRaysInstanced``: ray queries over placed copies of built trees), sphere primitives
-(``PrepareSpheres``, ``IntersectRaysSpheres``: ray queries over a tree built on spheres), mixed instancing
+(``PrepareSpheres``, ``IntersectRaysSpheres``: ray queries over a tree built on spheres), capsule primitives
+(``PrepareCapsules``, ``IntersectRaysCapsules``: ray queries over a tree built on round linear segments), mixed instancing
 (``geometry_table``, ``IntersectRaysInstancedMixed``: triangle and sphere BLASes under one TLAS), and closest-point queries
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
@@ -77,6 +78,10 @@ RT_INSTANCE_BAD_BLAS, RT_INSTANCE_SINGULAR = 1, 2
 SPHERE = np.dtype([("center", "<f4", 3), ("radius", "<f4")])                                                 # 16 B
 assert SPHERE.itemsize == 16
 RT_SPHERE_BAD = 1
+# capsule primitives (rt_prepare_capsules / rt_intersect_rays_capsules)
+CAPSULE = np.dtype([("p0", "<f4", 3), ("radius", "<f4"), ("p1", "<f4", 3), ("pad", "<u4")])                  # 32 B
+assert CAPSULE.itemsize == 32
+RT_CAPSULE_BAD = 1
 # mixed instancing (rt_intersect_rays_instanced_mixed): what the leaves of each BLAS hold, parallel to the ACCEL table
 GEOMETRY = np.dtype([("data", "<u8"), ("count", "<u4"), ("kind", "<u4")])                                    # 16 B
 RT_GEOM_TRIANGLES = 0
@@ -224,6 +229,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
            "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_prepare_motion_instances",
            "rt_intersect_rays_instanced_motion", "rt_prepare_spheres", "rt_intersect_rays_spheres",
+           "rt_prepare_capsules", "rt_intersect_rays_capsules",
            "rt_intersect_rays_instanced_mixed", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
@@ -313,6 +319,10 @@ def lib() -> ctypes.CDLL:
     L.rt_prepare_spheres.argtypes = [vp, u32, vp, vp, vp]
     L.rt_intersect_rays_spheres.restype = i32
     L.rt_intersect_rays_spheres.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, i32, vp, vp]
+    L.rt_prepare_capsules.restype = i32
+    L.rt_prepare_capsules.argtypes = [vp, u32, vp, vp, vp]
+    L.rt_intersect_rays_capsules.restype = i32
+    L.rt_intersect_rays_capsules.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, i32, vp, vp]
     L.rt_intersect_rays_instanced_mixed.restype = i32
     L.rt_intersect_rays_instanced_mixed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, vp, vp, u32, i32, vp, vp]
     L.rt_closest_points.restype = i32
@@ -854,6 +864,57 @@ def IntersectRaysSpheres(triangles, nodes, root: int, count: int, spheres, num_s
     _check(lib().rt_intersect_rays_spheres(ctypes.byref(a), _ptr(spheres), ns, _ptr(rays), n, _ptr(order), k, _ptr(hits),
                                            kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
            "rt_intersect_rays_spheres")
+
+
+def PrepareCapsules(capsules, num_capsules: int, proxies, status, stream=None) -> None:
+    """rt_prepare_capsules: `capsules` (CAPSULE records, device, e.g. float32 [N, 8]: p0, radius, p1, pad) -> `proxies`
+    (num_capsules TRIANGLE records: the build input of any builder with pairs and splits off; prepare into them again and Refit
+    for moving capsules) and `status` (a device uint32 the call clears; RT_CAPSULE_BAD when a capsule is not valid, see
+    capsule_status).  Asynchronous on `stream`."""
+    n = int(num_capsules)
+    for name, buf, size in (("capsules", capsules, 32), ("proxies", proxies, 36)):
+        if n and (not buf.is_contiguous() or _nbytes(buf) < size * n):
+            raise ValueError(f"{name} must be a contiguous device buffer of {n} {size}-byte records")
+    _check(lib().rt_prepare_capsules(_ptr(capsules), n, _ptr(proxies), _ptr(status), _stream_ptr(stream)),
+           "rt_prepare_capsules")
+
+
+def capsule_status(status) -> int:
+    """The RT_CAPSULE_* flags of the last PrepareCapsules (copies the word back: waits for the work queued before it)."""
+    return _status_word(status)
+
+
+def IntersectRaysCapsules(triangles, nodes, root: int, count: int, capsules, num_capsules: int, rays, hits, *,
+                          any_hit: bool = False, order=None, num_indices: Optional[int] = None, counters=None,
+                          stream=None) -> None:
+    """rt_intersect_rays_capsules: IntersectRaysSpheres over a tree built on PrepareCapsules's proxies and the `capsules` it was
+    prepared from.  A HIT record carries t, the capsule index as primitive_id, u = 1 when the ray began inside the capsule (its
+    far crossing was taken) else 0, and v = where along the axis the ray crossed: 0 on p0's cap, 1 on p1's cap, between them on
+    the body; a miss is {+inf, MISS, 0, 0}.  `order`, num_indices, counters (box tests, capsule tests, wave steps) as for
+    IntersectRaysSpheres.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    nc = int(num_capsules)
+    if nc and (not capsules.is_contiguous() or _nbytes(capsules) < 32 * nc):
+        raise ValueError(f"capsules must be a contiguous device buffer of {nc} 32-byte records")
+    k = 0
+    if order is not None:
+        if not order.is_contiguous():
+            raise ValueError("order must be a contiguous device buffer")
+        k = _nbytes(order) // 4 if num_indices is None else int(num_indices)
+        if _nbytes(order) < 4 * k:
+            raise ValueError(f"order must hold {k} words")
+        if k == 0:
+            return
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_intersect_rays_capsules(ctypes.byref(a), _ptr(capsules), nc, _ptr(rays), n, _ptr(order), k, _ptr(hits),
+                                            kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_capsules")
 
 
 def geometry_table(entries, device="cuda"):

@@ -1,0 +1,161 @@
+// capsule_query.hip -- rt_prepare_capsules and rt_intersect_rays_capsules: ray queries over a tree built on capsules (round
+// linear segments; semantics: rt_abi.h, capsule block).
+//
+// prepare_capsules_kernel, one thread per capsule: two 16-byte loads, the padded box of the two end spheres as a proxy
+// triangle (rt_prepare_spheres's arithmetic on the union; rt_instance_proxy.hpp's proxy_triangle), an invalid capsule flagged
+// and given the point proxy.
+//
+// capsule_query_kernel<ANY, INDEXED>: sphere_query_kernel's launch shape -- one lane per ray, 64 consecutive rays (or order[]
+// entries) per wave, kTraceWaves waves per workgroup, workgroups remapped to XCDs in chunks of 8, the lane-interleaved LDS
+// stack with its private spill, counters wave-reduced, added in LDS and published with 4 device atomics per workgroup -- on
+// the traversal of rt_capsule_traverse.hpp: the tracer's box phase, a capsule test at the leaf.  A ray is two 16-byte loads,
+// a leaf visit one 16-byte load (the leaf's first quarter for the index) and then two independent ones (the capsule), the
+// record one 16-byte store.  Lanes past the batch, rays with an empty or NaN [tmin, tmax] and rays with a NaN component trace
+// nothing, as in sphere_query_kernel.  No pair-prefetch arm, no hold at pop.
+// Compiled with -ffp-contract=off: every float operation is the documented one.
+#include "rt_device.hpp"
+#include "rt_launch.hpp"
+#include "rt_instance_proxy.hpp"
+#include "rt_capsule_traverse.hpp"
+#include "rt_traverse.hpp"
+
+static_assert(sizeof(rt_capsule) == 32 && offsetof(rt_capsule, radius) == 12 && offsetof(rt_capsule, p1) == 16,
+              "rt_capsule: two 16-byte halves (p0, radius), (p1, pad)");
+static_assert(rt::kQueryBlock == rt::kTraceWaves * 64, "rt_launch.hpp: one lane per ray, kTraceWaves waves per workgroup");
+
+namespace rt {
+
+namespace {
+
+constexpr float kCapsulePad = 1.0f / 262144.0f;   // 2^-18 of the box's largest |bound| (rt_abi.h)
+
+// ---------------------------------------------------------------- prepare
+__global__ __launch_bounds__(256) void prepare_capsules_kernel(const float4* capsules, uint32_t num_capsules,
+                                                               rt_triangle* proxies, uint32_t* status)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= num_capsules) return;
+    const float4 c0 = capsules[2 * (uint64_t)i], c1 = capsules[2 * (uint64_t)i + 1];
+    const bool valid = __builtin_isfinite(c0.x) && __builtin_isfinite(c0.y) && __builtin_isfinite(c0.z) &&
+                       __builtin_isfinite(c1.x) && __builtin_isfinite(c1.y) && __builtin_isfinite(c1.z) && c0.w >= 0.0f &&
+                       c0.w < __builtin_inff();
+    rt_triangle px = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};   // invalid: a point proxy at the origin
+    if (valid) {
+        const float p0[3] = {c0.x, c0.y, c0.z}, p1[3] = {c1.x, c1.y, c1.z};
+        Box3 bx;
+        float e = 0.0f;
+        for (int k = 0; k < 3; k++) {
+            bx.lo[k] = fminf(p0[k] - c0.w, p1[k] - c0.w);
+            bx.hi[k] = fmaxf(p0[k] + c0.w, p1[k] + c0.w);
+            e = fmaxf(e, fmaxf(fabsf(bx.lo[k]), fabsf(bx.hi[k])));
+        }
+        const float pad = e * kCapsulePad;
+        for (int k = 0; k < 3; k++) { bx.lo[k] = bx.lo[k] - pad; bx.hi[k] = bx.hi[k] + pad; }
+        px = proxy_triangle(bx);
+    }
+    proxies[i] = px;
+    if (!valid) atomicOr(status, (uint32_t)RT_CAPSULE_BAD);
+}
+
+// ---------------------------------------------------------------- query
+// launch position j -> ray index (0xFFFFFFFF: no ray -- num_rays is a uint32, so it is never in range)
+template <bool INDEXED>
+__device__ __forceinline__ uint64_t capsule_ray_index(const CapsuleParams& p, uint64_t j)
+{
+    if constexpr (INDEXED) return j < p.num_indices ? p.order[j] : 0xFFFFFFFFull;
+    else return j;
+}
+
+template <bool ANY, bool INDEXED>
+__global__ __launch_bounds__(kTraceWaves * 64, RT_CAPSULE_WAVES)
+void capsule_query_kernel(CapsuleParams p)
+{
+    __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
+    __shared__ unsigned long long csum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (p.counters) {                         // (kernel argument: the same for every thread)
+        if (threadIdx.x < 4) csum[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
+    const uint64_t i = capsule_ray_index<INDEXED>(p, ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane);
+    const bool in_range = i < p.num_rays;
+
+    float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, -1.f};
+    if (in_range) { a = p.rays[2 * i]; b = p.rays[2 * i + 1]; }
+    Ray r;
+    r.ox = a.x; r.oy = a.y; r.oz = a.z; r.tmin = a.w;
+    r.dx = b.x; r.dy = b.y; r.dz = b.z; r.tmax = b.w;
+    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
+    // not traced (a miss, no tests): as sphere_query_kernel
+    const bool nan_ray = __builtin_isnan(r.ox) | __builtin_isnan(r.oy) | __builtin_isnan(r.oz) | __builtin_isnan(r.dx) |
+                         __builtin_isnan(r.dy) | __builtin_isnan(r.dz);
+    const bool active = in_range && r.tmin <= r.tmax && !nan_ray;
+
+    SpillArray spill;
+    Trav t;
+    t.lds = (lds_u32*)&stack_lds[wave][0][lane];
+    t.spill = spill;
+    uint32_t steps[2] = {0u, 0u};
+    CapsuleHit h = {0u, 0.f, 0.f};
+    const bool hit = trace_ray_capsules<ANY>(p, r, h, t, active, steps);
+
+    if (in_range) {
+        float4 o = {__builtin_inff(), __uint_as_float(RT_MISS), 0.f, 0.f};
+        if (hit) o = float4{r.tmax, __uint_as_float(h.id), h.far_root, h.v};
+        p.hits[i] = o;
+    }
+    if (p.counters) {
+        const uint32_t bsum = wave_sum_u32(t.box_tests), tsum = wave_sum_u32(t.tri_tests);
+        if (lane == 0) {
+            atomicAdd(&csum[0], (unsigned long long)bsum);
+            atomicAdd(&csum[1], (unsigned long long)tsum);
+            atomicAdd(&csum[2], (unsigned long long)steps[0]);
+            atomicAdd(&csum[3], (unsigned long long)steps[1]);
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const unsigned long long v = csum[threadIdx.x];
+            if (v) atomicAdd(&p.counters[threadIdx.x], v);
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_prepare_capsules(const rt_capsule* capsules, uint32_t num_capsules, rt_triangle* proxies, uint32_t* status,
+                                   hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess || num_capsules == 0) return e;
+    prepare_capsules_kernel<<<dim3((num_capsules + 255) / 256), dim3(256), 0, st>>>(reinterpret_cast<const float4*>(capsules),
+                                                                                    num_capsules, proxies, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_capsule_query(const rt_accel& as, const rt_capsule* capsules, uint32_t num_capsules, const rt_ray* rays,
+                                uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, bool any_hit,
+                                uint64_t* counters, hipStream_t st)
+{
+    CapsuleParams p;
+    set_tree(p, as);
+    p.capsules = reinterpret_cast<const float4*>(capsules);
+    p.num_capsules = num_capsules;
+    p.rays = reinterpret_cast<const float4*>(rays);
+    p.hits = reinterpret_cast<float4*>(hits);
+    p.num_rays = num_rays;
+    p.counters = reinterpret_cast<unsigned long long*>(counters);
+    p.order = order;
+    p.num_indices = order ? num_indices : 0u;
+    const dim3 grid(query_blocks(order ? num_indices : num_rays)), block(kQueryBlock);
+    if (order) {
+        if (any_hit) capsule_query_kernel<true, true><<<grid, block, 0, st>>>(p);
+        else capsule_query_kernel<false, true><<<grid, block, 0, st>>>(p);
+    } else {
+        if (any_hit) capsule_query_kernel<true, false><<<grid, block, 0, st>>>(p);
+        else capsule_query_kernel<false, false><<<grid, block, 0, st>>>(p);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace rt

@@ -535,6 +535,32 @@ int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint
                                       mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
 }
 
+static_assert(sizeof(rt_capsule) == 32, "rt_abi.h: rt_capsule is one 32-byte record");
+
+int rt_prepare_capsules(const rt_capsule* capsules, uint32_t num_capsules, rt_triangle* proxies, uint32_t* status, void* stream)
+{
+    if (!status || misaligned(status, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(capsules, 16) || misaligned(proxies, 16)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_capsules && (!capsules || !proxies)) return RT_ERR_INVALID_ARGUMENT;
+    return hip_rc(launch_prepare_capsules(capsules, num_capsules, proxies, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_capsules(const rt_accel* as, const rt_capsule* capsules, uint32_t num_capsules, const rt_ray* rays,
+                               uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
+                               uint64_t* counters, void* stream)
+{
+    if (!tree_args(as)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(capsules, 16) || misaligned(rays, 16) || misaligned(hits, 16) || misaligned(order, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_capsules && !capsules) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays && (!rays || !hits)) return RT_ERR_INVALID_ARGUMENT;
+    // nothing to launch: no ray, or an index list without an entry
+    if (num_rays == 0 || (order && num_indices == 0)) return RT_OK;
+    return hip_rc(launch_capsule_query(*as, capsules, num_capsules, rays, num_rays, order, num_indices, hits,
+                                       mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
+}
+
 static_assert(sizeof(rt_geometry) == 16, "rt_abi.h: rt_geometry is one 16-byte record");
 
 int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
@@ -828,6 +854,10 @@ const char* rt_version_string(void)
            "spheres: ray queries over a tree built on sphere proxies (one prepare launch, padded boxes, any builder, refit "
            "for moving spheres), the ray query's box phase with a sphere test at the leaf (two dependent 16-byte loads, the "
            "discriminant from the perpendicular offset), closest / any hit, direct or through an index list | "
+           "capsules: ray queries over a tree built on capsule proxies (round linear segments; one prepare launch, the padded "
+           "box of both end spheres, any builder, refit for moving capsules), the sphere query's loop with a capsule test at "
+           "the leaf (one 16-byte load, then two independent ones; the ray re-based at its point nearest the midpoint, the "
+           "infinite cylinder's roots choose the body or one end sphere by side), closest / any hit, direct or indexed | "
            "instance_mixed: the instanced ray query over triangle and sphere BLASes in one TLAS, a 16-byte geometry record per "
            "BLAS read on entry (kind, sphere array, count kept per lane), the leaf phase tests a triangle pair or a sphere by "
            "the lane's kind on the object-space ray, one tmax across both, the record shape by the hit instance's kind | "

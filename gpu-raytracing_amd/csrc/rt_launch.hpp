@@ -242,6 +242,13 @@ hipError_t launch_sphere_query(const rt_accel& as, const rt_sphere* spheres, uin
                                uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, bool any_hit,
                                uint64_t* counters, hipStream_t st);
 
+// capsule_query.hip: rt_prepare_capsules / rt_intersect_rays_capsules after their argument checks (as the sphere pair)
+hipError_t launch_prepare_capsules(const rt_capsule* capsules, uint32_t num_capsules, rt_triangle* proxies, uint32_t* status,
+                                   hipStream_t st);
+hipError_t launch_capsule_query(const rt_accel& as, const rt_capsule* capsules, uint32_t num_capsules, const rt_ray* rays,
+                                uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, bool any_hit,
+                                uint64_t* counters, hipStream_t st);
+
 // ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
 struct RaySortLayout {
     size_t box;         // float lo[4], hi[4] at the start of the 256-byte header

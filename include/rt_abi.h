@@ -570,6 +570,86 @@ int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint
                               uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
                               uint64_t* counters, void* stream);
 
+/* ---- capsule primitives (no reference counterpart).  Ray queries over a set of CAPSULES -- round linear curve segments: a
+ * segment p0..p1 swept by a sphere of one radius; bonds between atoms, fibres, hair, streamlines, cables, the link capsules of
+ * a robot cell -- through a tree any builder makes over one PROXY TRIANGLE per capsule.  The sibling of the sphere block: every
+ * convention not restated here is that block's.
+ *
+ * rt_capsule (caller input, 32 bytes, 16-byte aligned): p0, radius, p1, pad (never read).  A capsule is VALID when both end
+ * points are finite and 0 <= radius < +inf.  p0 == p1 is valid (a sphere); radius == 0 is valid (a segment, which only a ray
+ * through it hits).
+ *
+ * rt_prepare_capsules, one launch after a clear of *status, one thread per capsule.  For a valid capsule, in float32:
+ *   - per axis lo = min(fl(p0 - r), fl(p1 - r)), hi = max(fl(p0 + r), fl(p1 + r));
+ *   - E = the largest |lo| or |hi| over the three axes; pad = fl(E * 2^-18); the box is [fl(lo - pad), fl(hi + pad)] (the
+ *     sphere block's pad and its reason: the box bounds both end spheres, hence their convex hull, and the slab test's error
+ *     is a matter of the box's magnitude alone);
+ *   - proxies[i] = {v0 = lo, v1 = hi, v2 = lo*0.5f + hi*0.5f} of that box.
+ *   For p0 == p1 this is rt_prepare_spheres's proxy of (p0, r), bit for bit.
+ * An invalid capsule ORs RT_CAPSULE_BAD into *status and gets the point proxy at the origin (v0 = v1 = v2 = 0).
+ *
+ * Tree: any of the three builders over `proxies` (num_triangles = num_capsules) with enable_pairs = enable_splits = 0.  A leaf's
+ * primitive_id_0 is then the capsule index.  Moving capsules: rt_prepare_capsules into the same proxies again, then rt_refit
+ * through a plan, or a rebuild.
+ *
+ * rt_intersect_rays_capsules: rays, the [tmin, tmax] window, the NaN and empty-range rules, the miss record, closest hit and
+ * RT_RAY_ANY_HIT, the order list (out-of-range entries skipped; rt_sort_rays's order usable as it is), the box phase, the
+ * counters' layout, alignment and asynchrony are rt_intersect_rays_spheres's.
+ *   At a leaf: id = primitive_id_0.  The leaf is skipped and not counted when id >= num_capsules or !(r >= 0) || r == +inf (a
+ *   non-finite end point rejects itself in the test).  Otherwise, with p0, p1, r the capsule and o, d the ray, in float32,
+ *   every operation rounded on its own, IEEE division, correctly rounded square root, every dot product x.y summed as
+ *   (x0*y0 + x1*y1) + x2*y2:
+ *       n = p1 - p0                                  (per axis)
+ *     Degenerate capsule -- nx == 0, ny == 0 and nz == 0: the sphere block's test on (c = p0, r), bit for bit; v = 0.
+ *     Otherwise the ray is re-based at its point nearest the capsule's midpoint, so that no later term is of the size of
+ *     |o - m|^2 (the sphere block's argument); all roots below are in tau = t - s on the ray q + tau*d:
+ *       m  = p0*0.5 + p1*0.5                         (per axis fl(fl(p0*0.5) + fl(p1*0.5)))
+ *       f  = o - m
+ *       a  = d.d;   b = -(f.d);   s = b / a
+ *       q  = f + s*d                                 (per axis fl(fx + fl(s*dx)))
+ *       nn = n.n;  nd = n.d;  nq = n.q;  qd = q.d;  qq = q.q
+ *       A  = nn*a - nd*nd                            (fl(fl(nn*a) - fl(nd*nd)), and so below)
+ *       C  = nn*(qq - r*r) - nq*nq
+ *       hn = nn*0.5                                  (the body spans -hn < y < hn, y = n.(point - m))
+ *     cap(g), the roots of an end sphere whose centre lies at -g from q -- the sphere block's steps with f = g:
+ *       bg = -(g.d);  sg = bg / a;  pg = g + sg*d;  l2 = pg.pg;  disc = r*r - l2;  ok = disc >= 0
+ *       hh = sqrt(disc / a);  near = sg - hh;  far = sg + hh
+ *       p0's cap is cap(fa), fa = q + 0.5*n (per axis fl(qx + fl(0.5*nx))); p1's is cap(fb), fb = q - 0.5*n.
+ *     A > 0 (the ray is not parallel to the axis):
+ *       B  = nn*qd - nq*nd;   h = B*B - A*C;   !(h >= 0): rejected
+ *       tau1 = (-B - sqrt(h)) / A;   tau2 = (-B + sqrt(h)) / A
+ *       y1 = nq + tau1*nd;   y2 = nq + tau2*nd
+ *       entry: tau1 with v = y1/nn + 0.5 (fl(fl(y1/nn) + 0.5)) when y1 > -hn and y1 < hn; else p0's cap's near root with v = 0
+ *              when y1 <= -hn; else p1's cap's near root with v = 1.  A cap that is not ok: rejected.
+ *       exit:  the same with tau2, y2 and the caps' far roots.
+ *       The cap is chosen by the cylinder root's side and a cap root is never tested for its own side: no crack at the seams.
+ *     !(A > 0) (parallel; a rounded-negative or NaN A included):
+ *       C > 0: rejected.  entry = the near root of p0's cap (v = 0) when nd > 0, else of p1's cap (v = 1); exit = the far root
+ *       of the other cap (v = 1 when nd > 0, else 0).  Either cap not ok: rejected.
+ *     Window:
+ *       t_near = s + entry;   t_far = s + exit
+ *       t = t_near if tmin <= t_near <= tmax, else t_far if tmin <= t_far <= tmax (the ray began inside), else rejected
+ *   An accepted t becomes the ray's tmax; an equal t is accepted, so ties go to the capsule tested later.
+ *   hits[i]: t, primitive_id = the capsule index, u = 1.0f when t_far was taken else 0.0f (the sphere record's u), v = the
+ *   axial parameter of the crossing taken: in (0, 1) on the body, exactly 0.0f on p0's cap, exactly 1.0f on p1's cap, 0.0f for
+ *   a degenerate capsule -- whose record is therefore rt_intersect_rays_spheres's, byte for byte.
+ *   Counters (optional, added to): [0] box tests, [1] capsule tests (leaves whose capsule was tested), [2] / [3] wave steps.
+ * Both calls are asynchronous (no host copy, no synchronisation: hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null status or as; null capsules / proxies with
+ * num_capsules > 0; null rays / hits with num_rays > 0; capsules / proxies / rays / hits not 16-byte aligned; status / order
+ * not 4-byte aligned; as->count > 7 (or a null tree pointer with count > 0); a bad mode.  Zero counts run nothing, except that
+ * prepare still clears *status.
+ *
+ * Out of scope: per-vertex radii (cone-spheres); a capsule kind in rt_geometry / the mixed instanced query; motion, filters,
+ * all-hit and first-K forms; point queries against capsules; capsules and other kinds in one tree; the C++ host mirror and
+ * rt_cli. */
+typedef struct rt_capsule { rt_float3 p0; float radius; rt_float3 p1; uint32_t pad; } rt_capsule;   /* 32 bytes; pad not read */
+enum { RT_CAPSULE_BAD = 1 };
+int rt_prepare_capsules(const rt_capsule* capsules, uint32_t num_capsules, rt_triangle* proxies, uint32_t* status, void* stream);
+int rt_intersect_rays_capsules(const rt_accel* as, const rt_capsule* capsules, uint32_t num_capsules, const rt_ray* rays,
+                               uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
+                               uint64_t* counters, void* stream);
+
 /* ---- mixed instancing (no reference counterpart).  The instanced ray query over a BLAS table whose trees hold triangles OR
  * spheres: a surface mesh with atoms, particles inside geometry, sphere-swept obstacles in a robot cell -- one TLAS, one walk,
  * one tmax across both kinds, an any-hit ray that stops at the first primitive of either.  Nothing new is prepared or built:
