@@ -82,6 +82,8 @@ RT_SPHERE_BAD = 1
 CAPSULE = np.dtype([("p0", "<f4", 3), ("radius", "<f4"), ("p1", "<f4", 3), ("pad", "<u4")])                  # 32 B
 assert CAPSULE.itemsize == 32
 RT_CAPSULE_BAD = 1
+# sphere cast (rt_sphere_cast): which part of the triangle the ball touched
+RT_SWEEP_NONE, RT_SWEEP_FACE, RT_SWEEP_EDGE, RT_SWEEP_CORNER, RT_SWEEP_OVERLAP = 0, 1, 2, 3, 4
 # mixed instancing (rt_intersect_rays_instanced_mixed): what the leaves of each BLAS hold, parallel to the ACCEL table
 GEOMETRY = np.dtype([("data", "<u8"), ("count", "<u4"), ("kind", "<u4")])                                    # 16 B
 RT_GEOM_TRIANGLES = 0
@@ -229,7 +231,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_build_refit_plan", "rt_refit", "rt_motion_validate", "rt_intersect_rays_motion",
            "rt_prepare_instances", "rt_intersect_rays_instanced", "rt_prepare_motion_instances",
            "rt_intersect_rays_instanced_motion", "rt_prepare_spheres", "rt_intersect_rays_spheres",
-           "rt_prepare_capsules", "rt_intersect_rays_capsules",
+           "rt_prepare_capsules", "rt_intersect_rays_capsules", "rt_sphere_cast",
            "rt_intersect_rays_instanced_mixed", "rt_closest_points",
            "rt_range_scratch_bytes", "rt_range_count", "rt_range_collect", "rt_k_nearest",
            "rt_ray_sort_scratch_bytes", "rt_ray_sort_layout_get", "rt_sort_rays", "rt_intersect_rays_indexed",
@@ -323,6 +325,8 @@ def lib() -> ctypes.CDLL:
     L.rt_prepare_capsules.argtypes = [vp, u32, vp, vp, vp]
     L.rt_intersect_rays_capsules.restype = i32
     L.rt_intersect_rays_capsules.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, i32, vp, vp]
+    L.rt_sphere_cast.restype = i32
+    L.rt_sphere_cast.argtypes = [ctypes.POINTER(_Accel), vp, vp, ctypes.c_float, u32, vp, u32, vp, vp, i32, vp, vp]
     L.rt_intersect_rays_instanced_mixed.restype = i32
     L.rt_intersect_rays_instanced_mixed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, vp, vp, u32, i32, vp, vp]
     L.rt_closest_points.restype = i32
@@ -915,6 +919,48 @@ def IntersectRaysCapsules(triangles, nodes, root: int, count: int, capsules, num
     _check(lib().rt_intersect_rays_capsules(ctypes.byref(a), _ptr(capsules), nc, _ptr(rays), n, _ptr(order), k, _ptr(hits),
                                             kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
            "rt_intersect_rays_capsules")
+
+
+def SphereCast(triangles, nodes, root: int, count: int, rays, hits, radii=None, radius: float = 0.0, features=None, order=None,
+               any_hit: bool = False, counters=None, *, num_indices: Optional[int] = None, stream=None) -> None:
+    """rt_sphere_cast: a ball swept along each ray over any triangle tree IntersectRays takes (`triangles` / `nodes`: the
+    builder's triangles_out / nodes_out, root / count of its root).  `radii` (optional): a contiguous device float32 buffer, one
+    world-space radius per ray; without it every ray takes `radius` (finite, not negative).  A HIT record carries t = the
+    centre's parameter at first contact, primitive_id, and (u, v) = the weights of the contact point on the triangle for the
+    caller's corners v1 and v2: the contact normal is (o + t*d - contact) / radius.  A miss is {+inf, MISS, 0, 0}.  `features`
+    (optional): a contiguous device uint32 / int32 buffer, one RT_SWEEP_* word per ray -- which part of the triangle was
+    touched, RT_SWEEP_OVERLAP when the ball touches at tmin already, RT_SWEEP_NONE on a miss.  A ray with a negative, NaN or
+    infinite radius is not traced.  Radius 0 gives IntersectRays's records.  `order`, num_indices and counters (box tests,
+    leaves visited, wave steps) as for IntersectRaysSpheres.  Asynchronous on `stream`."""
+    if not rays.is_contiguous() or not hits.is_contiguous() or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits a contiguous device buffer")
+    n = _nbytes(rays) // 32
+    if _nbytes(hits) < 16 * n:
+        raise ValueError(f"hits must hold {n} 16-byte records")
+    if radii is not None:
+        if not radii.is_contiguous() or radii.element_size() != 4 or not radii.dtype.is_floating_point or _nbytes(radii) < 4 * n:
+            raise ValueError(f"radii must be a contiguous device buffer of {n} float32 values")
+    else:
+        radius = float(radius)
+        if not (0.0 <= radius < float("inf")):
+            raise ValueError("radius must be finite and not negative")
+    if features is not None and (not features.is_contiguous() or features.element_size() != 4 or _nbytes(features) < 4 * n):
+        raise ValueError(f"features must be a contiguous device buffer of {n} 32-bit words")
+    k = 0
+    if order is not None:
+        if not order.is_contiguous():
+            raise ValueError("order must be a contiguous device buffer")
+        k = _nbytes(order) // 4 if num_indices is None else int(num_indices)
+        if _nbytes(order) < 4 * k:
+            raise ValueError(f"order must hold {k} words")
+        if k == 0:
+            return
+    if n == 0:
+        return
+    a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
+    _check(lib().rt_sphere_cast(ctypes.byref(a), _ptr(rays), _ptr(radii), float(radius), n, _ptr(order), k, _ptr(hits),
+                                _ptr(features), kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_sphere_cast")
 
 
 def geometry_table(entries, device="cuda"):

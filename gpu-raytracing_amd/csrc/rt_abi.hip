@@ -561,6 +561,23 @@ int rt_intersect_rays_capsules(const rt_accel* as, const rt_capsule* capsules, u
                                        mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
 }
 
+int rt_sphere_cast(const rt_accel* as, const rt_ray* rays, const float* radii, float radius, uint32_t num_rays,
+                   const uint32_t* order, uint32_t num_indices, rt_hit* hits, uint32_t* features, int mode, uint64_t* counters,
+                   void* stream)
+{
+    if (!tree_args(as)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(order, 4) || misaligned(radii, 4) || misaligned(features, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    // the one radius of a call without radii: finite and not negative (a NaN fails the first compare)
+    if (!radii && (!(radius >= 0.0f) || radius == __builtin_inff())) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays && (!rays || !hits)) return RT_ERR_INVALID_ARGUMENT;
+    // nothing to launch: no ray, or an index list without an entry
+    if (num_rays == 0 || (order && num_indices == 0)) return RT_OK;
+    return hip_rc(launch_sphere_cast(*as, rays, radii, radius, num_rays, order, num_indices, hits, features,
+                                     mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
+}
+
 static_assert(sizeof(rt_geometry) == 16, "rt_abi.h: rt_geometry is one 16-byte record");
 
 int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
@@ -858,6 +875,10 @@ const char* rt_version_string(void)
            "box of both end spheres, any builder, refit for moving capsules), the sphere query's loop with a capsule test at "
            "the leaf (one 16-byte load, then two independent ones; the ray re-based at its point nearest the midpoint, the "
            "infinite cylinder's roots choose the body or one end sphere by side), closest / any hit, direct or indexed | "
+           "spherecast: a ball swept along each ray over any triangle tree (no prepare step), the ray query's box phase on "
+           "boxes grown by the lane's radius plus a 2^-18 pad, at the leaf the overlap predicate at tmin (the range query's "
+           "d2), else the facing offset face and the near roots of the three edge capsules against one shrinking tmax, radius "
+           "0 lanes run the ray query's tests, closest / any hit, direct or indexed, a feature word per ray | "
            "instance_mixed: the instanced ray query over triangle and sphere BLASes in one TLAS, a 16-byte geometry record per "
            "BLAS read on entry (kind, sphere array, count kept per lane), the leaf phase tests a triangle pair or a sphere by "
            "the lane's kind on the object-space ray, one tmax across both, the record shape by the hit instance's kind | "

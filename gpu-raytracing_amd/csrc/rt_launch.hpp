@@ -249,6 +249,12 @@ hipError_t launch_capsule_query(const rt_accel& as, const rt_capsule* capsules, 
                                 uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, bool any_hit,
                                 uint64_t* counters, hipStream_t st);
 
+// sphere_cast_query.hip: rt_sphere_cast after its argument checks (a launch of at least one lane; order == null: lane j takes
+// ray j; radii == null: every ray takes `radius`; features may be null)
+hipError_t launch_sphere_cast(const rt_accel& as, const rt_ray* rays, const float* radii, float radius, uint32_t num_rays,
+                              const uint32_t* order, uint32_t num_indices, rt_hit* hits, uint32_t* features, bool any_hit,
+                              uint64_t* counters, hipStream_t st);
+
 // ray_sort.hip: rt_sort_rays after its argument checks (num_rays > 0)
 struct RaySortLayout {
     size_t box;         // float lo[4], hi[4] at the start of the 256-byte header

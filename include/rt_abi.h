@@ -650,6 +650,88 @@ int rt_intersect_rays_capsules(const rt_accel* as, const rt_capsule* capsules, u
                                uint32_t num_rays, const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode,
                                uint64_t* counters, void* stream);
 
+/* ---- sphere cast (no reference counterpart).  How far can a BALL of radius rad travel along a ray before it touches the mesh,
+ * and where does it touch: the sweep of collision and motion-planning callers (character controllers, camera booms, continuous
+ * collision of sphere-swept links).  A query over the triangle trees rt_intersect_rays takes -- LBVH, pairs, hybrid, SAH, SAH
+ * with pairs and / or splits, refitted trees, runs of 1 to 7 slots, the empty tree.  No builder, no prepare step.  A ball
+ * swept against a triangle is a ray against the triangle's Minkowski sum with the ball: two offset faces, three edge capsules
+ * whose end spheres are the corners.  Every convention not restated here is rt_intersect_rays_spheres's (sphere block).
+ *
+ * rays: rt_intersect_rays's; t is in units of |dir|.  radii[i] is the world-space radius of the ball whose centre travels
+ * along rays[i]; radii == NULL gives every ray `radius`.  A ray is NOT TRACED (the miss record, RT_SWEEP_NONE, no test
+ * counted) when the ray query would not trace it or its radius is negative, NaN or +inf.  order, num_indices and mode are
+ * rt_intersect_rays_spheres's; radii, hits and features are indexed by ray index.
+ *
+ * Box phase: the tracer's -- slab test, ordered compares, nearest child first with the index tie rule, one 64-entry stack,
+ * pushes beyond 64 dropped -- on GROWN boxes: every slot's box is [fl(lo - e), fl(hi + e)] per axis, e made once per ray:
+ *       rad == 0: the boxes as stored (growth exactly 0)
+ *       else      M   = the largest |lo| or |hi| over the three axes of the slots of the root run (as->root, as->count) whose
+ *                       type is not "none"
+ *                 pad = fl(2^-18 * max(rad, M));   e = fl(rad + pad)
+ *   The contact point lies on the triangle, hence in the leaf's box (in a split tree: in some reference's clipped box), so the
+ *   centre at contact lies in that box grown by rad.  pad plays the sphere block's role: the slab test carries about 1.5 ulp
+ *   of relative error in (bound - o) * inv, and a grown bound is no larger than M + rad in magnitude, so for an origin within
+ *   a few such magnitudes 2^-18 * max(rad, M) covers it with margin.
+ *
+ * At a leaf: one test is counted per leaf visited, as in the ray query.  Triangle A = (v0, v1, v2) is tested, then triangle
+ * B = (v2, v1, v3) unless v3 == v2 bit for bit (the ray query's skip); any-hit tests B after a hit on A as well, as the ray
+ * query does.  A pair's shared edge v1-v2 is tested TWICE, once as A's and once as B's.
+ * Per triangle with STORED corners s0, s1, s2, primitive id and rotation, in float32, every operation rounded on its own, IEEE
+ * division, correctly rounded square root, every dot product x.y summed as (x0*y0 + x1*y1) + x2*y2:
+ *   rad == 0: rt_intersect_rays's triangle test alone (Moller-Trumbore on the stored corners, epsilon 1e-9, t in [tmin, tmax]).
+ *     The records, counters[0] and counters[1] of such rays are rt_intersect_rays's, byte for byte.  Feature: RT_SWEEP_FACE.
+ *   rad > 0:
+ *   1. Initial overlap.
+ *       c0 = o + tmin*d                              (per axis fl(ox + fl(tmin*dx)))
+ *       D  = d2(c0, a, b, c) of the closest-point block, (a, b, c) the CALLER's corners (the stored ones un-rotated, as the
+ *            range query takes them), with its weights (u, v) of b and c
+ *       D <= fl(rad*rad): accepted with t = tmin, the record's (u, v) = those weights (+ 0: a -0 is written as +0, as
+ *       rt_closest_points writes them), RT_SWEEP_OVERLAP.  This is
+ *       rt_range_count's predicate in sphere shape on (c0, fl(rad*rad)), bit for bit.  Nothing else of the triangle is tested.
+ *   2. Otherwise the ball starts outside the convex sum and the candidates below are tried IN THIS ORDER, each against the
+ *      current tmax: a candidate t is accepted when tmin <= t <= tmax and becomes tmax, so of equal candidates the later wins.
+ *      Only entry roots are candidates; no far root is ever taken.
+ *     a. The facing offset face.
+ *       e1 = s1 - s0;  e2 = s2 - s0;  n = e1 x e2    (nx = fl(fl(e1y*e2z) - fl(e1z*e2y)), cyclic)
+ *       len = sqrt(n.n);   !(len > 0): no face candidate (zero area, a NaN)
+ *       dn = d.n;   k = -rad when dn < 0, else rad
+ *       o' = o + k*(n/len)                           (per axis fl(ox + fl(k * fl(nx/len))): the origin shifted TOWARD the triangle
+ *                                                     by rad, so the shifted ray meets the triangle where the centre's ray meets
+ *                                                     the offset face that looks at it)
+ *       rt_intersect_rays's triangle test on (o', d, tmin, tmax) and the stored corners: its t, and its (bu, bv) as the weights of
+ *       s1 and s2.  RT_SWEEP_FACE.
+ *     b. The edges (s0, s1), (s1, s2), (s2, s0).  For an edge (pa, pb): the ENTRY of the capsule block's test of (p0 = pa,
+ *        p1 = pb, r = rad), that block's steps and names:
+ *       n == 0 exactly (a degenerate edge): the sphere block's steps about c = pa: t = t_near when disc >= 0, axial v = 0.
+ *       else m, f, a, b, s, q, nn, nd, nq, qd, qq, A, C, hn as there, and
+ *         A > 0:   B, h as there; !(h >= 0): none.  tau1, y1 as there; entry = tau1 with v = fl(fl(y1/nn) + 0.5) when
+ *                  -hn < y1 < hn, else the NEAR root of pa's end sphere (y1 <= -hn; v = 0) or pb's (v = 1); not ok: none
+ *         else:    C > 0: none.  entry = the near root of pa's end sphere (v = 0) when nd > 0, else of pb's (v = 1); not ok: none
+ *         t = fl(s + entry)
+ *       The block's exit (tau2, the far roots) is not evaluated.  Weights of (s1, s2) at axial v: (v, 0) on (s0, s1);
+ *       (fl(1 - v), v) on (s1, s2); (0, fl(1 - v)) on (s2, s0).  RT_SWEEP_EDGE when 0 < v < 1, else RT_SWEEP_CORNER (v is exactly
+ *       0 or 1 there: the capsule block's guarantee).
+ *   3. An accepted t becomes the ray's tmax for every later part, triangle and box; RT_RAY_ANY_HIT ends the ray after the leaf
+ *      of its first accepted triangle.
+ * hits[i]: t = the centre's parameter at first contact; primitive_id = the caller's triangle; (u, v) = the weights of the
+ * CONTACT POINT ON THE TRIANGLE for the caller's corners v1 and v2 -- for an overlap as step 1 gives them, else the stored
+ * corners' (bu, bv) mapped through the leaf's rotations exactly as rt_intersect_rays maps its own.  The contact normal is
+ * (o + t*d - contact) / rad.  A miss is rt_intersect_rays's miss record.
+ * features (optional, 4-byte aligned device uint32 per ray): which part was touched, RT_SWEEP_NONE on a miss.
+ * Counters (optional, added to): [0] box tests, [1] leaves visited, [2] / [3] wave steps.
+ * The call is asynchronous (no host copy, no synchronisation: hipGraph-capturable).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT), also when num_rays == 0: a null as; as->count > 7 (or
+ * a null tree pointer with count > 0); a bad mode; rays / hits not 16-byte aligned; order / radii / features not 4-byte aligned;
+ * radii == NULL with a radius that is negative, NaN or infinite; null rays / hits with num_rays > 0.  num_rays == 0, or an
+ * order list with num_indices == 0, runs nothing.
+ *
+ * Out of scope: swept capsules or boxes; instanced, motion, filtered, all-hit and first-K forms; sweeps over sphere or capsule
+ * trees; the C++ host mirror and rt_cli. */
+enum { RT_SWEEP_NONE = 0, RT_SWEEP_FACE = 1, RT_SWEEP_EDGE = 2, RT_SWEEP_CORNER = 3, RT_SWEEP_OVERLAP = 4 };
+int rt_sphere_cast(const rt_accel* as, const rt_ray* rays, const float* radii, float radius, uint32_t num_rays,
+                   const uint32_t* order, uint32_t num_indices, rt_hit* hits, uint32_t* features, int mode,
+                   uint64_t* counters, void* stream);
+
 /* ---- mixed instancing (no reference counterpart).  The instanced ray query over a BLAS table whose trees hold triangles OR
  * spheres: a surface mesh with atoms, particles inside geometry, sphere-swept obstacles in a robot cell -- one TLAS, one walk,
  * one tmax across both kinds, an any-hit ray that stops at the first primitive of either.  Nothing new is prepared or built:
