@@ -107,7 +107,8 @@ __device__ __forceinline__ bool intersect_tri(float v0x, float v0y, float v0z, f
 // a lane that has just popped entry E from level s of its stack takes no box step while a quad-mate still holds E at level s
 // of its own stack -- the mate is deeper in the subtree both took first, and when it pops E the two step on E with one
 // address, which the address path charges as one request (quad_hold below).  The rule is evaluated once per
-// vote: the second box step under the vote steps every lane in PH_STEP.  (Which kernels take it at 1 and 2: trace_kernel.hip.)
+// vote: the second box step under the vote steps every lane in PH_STEP.  (Which kernels take it at 1 and 2: trace_kernel.hip.
+// Shipped since: quad_hold_sp, the same rule on the stack depths alone, before BOTH steps -- RT_TRACE_HOLD_FIRST / _SECOND below.)
 #ifndef RT_TRACE_QUAD_WAIT
 #define RT_TRACE_QUAD_WAIT 1
 #endif
@@ -440,22 +441,79 @@ __device__ __forceinline__ bool quad_hold(const Trav& t)
     return hold;
 }
 
+// Hold by stack depth alone (RT_TRACE_HOLD_SECOND / RT_TRACE_HOLD_FIRST), evaluated by the WHOLE wave like quad_hold and for
+// the same reason: never under a lane-divergent branch.  True for a lane that sits on a freshly popped entry (PH_STEP_POP,
+// popped from level sp < kStackLds) while a quad-mate that is still traversing has mate.sp > sp.  No stack entry is compared
+// and nothing is read from LDS: the key is quad_hold's, broadcast afresh (four quad-perm DPP moves), then four compares,
+// three ORs and one AND.  A lane never holds for itself: its own key is its own sp (or 0).  A mate with greater sp is deeper
+// in a subtree this lane has left; most often it is the subtree both took first, and the entry this lane popped is the one
+// the mate will pop at the same level -- the case quad_hold tests for exactly.  Holding for the others as well costs wave
+// steps and merges no fewer requests (tools/quad_wait_model.py --second sp, profiles/hold_second_model.txt).
+//
+// Progress.  A lane holds only for an unfinished mate with strictly greater sp, so the unfinished lane of a quad with the
+// greatest sp never holds.  HOLD_FIRST = 0: the first step of every vote is quad_hold's, and its argument that every pass of
+// the loop steps a lane or runs a leaf phase stands word for word; the second step may step nobody, which costs one empty step
+// and harms nothing.  HOLD_FIRST = 1: the same by the greatest-sp argument -- that lane is in `stepping` or parked.  A held
+// lane's mate reaches sp <= s or finishes after finitely many of its own tests (pops are LIFO also on a full stack, where
+// only pushes are dropped), and either ends the hold.  The lean margin is untouched: a lane that sits out pushes nothing.
+// The exact vote's "sits out" rule composes with this one: the second step's mask is PH_STEP && exact_cur(cur) && !hold, and
+// a lane that sits out for either reason keeps its phase (PH_STEP_POP stays PH_STEP_POP), as a lane held before the first
+// step does.  Each ray's sequence of tests, pushes and pops is unchanged; only the interleaving across lanes changes.
+//   RT_TRACE_HOLD_SECOND  1 (shipped): the second step's mask excludes the lanes for which quad_hold_sp is true; 0: it steps
+//                         every lane in PH_STEP.
+//   RT_TRACE_HOLD_FIRST   1 (shipped): the first step's `go` is quad_hold_sp's -- no ds_read_b128, no branch and no wait in front
+//                         of the vote; 0: quad_hold's.
+// Both at 0 is the loop before these knobs, instruction for instruction.  Measured (DESIGN section 5,
+// profiles/hold_second_bench.txt, hold_second_pmc.txt, hold_second_asm.txt): both on, L1 lookups -43 %, TA busy -12 %, +8 % wave
+// steps; +4.1 % on the headline in flight, +1.8 % one frame at a time.  Either knob alone loses somewhere: SECOND alone pays
+// quad_hold's LDS read and the new test (no gain one frame at a time, -1.3 % on a pairs tree), FIRST alone holds more lanes
+// for nothing (-2.9 %).
+#ifndef RT_TRACE_HOLD_SECOND
+#define RT_TRACE_HOLD_SECOND 1
+#endif
+#ifndef RT_TRACE_HOLD_FIRST
+#define RT_TRACE_HOLD_FIRST 1
+#endif
+constexpr int kHoldSecond = RT_TRACE_HOLD_SECOND, kHoldFirst = RT_TRACE_HOLD_FIRST;
+static_assert((kHoldSecond == 0 || kHoldSecond == 1) && (kHoldFirst == 0 || kHoldFirst == 1), "RT_TRACE_HOLD_SECOND / RT_TRACE_HOLD_FIRST are 0 or 1");
+template <bool ANY>
+__device__ __forceinline__ bool quad_hold_sp(const Trav& t)
+{
+    const bool popped = t.phase == PH_STEP_POP && t.sp < kStackLds;
+    const int key = ANY && t.phase == PH_DONE ? 0 : t.sp;
+    const int k0 = __builtin_amdgcn_mov_dpp(key, 0x00, 0xF, 0xF, true), k1 = __builtin_amdgcn_mov_dpp(key, 0x55, 0xF, 0xF, true);
+    const int k2 = __builtin_amdgcn_mov_dpp(key, 0xAA, 0xF, 0xF, true), k3 = __builtin_amdgcn_mov_dpp(key, 0xFF, 0xF, 0xF, true);
+    return popped & ((k0 > t.sp) | (k1 > t.sp) | (k2 > t.sp) | (k3 > t.sp));
+}
+
 // The two box steps of a QW vote; `go`: this lane takes the first (in PH_STEP / PH_STEP_POP and not held); the second steps
-// every lane in PH_STEP, held ones included.  lean: the vote's arm; NARROW: both steps in the pair-local form (RT_TRACE_PAIR_STEP).
+// every lane in PH_STEP, held ones included (kHoldSecond: but for those quad_hold_sp holds).  lean: the vote's arm; NARROW: both
+// steps in the pair-local form (RT_TRACE_PAIR_STEP).
 template <bool PF, bool ANY, bool NARROW = false, class Params>
 __device__ __forceinline__ void quad_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
 {
     if (go) box_step<PF, true, NARROW ? 1 : 0>(p, r, t, lean);
-    if ((t.phase & 3u) == PH_STEP) box_step<PF, true, NARROW ? 2 : 0>(p, r, t, lean);
+    if constexpr (kHoldSecond != 0) {
+        // (bitwise on purpose: quad_hold_sp is evaluated by every lane; the cast tells the compiler so)
+        if (((t.phase & 3u) == PH_STEP) & (int)!quad_hold_sp<ANY>(t)) box_step<PF, true, NARROW ? 2 : 0>(p, r, t, lean);
+    } else {
+        if ((t.phase & 3u) == PH_STEP) box_step<PF, true, NARROW ? 2 : 0>(p, r, t, lean);
+    }
 }
 
 // The two box steps of an EXACT vote (kPairStep == 2): the first as above -- the vote has seen every unfinished lane's cur --
-// the second steps the lanes in PH_STEP whose NEW cur is exact as well; the others sit it out (progress: at exact_cur).
+// the second steps the lanes in PH_STEP whose NEW cur is exact as well (kHoldSecond: and which quad_hold_sp does not hold); the
+// others sit it out (progress: at exact_cur and at quad_hold_sp).
 template <bool PF, bool ANY, class Params>
 __device__ __forceinline__ void exact_vote_steps(const Params& p, const Ray& r, Trav& t, bool go, bool lean)
 {
     if (go) box_step<PF, true, 3>(p, r, t, lean);
-    if (((t.phase & 3u) == PH_STEP) & exact_cur(t.cur)) box_step<PF, true, 3>(p, r, t, lean);
+    if constexpr (kHoldSecond != 0) {
+        // (bitwise on purpose: quad_hold_sp is evaluated by every lane; the cast tells the compiler so)
+        if (((t.phase & 3u) == PH_STEP) & exact_cur(t.cur) & (int)!quad_hold_sp<ANY>(t)) box_step<PF, true, 3>(p, r, t, lean);
+    } else {
+        if (((t.phase & 3u) == PH_STEP) & exact_cur(t.cur)) box_step<PF, true, 3>(p, r, t, lean);
+    }
 }
 
 // The leaf phase's fetch: a leaf (64 bytes) in four 16-byte requests issued together.  The empty asm "uses" all sixteen dwords:
@@ -503,7 +561,7 @@ __device__ __forceinline__ bool trace_ray(const Params& p, Ray& r, Hit& h, Trav&
         uint64_t stepping, parked;
         while (true) {
             if constexpr (QW) {
-                const bool go = ((t.phase & 3u) == PH_STEP) & !quad_hold<ANY>(t);
+                const bool go = ((t.phase & 3u) == PH_STEP) & !(kHoldFirst != 0 ? quad_hold_sp<ANY>(t) : quad_hold<ANY>(t));
                 stepping = __builtin_amdgcn_ballot_w64(go);
                 parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
                 // the lean vote (kLeanMargin): no unfinished lane within the margin of its LDS column's end.  (A finished

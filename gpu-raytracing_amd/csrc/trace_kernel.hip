@@ -27,6 +27,16 @@
 //     second step under the vote steps every lane in PH_STEP, held ones included.  A held lane keeps its phase; a mate
 //     that pops E in the meantime steps on it with the held lane, one address, one request.  Again only the
 //     interleaving across lanes changes.  Nobody waits for ever: see the comment at quad_hold;
+//   * HOLD BY STACK DEPTH, BEFORE BOTH STEPS (quad_hold_sp, RT_TRACE_HOLD_FIRST / RT_TRACE_HOLD_SECOND = 1, rt_traverse.hpp; shipped in
+//     the place of the entry test above, which is what both knobs at 0 build): the same rule without looking at the stack --
+//     a lane that has just popped from level s < 16 sits a box step out while an unfinished quad-mate's sp is greater than s.
+//     The mate is deeper, most often in the subtree both took first.  It is sp alone, already in a register: four quad-perm
+//     DPP moves folded into a max and one compare, no ds_read_b128, no branch, no wait in front of the loads -- cheap enough
+//     to ask before the SECOND step of a vote as well, where the entry test lost.  The second step's lane
+//     mask is PH_STEP && exact_cur(cur) && !hold; a lane that sits out keeps PH_STEP_POP and pushes nothing, so the lean
+//     margin stands.  The unfinished lane of a quad with the greatest sp never holds: every pass still steps a lane or runs
+//     a leaf phase.  Measured on the headline: 43 % fewer L1 lookups, TA busy -12 %, 8 % more wave steps, +4.1 % with frames in
+//     flight and +1.8 % one frame at a time (profiles/hold_second_bench.txt, hold_second_pmc.txt);
 //   * TWO ARMS OF A VOTE (the same instantiations; kLeanMargin, rt_traverse.hpp): one more ballot per vote asks whether any
 //     unfinished lane has more than kStackLds - 4 = 12 stack entries.  If none has, the vote is LEAN: every push and pop of
 //     its two box steps, and of the leaf phase if the vote ends the box phase, is one ds_write / ds_read on the LDS column

@@ -16,12 +16,14 @@ tmp=$(mktemp -d)
 trap 'git -C "$here" worktree remove --force "$tmp/other" 2>/dev/null; rm -rf "$tmp"' EXIT
 git -C "$here" worktree add --quiet --detach "$tmp/other" "$rev" || exit 2
 
-ARMS="-DRT_TRACE_PAIR_STEP=0 -DRT_TRACE_PAIR_STEP=1 -DRT_TRACE_LEAN_STEP=0 -DRT_TRACE_QUAD_WAIT=0 -DRT_TRACE_QUAD_WAIT=2 -DRT_TRACE_TUNING"
+# (an arm of several defines is written with + between them; a define the other side does not know changes nothing there, so
+# "both hold knobs off" is compared with <rev>'s own default where <rev> is older than the knobs)
+ARMS="-DRT_TRACE_PAIR_STEP=0 -DRT_TRACE_PAIR_STEP=1 -DRT_TRACE_LEAN_STEP=0 -DRT_TRACE_QUAD_WAIT=0 -DRT_TRACE_QUAD_WAIT=2 -DRT_TRACE_TUNING -DRT_TRACE_HOLD_SECOND=0+-DRT_TRACE_HOLD_FIRST=0"
 srcs=$(make -s --no-print-directory -C "$here/$csrc" --eval='_p: ; @echo $(SRCS)' _p)
 cases=()
 for f in $srcs; do cases+=("default||$f"); done
 for f in trace_kernel.hip ray_query.hip; do
-    for a in $ARMS; do cases+=("$a|$a|$f"); done
+    for a in $ARMS; do cases+=("$a|${a//+/ }|$f"); done
 done
 
 # emit <tree> <outdir>: the filtered device assembly of every case, JOBS compilations at a time

@@ -24,6 +24,11 @@ beside it).  pair=3 is the EXACT vote (RT_TRACE_PAIR_STEP = 2, exact_cur): no un
 lane sits on a pair below index 2^27 - 1; both steps run as Ray.pair_step without a tail, and a lane whose cur is not exact
 after the first step sits the second out.
 
+--first entry|sp / --second none|entry|sp (run_wave(first=, second=)) choose the rule in front of each of a vote's two steps:
+"entry" is quad_hold, "sp" is quad_hold_sp (RT_TRACE_HOLD_FIRST / RT_TRACE_HOLD_SECOND, csrc/rt_traverse.hpp) -- a freshly popped
+lane sits out while an unfinished mate's stack is deeper than the popped level, no entry compared.  Given either, one line is
+printed for that combination (profiles/hold_second_model.txt); without them the three lines of quad_wait_model.txt.
+
 The arithmetic is float64 on the float32 inputs: a model of the schedule, not a second oracle.
 
   python3 tools/quad_wait_model.py --grid 708 --camera a --tree lbvh --samples 40
@@ -300,6 +305,17 @@ def holds(rays, k):
     return any(m.phase != DONE and m.sp > r.sp and m.stack[r.sp] == r.cur for m in rays if m is not r)
 
 
+def holds_sp(rays, k):
+    """quad_hold_sp for lane k of the quad `rays`: the stack depths alone, no entry is compared"""
+    r = rays[k]
+    if not (r.phase == STEP and r.popped and r.sp < STACK_LDS):
+        return False
+    return any(m.phase != DONE and m.sp > r.sp for m in rays if m is not r)
+
+
+HOLD_RULES = {"entry": holds, "sp": holds_sp}
+
+
 def run_quad(rays, hold):
     """Rounds of one quad without parking.  Returns dict(rounds, lane_steps, requests, longest); raises if a round of an
     unfinished quad steps no lane."""
@@ -321,7 +337,7 @@ def run_quad(rays, hold):
                 longest=max(sum(1 for v in r.visits if v[0] == "b") for r in rays))
 
 
-def run_wave(rays, hold, second=False, pair=0):
+def run_wave(rays, hold, second=False, pair=0, first="entry"):
     """The kernel's loop (trace_ray) over the 64 lanes of a tile, lanes 4q .. 4q+3 = quad q.  Returns dict(nbox, nleaf,
     box_instr, lane_steps, requests): nbox / nleaf are the wave's counters 2 / 3, box_instr the box steps that ran with at
     least one lane, req_* the lane requests (quad_requests) summed over those steps.  second: the second box step under a
@@ -333,14 +349,31 @@ def run_wave(rays, hold, second=False, pair=0):
     (of those, wide_carried on the first pair of a node of more than two slots).  pair = 3: the exact vote (RT_TRACE_PAIR_STEP = 2);
     exact counts its votes, sat_out the lanes in PH_STEP that sat out a second step because their new cur was not exact, by what
     it was: sat_wide (more than two slots), sat_lone (a lone slot), sat_far (a pair from index 2^27 - 1 up).  Raises if a pass of
-    the loop neither steps a lane nor runs a leaf phase."""
+    the loop neither steps a lane nor runs a leaf phase.
+    first / second name the rule in front of each step of a vote (RT_TRACE_HOLD_FIRST / RT_TRACE_HOLD_SECOND): first "entry"
+    (quad_hold: the mate holds the popped entry at that level) or "sp" (quad_hold_sp: the mate's stack is deeper, nothing is
+    compared); second "none" (= False: every lane in PH_STEP steps), "entry" (= True, the retired arm) or "sp" (the
+    RT_TRACE_HOLD_SECOND = 1 arm).  held2 counts the lanes in PH_STEP that the second rule kept out of a second step, empty2 the
+    second steps that were left with no lane."""
+    second = {False: "none", True: "entry"}.get(second, second)
+    assert first in HOLD_RULES and second in ("none", "entry", "sp")
     quads = [rays[q:q + 4] for q in range(0, len(rays), 4)]
     nbox = nleaf = box_instr = lane_steps = 0
     requests = [0, 0, 0]
-    forms = dict(narrow=0, general=0, tails=0, carried=0, wide_carried=0, exact=0, sat_out=0, sat_wide=0, sat_lone=0, sat_far=0)
+    forms = dict(narrow=0, general=0, tails=0, carried=0, wide_carried=0, exact=0, sat_out=0, sat_wide=0, sat_lone=0, sat_far=0,
+                 held2=0, empty2=0)
 
-    def going():
-        return [r for qd in quads for k, r in enumerate(qd) if r.phase == STEP and not (hold and holds(qd, k))]
+    def going(rule=first):
+        return [r for qd in quads for k, r in enumerate(qd) if r.phase == STEP and not (hold and HOLD_RULES[rule](qd, k))]
+
+    def going2():
+        """the lanes of a vote's second step, before the exact vote's own mask"""
+        every = [r for r in rays if r.phase == STEP]
+        if second == "none" or not hold:
+            return every
+        nxt = going(second)
+        forms["held2"] += len(every) - len(nxt)
+        return nxt
 
     def step(go, narrow=False, tail=False, exact=False):
         nonlocal box_instr, lane_steps
@@ -373,23 +406,29 @@ def run_wave(rays, hold, second=False, pair=0):
                 if any(r.phase != DONE and (not exact_cur(r.cur) or r.near_e != NO_NEAR) for r in rays):
                     forms["general"] += 1
                     step(go)
-                    step(going() if second else [r for r in rays if r.phase == STEP])
+                    nxt = going2()
+                    forms["empty2"] += not nxt
+                    step(nxt)
                 else:
                     forms["exact"] += 1
                     step(go, True, False, True)        # (never empty: the vote is taken with a lane that steps)
-                    nxt = going() if second else [r for r in rays if r.phase == STEP]
+                    nxt = going2()
                     for r in nxt:
                         if not exact_cur(r.cur):
                             cnt = r.cur >> 29
                             forms["sat_out"] += 1
                             forms["sat_wide" if cnt > 2 else "sat_lone" if cnt < 2 else "sat_far"] += 1
-                    step([r for r in nxt if exact_cur(r.cur)], True, False, True)
+                    nxt = [r for r in nxt if exact_cur(r.cur)]
+                    forms["empty2"] += not nxt
+                    step(nxt, True, False, True)
                 continue
             counts = [r for r in rays if (r.phase != DONE if pair == 1 else r.phase == STEP)]
             narrow = pair != 0 and not any((r.cur >> 29) > 2 or r.near_e != NO_NEAR for r in counts)
             forms["narrow" if narrow else "general"] += 1
             step(go, narrow, False)
-            step(going() if second else [r for r in rays if r.phase == STEP], narrow, True)
+            nxt = going2()
+            forms["empty2"] += not nxt
+            step(nxt, narrow, True)
         if not go and parked == 0:
             if any(r.phase != DONE for r in rays):
                 raise AssertionError("the wave ends with an unfinished lane")
@@ -436,6 +475,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--wave", action="store_true", help="the kernel's schedule over whole 8 x 8 tiles")
     ap.add_argument("--pair", type=int, choices=[0, 1, 2, 3], default=0, help="with --wave: narrow votes run the pair-local step (1: every unfinished lane counts, 2: parked lanes left out); 3: the exact vote of RT_TRACE_PAIR_STEP = 2")
+    ap.add_argument("--first", choices=["entry", "sp"], default=None, help="with --wave: the rule before a vote's first step (default: the three lines of lock-step, entry / none and entry / entry)")
+    ap.add_argument("--second", choices=["none", "entry", "sp"], default=None, help="with --wave: the rule before a vote's second step; giving --first or --second prints that one combination")
     a = ap.parse_args()
     scenes = importlib.import_module("gpu-raytracing_amd.scenes")
     from oracle import oracle_py as ora
@@ -445,14 +486,18 @@ def main():
     rng = random.Random(a.seed)
     w, h = a.width, a.height
     print(f"grid_mesh({a.grid}) {a.tree} camera {a.camera} {w}x{h}, {a.samples} random {'tiles' if a.wave else 'quads'}, seed {a.seed}")
-    for name, hold, second in (("lock-step", False, False), ("hold-at-pop", True, False)) + ((("hold, 2nd too", True, True),) if a.wave else ()):
+    arms = (("lock-step", False, False), ("hold-at-pop", True, False)) + ((("hold, 2nd too", True, True),) if a.wave else ())
+    first = a.first or "entry"
+    if a.wave and (a.first or a.second):
+        arms = ((f"{first} / {a.second or 'none'}", True, a.second or "none"),)
+    for name, hold, second in arms:
         rng.seed(a.seed)
         tot = {}
         seqs = []
         for _ in range(a.samples):
             if a.wave:
                 rays = tile_rays(tree, cam, w, h, rng.randrange((w + 7) // 8), rng.randrange((h + 7) // 8))
-                res = run_wave(rays, hold, second, a.pair)
+                res = run_wave(rays, hold, second, a.pair, first)
             else:
                 rays = quad_rays(tree, cam, w, h, rng.randrange((w + 1) // 2), rng.randrange((h + 1) // 2))
                 res = run_quad(rays, hold)
@@ -467,6 +512,8 @@ def main():
                     f"requests per box instruction any/on/full " + " / ".join(f"{tot[k] / max(tot['box_instr'], 1):.1f}" for k in ("req_any", "req_on", "req_full")))
             if a.pair == 3:
                 line += f"  exact votes {100.0 * tot['exact'] / max(tot['exact'] + tot['general'], 1):.1f} %  lanes that sat out a second step {tot['sat_out']}"
+                if a.first or a.second:
+                    line += f"  held before a second step {tot['held2']}  second steps left empty {tot['empty2']}"
             elif a.pair:
                 line += f"  narrow votes {100.0 * tot['narrow'] / max(tot['narrow'] + tot['general'], 1):.1f} %"
         else:
