@@ -88,6 +88,11 @@ RT_SWEEP_NONE, RT_SWEEP_FACE, RT_SWEEP_EDGE, RT_SWEEP_CORNER, RT_SWEEP_OVERLAP =
 GEOMETRY = np.dtype([("data", "<u8"), ("count", "<u4"), ("kind", "<u4")])                                    # 16 B
 RT_GEOM_TRIANGLES = 0
 RT_GEOM_SPHERES = 1
+# instanced deferred shading (rt_shade_frame_instanced): what a hit in BLAS b is shaded from, parallel to the BLAS table
+SHADE_GEOMETRY = np.dtype([("triangles", "<u8"), ("attributes", "<u8"), ("num_triangles", "<u4"), ("material_base", "<i4"),
+                           ("pad", "<u4", 2)])                                                                # 32 B
+assert SHADE_GEOMETRY.itemsize == 32
+RT_SHADE_RENORMALIZE = 1
 # ray sorting (rt_sort_rays): a dead ray's key; every live key is below it
 RAY_KEY_BITS, RAY_KEY_DEAD = 30, 1 << 29
 # closest-point queries (rt_closest_points)
@@ -241,7 +246,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_first_hits_filtered", "rt_intersect_rays_instanced_filtered",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
-           "rt_generate_shadow_rays", "rt_shade_frame", "rt_error_string", "rt_version_string"]
+           "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -384,6 +389,9 @@ def lib() -> ctypes.CDLL:
     L.rt_generate_shadow_rays.argtypes = [vp, vp, u32, u32, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.rt_shade_frame.restype = i32
     L.rt_shade_frame.argtypes = [ctypes.POINTER(_Scene), vp, u32, vp, vp, vp, u32, u32, u32, i32, i32, vp, vp]
+    L.rt_shade_frame_instanced.restype = i32
+    L.rt_shade_frame_instanced.argtypes = [ctypes.POINTER(_Scene), vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, u32, u32, u32, i32, i32,
+                                           u32, vp, vp]
     L.rt_error_string.restype = ctypes.c_char_p
     L.rt_error_string.argtypes = [i32]
     L.rt_version_string.restype = ctypes.c_char_p
@@ -1619,6 +1627,61 @@ def ShadeFrame(triangles_in, num_triangles: int, rays, hits, rgba8, dims, *, ren
     _check(lib().rt_shade_frame(ctypes.byref(s), _ptr(triangles_in), int(num_triangles), _ptr(rays), _ptr(hits),
                                 _ptr(shadow_hits), w, h, int(spp), kRaysTiled if tiled else kRaysRowMajor, int(render_type),
                                 _ptr(rgba8), _stream_ptr(stream)), "rt_shade_frame")
+
+
+def shade_geometry_table(entries, device="cuda"):
+    """The device table of instanced shading, parallel to accel_table's: one rt_shade_geometry per BLAS.  An entry is
+    (triangles_in, attributes, num_triangles) or (triangles_in, attributes, num_triangles, material_base) -- the device
+    buffers of the BLAS's caller triangles (36-byte records, BuildInput.triangles_in) and of its 72-byte ATTRIBUTES -- or
+    None for a BLAS that is not shaded (a sphere BLAS of the mixed query): its hits shade as misses.  The caller keeps the
+    buffers alive."""
+    tab = np.zeros(len(entries), SHADE_GEOMETRY)
+    for k, e in enumerate(entries):
+        if e is None:
+            continue
+        tris, attrs, nt = e[0], e[1], int(e[2])
+        base = int(e[3]) if len(e) > 3 else 0
+        if not tris.is_contiguous() or not attrs.is_contiguous() or _nbytes(tris) < 36 * nt or _nbytes(attrs) < 72 * nt:
+            raise ValueError(f"entry {k}: triangles / attributes must be contiguous device buffers of {nt} 36- / 72-byte records")
+        tab[k] = (_ptr(tris), _ptr(attrs), nt, base, (0, 0))
+    return to_device(tab, device)
+
+
+def ShadeFrameInstanced(geometry, num_blas: int, instances, records, num_instances: int, rays, hits, instance_ids, rgba8, dims,
+                        *, render_type: int = kDepth, spp: int = 1, tiled: bool = False, renormalize: bool = True,
+                        instance_materials=None, shadow_instance_ids=None, materials=None, num_materials: int = 0,
+                        light=(0.0, 0.0, 0.0), textures: Optional[DeviceTextures] = None, stream=None) -> None:
+    """rt_shade_frame_instanced: ShadeFrame for the records of IntersectRaysInstanced (and its filtered / motion siblings) --
+    `hits` and `instance_ids` as the query wrote them for `rays` (GenerateCameraRays, same dims, spp and layout), `instances`
+    (INSTANCE) and `records` (PrepareInstances) of the pose to shade, `geometry` (shade_geometry_table, parallel to the BLAS
+    table).  `shadow_instance_ids` (kTextureLitShadows only): the instance ids of an any-hit instanced query on
+    GenerateShadowRays(rays, hits, MISS, ...)'s rays.  renormalize: re-unit the placed normals (RT_SHADE_RENORMALIZE; off, an
+    identity instance gives ShadeFrame's bytes).  instance_materials: an optional device int32 per instance, >= 0 replaces the
+    material id of every hit in that instance.  The frame is ShadeFrame's on the flattened scene, byte for byte.
+    Asynchronous on `stream`."""
+    w, h = int(dims[0]), int(dims[1])
+    n = CameraRayCount(w, h, int(spp), tiled)
+    ni, nb = int(num_instances), int(num_blas)
+    if _nbytes(rays) < 32 * n or _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n or _nbytes(rgba8) < 4 * w * h:
+        raise ValueError(f"rays / hits / instance_ids must hold {n} records, rgba8 {4 * w * h} bytes")
+    if shadow_instance_ids is not None and _nbytes(shadow_instance_ids) < 4 * n:
+        raise ValueError(f"shadow_instance_ids must hold {n} words")
+    if ni and (_nbytes(instances) < 64 * ni or _nbytes(records) < 64 * ni or _nbytes(geometry) < 32 * nb):
+        raise ValueError(f"instances / records must hold {ni} 64-byte records, geometry {nb} 32-byte records")
+    if instance_materials is not None and (instance_materials.element_size() != 4 or _nbytes(instance_materials) < 4 * ni):
+        raise ValueError(f"instance_materials must hold {ni} int32 words")
+    for name, t in (("rays", rays), ("hits", hits), ("instance_ids", instance_ids), ("rgba8", rgba8), ("geometry", geometry),
+                    ("instances", instances), ("records", records), ("shadow_instance_ids", shadow_instance_ids),
+                    ("instance_materials", instance_materials)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous device buffer")
+    s = _Scene(0, _ptr(materials), _ptr(textures.table) if textures is not None else 0, 0,
+               (ctypes.c_float * 3)(*[float(x) for x in light]), 0, num_materials, textures.count if textures is not None else 0)
+    _check(lib().rt_shade_frame_instanced(ctypes.byref(s), _ptr(geometry), nb, _ptr(instances), _ptr(records), ni,
+                                          _ptr(instance_materials), _ptr(rays), _ptr(hits), _ptr(instance_ids),
+                                          _ptr(shadow_instance_ids), w, h, int(spp), kRaysTiled if tiled else kRaysRowMajor,
+                                          int(render_type), RT_SHADE_RENORMALIZE if renormalize else 0, _ptr(rgba8),
+                                          _stream_ptr(stream)), "rt_shade_frame_instanced")
 
 
 def version() -> str:

@@ -835,6 +835,55 @@ int rt_shade_frame(const rt_scene* scene, const rt_triangle* triangles, uint32_t
     return hip_rc(launch_shade_frame(t, static_cast<hipStream_t>(stream)));
 }
 
+int rt_shade_frame_instanced(const rt_scene* scene, const rt_shade_geometry* geometry, uint32_t num_blas,
+                             const rt_instance* instances, const rt_instance_record* records, uint32_t num_instances,
+                             const int32_t* instance_materials, const rt_ray* rays, const rt_hit* hits,
+                             const uint32_t* instance_ids, const uint32_t* shadow_instance_ids, uint32_t w, uint32_t h,
+                             uint32_t spp, int layout, int render_type, uint32_t flags, uint8_t* rgba8, void* stream)
+{
+    if (!scene || !rays || !hits || !instance_ids || !rgba8) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances > 0 && (!geometry || !instances || !records || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(geometry, 16) || misaligned(instances, 16) || misaligned(records, 16) || misaligned(rays, 16) ||
+        misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(shadow_instance_ids, 4) ||
+        misaligned(instance_materials, 4) || misaligned(rgba8, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (layout != RT_RAYS_ROW_MAJOR && layout != RT_RAYS_TILED) return RT_ERR_INVALID_ARGUMENT;
+    if (spp != 1 && spp != 4 && spp != 16) return RT_ERR_INVALID_ARGUMENT;
+    if (flags & ~(uint32_t)RT_SHADE_RENORMALIZE) return RT_ERR_INVALID_ARGUMENT;
+    switch (render_type) {
+    case RT_RENDER_DEPTH: break;
+    case RT_RENDER_BOXTESTS: case RT_RENDER_TRIANGLE_TESTS: return RT_ERR_UNSUPPORTED;   // a hit record carries no test counts
+    case RT_RENDER_MATERIAL_ID: case RT_RENDER_DIFFUSE:
+        if (!scene->materials || scene->num_materials == 0) return RT_ERR_INVALID_ARGUMENT;   // (attributes: per BLAS)
+        break;
+    case RT_RENDER_LODS: case RT_RENDER_TEXTURE: case RT_RENDER_TEXTURE_LIT: case RT_RENDER_TEXTURE_LIT_SHADOWS:
+        if (!scene->materials || scene->num_materials == 0) return RT_ERR_INVALID_ARGUMENT;
+        if (scene->num_textures && !scene->textures) return RT_ERR_INVALID_ARGUMENT;
+        if (render_type == RT_RENDER_TEXTURE_LIT_SHADOWS && !shadow_instance_ids) return RT_ERR_INVALID_ARGUMENT;
+        break;
+    default: return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (w == 0 || h == 0) return RT_OK;
+    ShadeInstancedLaunch t;
+    t.scene = *scene;
+    t.geometry = geometry;
+    t.num_blas = num_blas;
+    t.instances = instances;
+    t.records = records;
+    t.num_instances = num_instances;
+    t.instance_materials = instance_materials;
+    t.rays = rays;
+    t.hits = hits;
+    t.instance_ids = instance_ids;
+    t.shadow_instance_ids = shadow_instance_ids;
+    t.w = w; t.h = h; t.spp = spp;
+    t.tiled = layout == RT_RAYS_TILED;
+    t.render_type = render_type;
+    t.flags = flags;
+    t.rgba8 = rgba8;
+    return hip_rc(launch_shade_frame_instanced(t, static_cast<hipStream_t>(stream)));
+}
+
 const char* rt_error_string(int code)
 {
     switch (code) {
@@ -912,7 +961,10 @@ const char* rt_version_string(void)
            "64-entry stack (16 in LDS), third vote only where the first two disagree, 8-byte records or one byte, grid points "
            "row-major or in 4x4x4 Morton bricks | "
            "shade: deferred shading from hit records, one thread per pixel, no stack, no LDS, no scratch, per-render-type "
-           "instantiations, shadow rays as a ray batch for the any-hit query";
+           "instantiations, shadow rays as a ray batch for the any-hit query | "
+           "instance_shade: deferred shading from instanced hit records, the shade kernel's frame with a gather per sample "
+           "(record tail, 32-byte geometry entry, object_to_world rows where corners are read, world_to_object rows where "
+           "normals are read), corners and normals placed in float32 per lane, the same shaders: the flattened scene's frame";
 }
 
 }  // extern "C"

@@ -299,6 +299,27 @@ struct ShadeLaunch {
     uint8_t* rgba8;
 };
 hipError_t launch_shade_frame(const ShadeLaunch& t, hipStream_t st);
+// shade_instanced.hip: rt_shade_frame_instanced after its argument checks (w * h > 0; num_instances > 0: geometry, instances
+// and records non-null)
+struct ShadeInstancedLaunch {
+    rt_scene scene;                       // materials, textures, light and their counts (attributes come from `geometry`)
+    const rt_shade_geometry* geometry;    // parallel to the BLAS table
+    uint32_t num_blas;
+    const rt_instance* instances;
+    const rt_instance_record* records;
+    uint32_t num_instances;
+    const int32_t* instance_materials;    // optional
+    const rt_ray* rays;
+    const rt_hit* hits;
+    const uint32_t* instance_ids;
+    const uint32_t* shadow_instance_ids;  // RT_RENDER_TEXTURE_LIT_SHADOWS only
+    uint32_t w, h, spp;
+    bool tiled;
+    int render_type;
+    uint32_t flags;                       // RT_SHADE_*
+    uint8_t* rgba8;
+};
+hipError_t launch_shade_frame_instanced(const ShadeInstancedLaunch& t, hipStream_t st);
 
 // instances.hip: rt_prepare_instances / rt_intersect_rays_instanced[_filtered] after their argument checks (the query:
 // num_rays > 0)

@@ -1553,6 +1553,70 @@ int rt_shade_frame(const rt_scene* scene, const rt_triangle* triangles, uint32_t
                    const rt_hit* hits, const rt_hit* shadow_hits, uint32_t w, uint32_t h, uint32_t spp, int layout,
                    int render_type, uint8_t* rgba8, void* stream);
 
+/* ---- instanced deferred shading (no reference counterpart).  rt_shade_frame for the records of the INSTANCED ray queries: an
+ * instanced record's primitive_id indexes a BLAS's own triangles in object space, so rt_shade_frame's one flat triangles[] /
+ * attributes[] cannot serve it without flattening every instance on the host.  The chain:
+ *   rt_generate_camera_rays -> rt_intersect_rays_instanced -> rt_generate_shadow_rays(num_triangles = RT_MISS) ->
+ *   rt_intersect_rays_instanced(any hit) -> rt_shade_frame_instanced       (the middle pair for RT_RENDER_TEXTURE_LIT_SHADOWS only)
+ * rt_generate_shadow_rays needs only the world ray and the world-space t, which the instanced query preserves: with
+ * num_triangles = RT_MISS every record but a miss is a hit, which is right for instanced records.  The any-hit instanced query
+ * gives the occlusion bit as an instance id.  The records of rt_intersect_rays_instanced_filtered and of
+ * rt_intersect_rays_instanced_motion work unchanged; for instance motion the caller passes the rt_instance array and the
+ * rt_prepare_instances records of the pose they want shaded.
+ *
+ * rt_shade_geometry (32 bytes; a DEVICE array parallel to the BLAS table, 16-byte aligned): what a hit in blas_table[b] is
+ * shaded from -- the BLAS's CALLER triangles (object space, the build input, not its tree), one rt_attributes per triangle,
+ * their count, and material_base, added to attributes[].material_id (several meshes, one concatenated material table).
+ *
+ * Sample i is a HIT iff, with k = instance_ids[i]: k < num_instances, records[k].flags == 0, b = records[k].blas < num_blas,
+ * geometry[b].triangles and geometry[b].attributes are non-null, and p = hits[i].primitive_id < geometry[b].num_triangles.
+ * Anything else (RT_MISS, garbage, the record of a dead ray) shades as rt_shade_frame's miss, whatever the other fields hold;
+ * nothing is read through an index that failed its check.
+ * A hit, with M = instances[k].object_to_world and W = records[k].world_to_object (float32, every operation rounded on its own):
+ *   corner c of geometry[b].triangles[p]:  row r = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3]   (rt_prepare_instances's order)
+ *   normal of corner c:                    n'_r = (W[0][r]*nx + W[1][r]*ny) + W[2][r]*nz             (the transpose of W's 3x3:
+ *                                          the inverse-transpose of M, the normal matrix)
+ *   flags & RT_SHADE_RENORMALIZE:          l2 = (n'x*n'x + n'y*n'y) + n'z*n'z; if l2 > 0 and finite, n'' = n' * (1.0f / sqrtf(l2));
+ *                                          otherwise, and without the flag, n' is used as it is.  The lit shaders do not normalise
+ *                                          the interpolated normal, so a scaled instance is lit wrongly without the flag; it is a
+ *                                          flag because an identity instance must give rt_shade_frame's bytes
+ *   uv:                                    unchanged
+ *   material id:                           attributes[p].material_id + geometry[b].material_base (int32, wrapping); if
+ *                                          instance_materials is non-null and instance_materials[k] >= 0, instance_materials[k];
+ *                                          then rt_shade_frame's range checks (outside the table: material 0)
+ *   then exactly rt_shade_frame's per-sample path: the ray rays[i] with tmax = hits[i].t, barycentrics (u, v), rotation 0,
+ *   spread = 2.0f / w, the same render types (RT_RENDER_BOXTESTS / RT_RENDER_TRIANGLE_TESTS: RT_ERR_UNSUPPORTED), the same
+ *   spp {1, 4, 16} accumulation, row-major / 8x8-tiled sample indexing and float -> u8 store.
+ *   RT_RENDER_TEXTURE_LIT_SHADOWS: shadowed iff shadow_instance_ids[i] < num_instances.
+ *   A MIRRORED instance (negative determinant) keeps its corner order, so the tangent frame's geometric normal (the cross
+ *   product of the placed edges) flips against the placed shading normals -- as it does in the flattened scene.
+ * Contract: the frame EQUALS rt_shade_frame's on the flattened scene -- the placed corners, the placed normals and the resolved
+ * material ids as one triangle and one attribute array, hit records whose primitive_id is the flattened index -- byte for byte,
+ * in every supported mode, layout and spp.  One identity instance without RT_SHADE_RENORMALIZE equals rt_shade_frame on the
+ * BLAS's own arrays byte for byte, for data without -0 components (-0 + 0 = +0).
+ * Out of scope: sphere BLASes of the mixed query (their table entry, with null pointers, shades as a miss); interpolated-pose
+ * shading for instance motion; the host mirror; rt_cli.
+ * Asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable).  w*h = 0: nothing runs.  num_instances = 0
+ * with null geometry / instances / records is legal: every pixel is a miss.  Argument errors, returned before any GPU work
+ * (RT_ERR_INVALID_ARGUMENT): null pointers (scene, rays, hits, instance_ids, rgba8; geometry, instances, records when
+ * num_instances > 0; materials / textures where rt_shade_frame requires them -- scene->attributes is NOT read), geometry,
+ * instances, records, rays or hits not 16-byte aligned, instance_ids, shadow_instance_ids, instance_materials or rgba8 not
+ * 4-byte aligned, a bad spp, layout or render_type, unknown flag bits, RT_RENDER_TEXTURE_LIT_SHADOWS with a null
+ * shadow_instance_ids, num_instances > 0 with num_blas = 0. */
+typedef struct rt_shade_geometry {      /* 32 bytes; DEVICE array parallel to the BLAS table */
+    const rt_triangle*   triangles;     /* the BLAS's caller triangles (object space), not its tree */
+    const rt_attributes* attributes;    /* one per triangle */
+    uint32_t num_triangles;
+    int32_t  material_base;             /* added to attributes[].material_id (one concatenated material table) */
+    uint32_t pad[2];
+} rt_shade_geometry;
+enum { RT_SHADE_RENORMALIZE = 1 };
+int rt_shade_frame_instanced(const rt_scene* scene, const rt_shade_geometry* geometry, uint32_t num_blas,
+                             const rt_instance* instances, const rt_instance_record* records, uint32_t num_instances,
+                             const int32_t* instance_materials, const rt_ray* rays, const rt_hit* hits,
+                             const uint32_t* instance_ids, const uint32_t* shadow_instance_ids, uint32_t w, uint32_t h,
+                             uint32_t spp, int layout, int render_type, uint32_t flags, uint8_t* rgba8, void* stream);
+
 /* static string for a return code */
 const char* rt_error_string(int code);
 
