@@ -14,7 +14,8 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 (``ClosestPoints``: the nearest triangle to each point, through any built tree), range queries (``RangeCount``,
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
-``RayHits``: every triangle a ray crosses inside its window, as CSR), triangle-overlap queries (``TriOverlapsCount``,
+``RayHits``: every triangle a ray crosses inside its window, as CSR; ``RayHitsCountInstanced``, ``RayHitsCollectInstanced``,
+``RayHitsInstanced``: the same over placed copies, each record with its instance), triangle-overlap queries (``TriOverlapsCount``,
 ``TriOverlapsCollect``, ``TriOverlaps``: every triangle a query triangle cuts, as CSR; ``self_pairs`` for the
 self-intersections of the mesh the tree was built over), signed distance and occupancy (``SignedDistance``, ``Occupancy``:
 how far the nearest triangle is and whether a point is inside a closed mesh, in one launch; ``GenerateGridPoints`` for the
@@ -246,7 +247,8 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_first_hits_filtered", "rt_intersect_rays_instanced_filtered",
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
-           "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced", "rt_error_string", "rt_version_string"]
+           "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced",
+           "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -372,6 +374,10 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays_instanced_filtered.restype = i32
     L.rt_intersect_rays_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, vp, vp, u32, i32, u32,
                                                        ctypes.POINTER(_InstanceHitFilter), vp, vp]
+    L.rt_ray_hits_count_instanced.restype = i32
+    L.rt_ray_hits_count_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp]
+    L.rt_ray_hits_collect_instanced.restype = i32
+    L.rt_ray_hits_collect_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -1205,6 +1211,91 @@ def RayHits(triangles, nodes, root: int, count: int, rays, *, sort: bool = False
             order = order[torch.argsort(key[order], stable=True)]
             hits = hits[order].contiguous()
     return offsets, hits
+
+
+def RayHitsCountInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                          num_blas: int, rays, offsets, *, scratch=None, counters=None, status=None, stream=None) -> int:
+    """rt_ray_hits_count_instanced: RayHitsCount through a TLAS (built over PrepareInstances's proxies without pairs or splits;
+    root / count of its root) and the instances' BLASes: offsets[0 .. N] = the exclusive prefix sum of the number of crossings of
+    each ray over all entered instances.  scratch: >= RayHitsScratchBytes(N) bytes, 256-byte aligned (taken from torch's
+    allocator when None).  counters: optional int64[4] ([0] box tests of both levels, [1] BLAS leaf records visited).  status:
+    optional device uint32 the call ORs RT_RAY_HITS_* flags into (see ray_hits_status).  N = 0: nothing runs.  Asynchronous on
+    `stream`, nothing is read back.  Returns N."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    if n == 0:
+        return 0
+    if scratch is None:
+        scratch = device_bytes(RayHitsScratchBytes(n), rays.device)
+    elif _nbytes(scratch) < RayHitsScratchBytes(n):
+        raise ValueError(f"scratch must hold RayHitsScratchBytes({n}) bytes")
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_hits_count_instanced(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table), int(num_blas),
+                                             _ptr(rays), n, _ptr(offsets), _ptr(scratch), _ptr(counters), _ptr(status),
+                                             _stream_ptr(stream)), "rt_ray_hits_count_instanced")
+    return n
+
+
+def RayHitsCollectInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                            num_blas: int, rays, offsets, hits, instance_ids, *, counts=None, counters=None, status=None,
+                            stream=None) -> int:
+    """rt_ray_hits_collect_instanced: ray i writes the HIT records of its first offsets[i+1] - offsets[i] crossings at
+    hits[offsets[i]:] and the instance of each at instance_ids[offsets[i]:] (`hits`: 16-byte records, `instance_ids`: 4-byte
+    words, both contiguous device buffers the offsets stay inside -- the caller's contract; `offsets`: int64 [N + 1] from
+    RayHitsCountInstanced, or i * K for a fixed K per ray).  A record carries the BLAS's own primitive_id and (u, v) and the
+    world-space t.  counts: optional device int32 [N], each ray's true row length.  A ray with more records than room sets
+    RT_RAY_HITS_TRUNCATED in `status`.  Order within a row: unspecified but deterministic.  Asynchronous on `stream`.
+    Returns N."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or \
+            _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, hits / instance_ids contiguous "
+                         "device buffers")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_hits_collect_instanced(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                               int(num_blas), _ptr(rays), n, _ptr(offsets), _ptr(hits), _ptr(instance_ids),
+                                               _ptr(counts), _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           "rt_ray_hits_collect_instanced")
+    return n
+
+
+def RayHitsInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table, num_blas: int,
+                     rays, *, sort: bool = False, counters=None, status=None, stream=None):
+    """Every crossing of every placed copy, as CSR: RayHitsCountInstanced, then the total offsets[N] is READ BACK TO THE HOST --
+    one synchronisation of `stream` per call, the only one, as in RayHits -- to allocate the rows, then
+    RayHitsCollectInstanced.  Returns (offsets, hits, instance_ids): torch int64 [N + 1], float32 [total, 4] (t, primitive_id
+    bits, u, v) and int32 [total] device tensors; ray i owns hits[offsets[i]:offsets[i+1]] and the same slice of instance_ids.
+    sort=True orders every row by ascending (t, instance, primitive_id) on the device (stable torch sorts: plumbing, not a
+    kernel).  With `counters`, the tests of both passes are added (twice one traversal)."""
+    torch = _torch()
+    n = _ray_batch(rays)
+    tree = (tlas_triangles, tlas_nodes, root, count, records, num_instances, blas_table, num_blas)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)    # (no fill kernel: nothing of torch's runs off `stream`)
+    RayHitsCountInstanced(*tree, rays, offsets, counters=counters, status=status, stream=stream)
+    with _on_stream(stream):
+        if n == 0:
+            offsets.zero_()                                                  # the count call runs nothing for an empty batch
+        total = int(offsets[n].item())
+        hits = torch.empty((max(total, 1), 4), dtype=torch.float32, device=rays.device)[:total]
+        ids = torch.empty(max(total, 1), dtype=torch.int32, device=rays.device)[:total]
+        RayHitsCollectInstanced(*tree, rays, offsets, hits, ids, counters=counters, status=status, stream=stream)
+        if sort and total > 1:
+            # three stable sorts: by primitive_id (unsigned), by instance (unsigned), then by the 64-bit key row << 32 | the
+            # monotone integer image of t (-0 counted as +0), which keeps every record inside its row
+            row = torch.repeat_interleave(torch.arange(n, device=rays.device), offsets[1:] - offsets[:-1], output_size=total)
+            bits = hits.view(torch.int32).to(torch.int64)
+            order = torch.argsort(bits[:, 1] & 0xFFFFFFFF, stable=True)
+            order = order[torch.argsort(ids.to(torch.int64)[order] & 0xFFFFFFFF, stable=True)]
+            tb = (hits[:, 0] + 0.0).contiguous().view(torch.int32).to(torch.int64)
+            key = (row << 32) | (torch.where(tb >= 0, tb, tb ^ 0x7FFFFFFF) + (1 << 31))
+            order = order[torch.argsort(key[order], stable=True)]
+            hits, ids = hits[order].contiguous(), ids[order].contiguous()
+    return offsets, hits, ids
 
 
 def RayFirstHits(triangles, nodes, root: int, count: int, rays, k: int, out, *, counters=None, status=None, stream=None) -> int:

@@ -703,6 +703,54 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
     return rt_ray_hits_collect_filtered(as, rays, num_rays, nullptr, offsets, hits, counts, counters, status, stream);
 }
 
+// what rt_ray_hits_count_instanced and rt_ray_hits_collect_instanced check alike: the instancing block's arguments and the CSR
+// block's; on success `q` holds what both launches read
+static bool hits_instanced_args(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                const uint64_t* offsets, uint64_t* counters, const uint32_t* status, InstanceQuery& q)
+{
+    if (!csr_args(tlas, rays, 16, true, offsets, status)) return false;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return false;
+    if (misaligned(records, 16) || misaligned(blas_table, 8)) return false;
+    q = InstanceQuery();
+    q.tlas = *tlas;
+    q.records = records;
+    q.num_instances = num_instances;
+    q.blas_table = blas_table;
+    q.num_blas = num_blas;
+    q.rays = rays;
+    q.num_rays = num_rays;
+    q.counters = counters;
+    return true;
+}
+
+int rt_ray_hits_count_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
+{
+    InstanceQuery q;
+    if (!hits_instanced_args(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, offsets, counters, status, q) ||
+        !csr_count_args(scratch))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_hits_count_instanced(q, offsets, scratch, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_hits_collect_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                  const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                  const uint64_t* offsets, rt_hit* hits, uint32_t* instance_ids, uint32_t* counts,
+                                  uint64_t* counters, uint32_t* status, void* stream)
+{
+    InstanceQuery q;
+    if (!hits_instanced_args(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, offsets, counters, status, q) ||
+        !csr_collect_args(hits, 16, counts) || !instance_ids || misaligned(instance_ids, 4))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    return hip_rc(launch_ray_hits_collect_instanced(q, offsets, counts, status, static_cast<hipStream_t>(stream)));
+}
+
 int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
                                const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, void* stream)
 {
@@ -964,7 +1012,11 @@ const char* rt_version_string(void)
            "instantiations, shadow rays as a ray batch for the any-hit query | "
            "instance_shade: deferred shading from instanced hit records, the shade kernel's frame with a gather per sample "
            "(record tail, 32-byte geometry entry, object_to_world rows where corners are read, world_to_object rows where "
-           "normals are read), corners and normals placed in float32 per lane, the same shaders: the flattened scene's frame";
+           "normals are read), corners and normals placed in float32 per lane, the same shaders: the flattened scene's frame | "
+           "ray_hits_instanced: instanced all-hit ray queries, every crossing of every placed copy with its instance, the "
+           "all-hit frame (fixed window, unordered 64-entry stack of 4-byte entries, 16 in LDS, CSR by the 64-bit device scan) "
+           "with the instanced query's second level in its loop (an entry of count 0 is an instance in the TLAS and a leaf in a "
+           "BLAS, per-lane base pointers, world ray reloaded on exit), hit records and instance ids in parallel segments";
 }
 
 }  // extern "C"

@@ -1094,6 +1094,71 @@ int rt_ray_hits_count(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
 int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, const uint64_t* offsets, rt_hit* hits,
                         uint32_t* counts, uint64_t* counters, uint32_t* status, void* stream);
 
+/* ---- instanced all-hit ray queries (no reference counterpart).  The all-hit query over a scene of placed copies of built
+ * trees: for each caller ray EVERY triangle it crosses inside its [tmin, tmax] window in every instance, each record with the
+ * instance it lies in -- layered transparency, thickness and entry / exit pairs, parity tests on placed closed meshes, CSG over
+ * placed parts, X-ray picking -- without flattening the scene.  The scene is the instancing block's (rt_prepare_instances, a
+ * TLAS over its proxies built WITHOUT pairs or splits, the records, the BLAS table of triangle trees); the result is the
+ * all-hit block's CSR with a second, parallel array: ray i owns hits[offsets[i] .. offsets[i+1]) and
+ * instance_ids[offsets[i] .. offsets[i+1]); record j of ray i is hits[offsets[i] + j] in instance instance_ids[offsets[i] + j],
+ * as rt_intersect_rays_instanced pairs hits[i] with instance_ids[i].
+ *
+ * Rays, window.  The all-hit block's liveness rule (a ray with tmin > tmax, or a NaN in origin, direction, tmin or tmax, is not
+ * traced: an empty row, no tests counted) and its fixed window: every slab test of both levels and every triangle test uses the
+ * ray's ORIGINAL tmin / tmax.  An affine map preserves t, so the window applies unchanged in object space and the t of a record
+ * needs no conversion.
+ * TLAS.  A non-NONE TLAS slot is examined with rt_trace's float32 slab test on the world ray and entered iff back >= front &&
+ * front <= tmax && back >= tmin.  A TLAS triangle slot that passes names instance primitive_id_0 of its leaf record.
+ * Entering an instance: under exactly rt_intersect_rays_instanced's conditions (the id < num_instances, the record's flags 0,
+ * its blas < num_blas, the table entry's count in 1..7), with that block's arithmetic: o' = W*(o, 1), d' = W3x3*d, each row
+ * ((w0*x + w1*y) + w2*z) [+ w3] in float32, 1/d' by IEEE division.  On leaving the instance the world ray is reloaded from
+ * rays[i]: the original bits.
+ * Inside the BLAS the walk is the all-hit block's on the object ray: its slot test, its leaf test on the stored corners,
+ * B = (v2, v1, v3) tested iff v3 != v2 bit for bit, and a record is rt_ray_hits_collect's for that object ray and tree -- t,
+ * the BLAS's own primitive_id, (u, v) mapped back through rt_triangle_pair.rotations.
+ *
+ * Result: per ray the MULTISET of (instance, record) over the entered instances; no ordering promise.  The TLAS is built
+ * without pairs or splits, so each instance sits in one TLAS leaf and is entered at most once; whether a TLAS slot, an instance
+ * or a BLAS slot is entered depends on the bytes and the ray alone (the window never moves), so the row does not depend on the
+ * visiting order, and rt_ray_hits_count_instanced and rt_ray_hits_collect_instanced -- one traversal, compiled twice -- cannot
+ * disagree.  What holds when no push was dropped:
+ *   1. composition: the row is the union, over the entered instances, of rt_ray_hits_collect's row on the instance's BLAS for
+ *      the object ray, each record tagged with the instance;
+ *   2. closest hit: some record of the row has the (instance, t, u, v) bits of rt_intersect_rays_instanced's closest-hit answer
+ *      for the same ray (every slot and instance that query entered with a smaller tmax is entered with the original one, and
+ *      the arithmetic is the same); a miss there has an empty row and the other way round;
+ *   3. an identity instance over a tree gives rt_ray_hits_collect's row on that tree, all ids 0 and the same counters[1], for
+ *      rays without -0 components (a transformed -0 may come out +0).
+ *   Split BLASes repeat a triangle once per reference reached, as in the all-hit block; two instances in the same place both
+ *   report.  It is not promised to equal a float64 brute force over the placed triangles (the all-hit block says why; here the
+ *   float32 ray transform and the padded proxy box come on top).
+ *
+ * rt_ray_hits_count_instanced: offsets[0 .. num_rays] = the exclusive prefix sum of the row lengths.  scratch:
+ *   rt_ray_hits_scratch_bytes(num_rays) bytes, 256-byte aligned, no initialisation needed.  Three launches, nothing read back.
+ * rt_ray_hits_collect_instanced: ray i writes its first min(matches, offsets[i+1] - offsets[i]) records at hits + offsets[i] and
+ *   their instances at instance_ids + offsets[i] and nothing else; counts (optional) gets the true row length; a ray with more
+ *   records than room ORs RT_RAY_HITS_TRUNCATED into *status.  offsets[i] = i * K is the one-pass fixed-K mode: exact counts,
+ *   the first min(counts[i], K) records of each segment valid.
+ * Both calls: counters, optional device uint64[4]: [0] += non-NONE slots examined, both levels together, [1] += BLAS leaf
+ * records visited; [2] / [3] are not touched.  status: optional device uint32 the calls OR RT_RAY_HITS_* flags into (never
+ * cleared).  Stack: ONE stack of 64 four-byte entries serves both levels, the BLAS's entries above the TLAS's: a BLAS entered at
+ * depth k has 64 - k entries.  A dropped push sets RT_RAY_HITS_STACK_OVERFLOW; the row is then a subset of the full row and the
+ * two calls still agree.  Asynchronous (no allocation, no host copy, no synchronisation: hipGraph-capturable).  num_rays = 0:
+ * nothing runs (offsets[0] is not written).
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null tlas / rays / offsets / scratch (count) /
+ * hits / instance_ids (collect); with num_instances > 0 a null records or blas_table, or num_blas = 0 (blas_table may be null
+ * only when num_instances = 0); a TLAS with count > 0 and a null node or leaf pointer, tlas->count > 7; rays / hits / records
+ * not 16-byte, offsets / blas_table not 8-byte, instance_ids / counts / status not 4-byte, scratch not 256-byte aligned.
+ * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, indexed and first-K forms, the host
+ * mirror and rt_cli. */
+int rt_ray_hits_count_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream);
+int rt_ray_hits_collect_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                  const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                  const uint64_t* offsets, rt_hit* hits, uint32_t* instance_ids, uint32_t* counts,
+                                  uint64_t* counters, uint32_t* status, void* stream);
+
 /* ---- first-K ray queries (no reference counterpart).  For each caller ray: the K nearest triangles it crosses inside its
  * [tmin, tmax] window, in order -- layered transparency, depth peeling, "skip the first surface" picking, thickness (entry /
  * exit pairs), CSG -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and

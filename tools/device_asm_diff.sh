@@ -6,7 +6,8 @@
 # trace_kernel.hip and ray_query.hip once more per kept off-arm of the tracer's knobs and with -DRT_TRACE_TUNING.  Comment
 # lines, .ident, .file and the __hip_cuid_* symbol (a hash of the source text) are dropped, the rest is compared with cmp.
 # The other side is built in a `git worktree` under a temporary directory, removed on exit.  Prints one line per file and
-# arm -- the line count and "identical" or "DIFFERS" -- and exits non-zero if anything differs or fails to compile.
+# arm -- the line count and "identical" or "DIFFERS" -- and exits non-zero if anything differs or fails to compile.  A file
+# of this tree's SRCS that <rev> does not have is reported as new and is no failure: there is nothing to compare it with.
 #   JOBS=n tools/device_asm_diff.sh 30690cb > profiles/retired_arms_asm_diff.txt
 set -uo pipefail
 rev=${1:?usage: device_asm_diff.sh <rev>}
@@ -45,7 +46,8 @@ bad=0
 for c in "${cases[@]}"; do
     IFS="|" read -r name def f <<< "$c"
     a=$tmp/head/$name.$f.s b=$tmp/rev/$name.$f.s
-    if [ ! -s "$a" ] || [ ! -s "$b" ]; then echo "$f $name: FAILED TO COMPILE"; cat "$tmp/head/$name.$f.err" "$tmp/rev/$name.$f.err" >&2; bad=1
+    if [ -s "$a" ] && [ ! -e "$tmp/other/$csrc/$f" ]; then echo "$f $name: $(wc -l < "$a") lines, new in this tree ($rev has no such file)"
+    elif [ ! -s "$a" ] || [ ! -s "$b" ]; then echo "$f $name: FAILED TO COMPILE"; cat "$tmp/head/$name.$f.err" "$tmp/rev/$name.$f.err" >&2; bad=1
     elif cmp -s "$a" "$b"; then echo "$f $name: $(wc -l < "$a") lines, identical"
     else echo "$f $name: $(wc -l < "$a") / $(wc -l < "$b") lines, DIFFERS ($(diff "$a" "$b" | grep -c '^[<>]') lines of diff)"; bad=1
     fi
