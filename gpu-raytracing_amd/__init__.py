@@ -15,7 +15,8 @@ vertices moved (``BuildRefitPlan`` once per build, ``Refit`` per frame), instanc
 ``RangeCollect``, ``RangeQuery``: every triangle within a radius or overlapping a box, as CSR), k-nearest queries
 (``KNearest``: the k nearest triangles to each point, in order), all-hit ray queries (``RayHitsCount``, ``RayHitsCollect``,
 ``RayHits``: every triangle a ray crosses inside its window, as CSR; ``RayHitsCountInstanced``, ``RayHitsCollectInstanced``,
-``RayHitsInstanced``: the same over placed copies, each record with its instance), triangle-overlap queries (``TriOverlapsCount``,
+``RayHitsInstanced``: the same over placed copies, each record with its instance; ``RayFirstHitsInstanced``: the k nearest
+crossings over placed copies, in order, in one launch), triangle-overlap queries (``TriOverlapsCount``,
 ``TriOverlapsCollect``, ``TriOverlaps``: every triangle a query triangle cuts, as CSR; ``self_pairs`` for the
 self-intersections of the mesh the tree was built over), signed distance and occupancy (``SignedDistance``, ``Occupancy``:
 how far the nearest triangle is and whether a point is inside a closed mesh, in one launch; ``GenerateGridPoints`` for the
@@ -248,7 +249,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced",
-           "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_error_string", "rt_version_string"]
+           "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_ray_first_hits_instanced", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -378,6 +379,8 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_count_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp]
     L.rt_ray_hits_collect_instanced.restype = i32
     L.rt_ray_hits_collect_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.rt_ray_first_hits_instanced.restype = i32
+    L.rt_ray_first_hits_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -1317,6 +1320,35 @@ def RayFirstHits(triangles, nodes, root: int, count: int, rays, k: int, out, *, 
     a = _Accel(_ptr(triangles), _ptr(nodes), root, count)
     _check(lib().rt_ray_first_hits(ctypes.byref(a), _ptr(rays), n, k, _ptr(out), _ptr(counters), _ptr(status),
                                    _stream_ptr(stream)), "rt_ray_first_hits")
+    return n
+
+
+def RayFirstHitsInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                          num_blas: int, rays, k: int, hits, instance_ids, *, counters=None, status=None, stream=None) -> int:
+    """rt_ray_first_hits_instanced: RayFirstHits through a TLAS (built over PrepareInstances's proxies without pairs or splits;
+    root / count of its root) and the instances' BLASes: for each ray a row of k HIT records in `hits` (float32 [N, k, 4] on the
+    device) and the instance of each in `instance_ids` (int32 [N, k]): the k nearest crossings over all placed copies in
+    ascending (t, instance, primitive_id) order, padded with {+inf, MISS, 0, 0} / MISS.  A record carries the BLAS's own
+    primitive_id and (u, v) and the world-space t.  1 <= k <= RT_RAY_FIRST_MAX_K.  One launch: the window shrinks to the k-th
+    hit on both levels while the ray is traced.  Exactness: include/rt_abi.h, instanced first-K block (decided / undecided
+    rays).  counters: optional int64[4] ([0] box tests of both levels, [1] BLAS leaf records visited).  status: optional device
+    uint32 the call ORs RT_RAY_FIRST_STACK_OVERFLOW into (the caller clears it; see ray_first_status).  Asynchronous on
+    `stream`, nothing is allocated or read back.  Returns N."""
+    torch = _torch()
+    k = int(k)
+    if not 1 <= k <= RT_RAY_FIRST_MAX_K:
+        raise ValueError(f"k must be in 1 .. {RT_RAY_FIRST_MAX_K}")
+    n = _ray_batch(rays)
+    if not hits.is_contiguous() or hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 4):
+        raise ValueError(f"hits must be a contiguous float32 tensor of shape [{n}, {k}, 4]")
+    if not instance_ids.is_contiguous() or instance_ids.dtype != torch.int32 or tuple(instance_ids.shape) != (n, k):
+        raise ValueError(f"instance_ids must be a contiguous int32 tensor of shape [{n}, {k}]")
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_first_hits_instanced(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table), int(num_blas),
+                                             _ptr(rays), n, k, _ptr(hits), _ptr(instance_ids), _ptr(counters), _ptr(status),
+                                             _stream_ptr(stream)), "rt_ray_first_hits_instanced")
     return n
 
 

@@ -768,6 +768,32 @@ int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
     return rt_ray_first_hits_filtered(as, rays, num_rays, k, nullptr, out, counters, status, stream);
 }
 
+int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                uint32_t k, rt_hit* hits, uint32_t* instance_ids, uint64_t* counters, uint32_t* status,
+                                void* stream)
+{
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
+    if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(records, 16) || misaligned(blas_table, 8) ||
+        misaligned(instance_ids, 4) || misaligned(status, 4) || misaligned(counters, 8))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    InstanceQuery q = InstanceQuery();
+    q.tlas = *tlas;
+    q.records = records;
+    q.num_instances = num_instances;
+    q.blas_table = blas_table;
+    q.num_blas = num_blas;
+    q.rays = rays;
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    q.num_rays = num_rays;
+    q.counters = counters;
+    return hip_rc(launch_ray_first_hits_instanced(q, k, status, static_cast<hipStream_t>(stream)));
+}
+
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
 
 int rt_tri_overlaps_count(const rt_accel* as, const rt_triangle* queries, uint32_t num_queries, uint32_t flags,
@@ -1016,7 +1042,11 @@ const char* rt_version_string(void)
            "ray_hits_instanced: instanced all-hit ray queries, every crossing of every placed copy with its instance, the "
            "all-hit frame (fixed window, unordered 64-entry stack of 4-byte entries, 16 in LDS, CSR by the 64-bit device scan) "
            "with the instanced query's second level in its loop (an entry of count 0 is an instance in the TLAS and a leaf in a "
-           "BLAS, per-lane base pointers, world ray reloaded on exit), hit records and instance ids in parallel segments";
+           "BLAS, per-lane base pointers, world ray reloaded on exit), hit records and instance ids in parallel segments | "
+           "ray_first_instanced: instanced first-K ray queries, the k <= 32 nearest crossings over placed copies in "
+           "(t, instance, primitive_id) order with their instances, the first-K frame (shrinking bound, nearest-first step, "
+           "4-byte pending entries, private list) with the instanced all-hit query's second level in its loop, one bound for "
+           "both levels, the instances in an array parallel to the list's records, one launch";
 }
 
 }  // extern "C"

@@ -387,6 +387,10 @@ hipError_t launch_ray_hits_collect_instanced(const InstanceQuery& q, const uint6
 hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
                                  const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, hipStream_t st);
 
+// ray_first_instanced_query.hip: rt_ray_first_hits_instanced after its argument checks (num_rays > 0, 1 <= k <=
+// RT_RAY_FIRST_MAX_K).  q.hits / q.instance_ids: the rows of k; q.any_hit and q.num_primitives are not read.
+hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, uint32_t* status, hipStream_t st);
+
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.
 size_t tri_overlaps_scratch_bytes(uint32_t num_queries);   // uint64 per workgroup of 256 queries, 256-byte aligned

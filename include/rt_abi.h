@@ -1149,8 +1149,8 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
  * hits / instance_ids (collect); with num_instances > 0 a null records or blas_table, or num_blas = 0 (blas_table may be null
  * only when num_instances = 0); a TLAS with count > 0 and a null node or leaf pointer, tlas->count > 7; rays / hits / records
  * not 16-byte, offsets / blas_table not 8-byte, instance_ids / counts / status not 4-byte, scratch not 256-byte aligned.
- * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, indexed and first-K forms, the host
- * mirror and rt_cli. */
+ * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, an indexed form, the host mirror and
+ * rt_cli.  (The first-K form is rt_ray_first_hits_instanced, the instanced first-K block below.) */
 int rt_ray_hits_count_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                 const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
                                 uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream);
@@ -1230,6 +1230,71 @@ int rt_ray_hits_collect_instanced(const rt_accel* tlas, const rt_instance_record
 enum { RT_RAY_FIRST_STACK_OVERFLOW = 1 };
 int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k, rt_hit* out,
                       uint64_t* counters, uint32_t* status, void* stream);
+
+/* ---- instanced first-K ray queries (no reference counterpart).  The first-K query over a scene of placed copies of built
+ * trees: for each caller ray the K nearest crossings inside its [tmin, tmax] window over every instance, in order, each with
+ * the instance it lies in -- layered transparency, depth peeling, "skip the first surface" picking and thickness on a placed
+ * scene -- without flattening the scene and without the count pass, read-back, allocation, collect pass and sorts of
+ * rt_ray_hits_count_instanced / rt_ray_hits_collect_instanced cut to K.  ONE launch.  The scene is the instanced all-hit
+ * block's: rt_prepare_instances, a TLAS over its proxies built WITHOUT pairs or splits, the records, the BLAS table of triangle
+ * trees.
+ *
+ * Let W be the instanced all-hit row of the ray for its original window, as rt_ray_hits_collect_instanced defines it: a
+ * multiset of 20-byte items (instance, t, primitive_id, u, v).  The definition is the first-K block's with three changes.
+ * Key.  Items order by (t, instance, primitive_id).  Floats compare as floats; a NaN t orders above every number and NaNs are
+ *   equal to each other.  An accepted candidate enters the list iff
+ *   - the list is not full, or its key is below the k-th entry's, and
+ *   - no listed item has the same key.
+ *   Two instances of one BLAS in the same place therefore both report, the lower instance first; a split BLAS reports a triangle
+ *   once per instance.
+ * Bound on both levels.  b is the original tmax while the list holds fewer than k items, the t of the k-th item after (the
+ *   original tmax while that t is NaN): never NaN.  A non-NONE slot is entered iff back >= front && front <= b && back >= tmin
+ *   with the b of that moment -- in the TLAS on the world ray, in a BLAS on the object ray.  A pending entry that is re-tested
+ *   when it is popped is dropped iff front > b.  Equality never prunes.  The triangle test is the all-hit test against
+ *   [tmin, b].  An affine map keeps t, so one b serves both levels without conversion.
+ * Entering an instance.  The instanced all-hit block's, word for word: a TLAS triangle slot that passes names instance
+ *   primitive_id_0 of its leaf record; it is entered iff the id < num_instances, the record's flags are 0, its blas < num_blas
+ *   and the table entry's count is in 1..7; o' = W*(o, 1), d' = W3x3*d, each row ((w0*x + w1*y) + w2*z) [+ w3] in float32, 1/d'
+ *   by IEEE division; on leaving the instance the world ray is reloaded from rays[i], the original bits.
+ * Output.  hits[i*k .. i*k + k) and instance_ids[i*k .. i*k + k) (64-bit indexing) hold the list ascending by key, then
+ *   padding: {+inf, RT_MISS, 0, 0} with instance RT_MISS.  A ray that is not traced (the first-K block's liveness rule) gets k
+ *   pads and counts nothing; so does every ray when num_instances = 0 or the TLAS is empty (count = 0).  Rows at i >= num_rays
+ *   are not written.
+ * Gate.  For an item w of W, g(w) is the largest slab front over the TLAS slots on the path from the TLAS root run to the
+ *   instance's leaf slot, that slot included (world-ray fronts), and the BLAS slots from its root run to w's leaf slot, that slot
+ *   included (object-ray fronts); on a split BLAS the smallest such value over the paths.  Ws is W with duplicates by key removed,
+ *   sorted by key; E its first min(k, |Ws|) items; T1 the t of its (k+1)-th item, or the original tmax if there is none.
+ * Order.  An implementation matter, as in the first-K block: the surviving slot of a run with the smallest front goes next
+ *   (ties: the lower slot) on both levels, and an instance is walked to the end before the next TLAS entry is popped.
+ *
+ * What is promised with status 0 (DESIGN section 30 has the proofs; they are the first-K block's, because b never rises and
+ * the TLAS proxy's front is one more slot on the path):
+ *   1. every live item of the row is an item of W, bit for bit in all 20 bytes; the row is strictly ascending by key; pads come
+ *      only at the end;
+ *   2. DECIDED rays: if every w in E has g(w) <= T1, the row is E, bit for bit.  A ray with |Ws| <= k is decided;
+ *   3. EVERY ray: with T the final bound (the last live t of a full row -- the original tmax if that t is NaN -- else the
+ *      original tmax), every w in W with g(w) <= T and a key below the row's last live item is in the row;
+ *   4. counters[0] and counters[1] are at most rt_ray_hits_count_instanced's for the same rays, and equal when every ray has
+ *      |Ws| < k.
+ * Further, without a promise beyond the above: k = 1 on a decided ray gives a t at most rt_intersect_rays_instanced's
+ * closest-hit t, a miss there is a row of pads and the other way round; an identity instance over a tree gives
+ * rt_ray_first_hits's row on that tree with all instances 0, on rays decided for both and without -0 components.
+ *
+ * Stack: ONE stack of 64 four-byte entries serves both levels, the BLAS's entries above the TLAS's (the instanced all-hit
+ * block's).  A dropped push sets RT_RAY_FIRST_STACK_OVERFLOW; the row is then a sorted subset of W (claim 1 still holds).
+ * counters: optional device uint64[4]: [0] += non-NONE slots examined, both levels together, [1] += BLAS leaf records visited;
+ * [2] / [3] are not touched.  status: optional device uint32 the call ORs flags into (the caller clears it).  Asynchronous (no
+ * allocation, no scratch, no host copy, no synchronisation: hipGraph-capturable).  num_rays = 0: nothing runs.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): a null tlas / rays / hits / instance_ids; with
+ * num_instances > 0 a null records or blas_table, or num_blas = 0 (blas_table may be null only when num_instances = 0); a TLAS
+ * with count > 0 and a null node or leaf pointer, tlas->count > 7; k = 0 or k > RT_RAY_FIRST_MAX_K; rays / hits / records not
+ * 16-byte, blas_table / counters not 8-byte, instance_ids / status not 4-byte aligned.
+ * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, an indexed form, the host mirror and
+ * rt_cli. */
+int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                uint32_t k, rt_hit* hits, uint32_t* instance_ids,
+                                uint64_t* counters, uint32_t* status, void* stream);
 
 /* ---- hit filters for the ray queries (no reference counterpart).  The four ray queries above accept every triangle that
  * Moller-Trumbore accepts.  Their filtered siblings take one more argument, an rt_hit_filter, that says which of those
@@ -1375,8 +1440,9 @@ int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t 
  * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of rt_intersect_rays_instanced's; a flag bit
  * other than RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT in filter->flags; per_instance not 8-byte aligned; per_ray not 16-byte
  * aligned.  num_instance_filters > 0 with a null per_instance is fine.  Asynchronous and hipGraph-capturable like the sibling.
- * Out of scope: there is no per-primitive mask in this call -- grouping is per instance --, and the indexed, all-hit and first-K
- * queries have no instanced form, filtered or not. */
+ * Out of scope: there is no per-primitive mask in this call -- grouping is per instance --, and the indexed query
+ * has no instanced form; the instanced all-hit and first-K queries (rt_ray_hits_collect_instanced, rt_ray_first_hits_instanced)
+ * take no filter. */
 enum { RT_INSTANCE_FILTER_CULL_DISABLE = 1, RT_INSTANCE_FILTER_FLIP_FACING = 2 };
 typedef struct rt_instance_filter {
     uint32_t mask;                        /* im of rule 1 */
