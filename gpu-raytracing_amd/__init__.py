@@ -249,7 +249,9 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_tri_overlaps_scratch_bytes", "rt_tri_overlaps_count", "rt_tri_overlaps_collect",
            "rt_signed_distance", "rt_occupancy", "rt_generate_grid_points",
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced",
-           "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_ray_first_hits_instanced", "rt_error_string", "rt_version_string"]
+           "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_ray_first_hits_instanced",
+           "rt_ray_hits_count_instanced_filtered", "rt_ray_hits_collect_instanced_filtered",
+           "rt_ray_first_hits_instanced_filtered", "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -381,6 +383,15 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_hits_collect_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.rt_ray_first_hits_instanced.restype = i32
     L.rt_ray_first_hits_instanced.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, u32, vp, vp, vp, vp, vp]
+    ifl = ctypes.POINTER(_InstanceHitFilter)
+    L.rt_ray_hits_count_instanced_filtered.restype = i32
+    L.rt_ray_hits_count_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, ifl, vp, vp, vp, vp, vp]
+    L.rt_ray_hits_collect_instanced_filtered.restype = i32
+    L.rt_ray_hits_collect_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, ifl, vp, vp, vp, vp,
+                                                         vp, vp, vp]
+    L.rt_ray_first_hits_instanced_filtered.restype = i32
+    L.rt_ray_first_hits_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, u32, ifl, vp, vp, vp, vp,
+                                                       vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -1288,17 +1299,22 @@ def RayHitsInstanced(tlas_triangles, tlas_nodes, root: int, count: int, records,
         ids = torch.empty(max(total, 1), dtype=torch.int32, device=rays.device)[:total]
         RayHitsCollectInstanced(*tree, rays, offsets, hits, ids, counters=counters, status=status, stream=stream)
         if sort and total > 1:
-            # three stable sorts: by primitive_id (unsigned), by instance (unsigned), then by the 64-bit key row << 32 | the
-            # monotone integer image of t (-0 counted as +0), which keeps every record inside its row
-            row = torch.repeat_interleave(torch.arange(n, device=rays.device), offsets[1:] - offsets[:-1], output_size=total)
-            bits = hits.view(torch.int32).to(torch.int64)
-            order = torch.argsort(bits[:, 1] & 0xFFFFFFFF, stable=True)
-            order = order[torch.argsort(ids.to(torch.int64)[order] & 0xFFFFFFFF, stable=True)]
-            tb = (hits[:, 0] + 0.0).contiguous().view(torch.int32).to(torch.int64)
-            key = (row << 32) | (torch.where(tb >= 0, tb, tb ^ 0x7FFFFFFF) + (1 << 31))
-            order = order[torch.argsort(key[order], stable=True)]
-            hits, ids = hits[order].contiguous(), ids[order].contiguous()
+            hits, ids = _sort_instanced_rows(offsets, hits, ids, n, total)
     return offsets, hits, ids
+
+
+def _sort_instanced_rows(offsets, hits, ids, n: int, total: int):
+    """sort=True of RayHitsInstanced[Filtered]: three stable sorts, by primitive_id (unsigned), by instance (unsigned), then by
+    the 64-bit key row << 32 | the monotone integer image of t (-0 counted as +0), which keeps every record inside its row"""
+    torch = _torch()
+    row = torch.repeat_interleave(torch.arange(n, device=hits.device), offsets[1:] - offsets[:-1], output_size=total)
+    bits = hits.view(torch.int32).to(torch.int64)
+    order = torch.argsort(bits[:, 1] & 0xFFFFFFFF, stable=True)
+    order = order[torch.argsort(ids.to(torch.int64)[order] & 0xFFFFFFFF, stable=True)]
+    tb = (hits[:, 0] + 0.0).contiguous().view(torch.int32).to(torch.int64)
+    key = (row << 32) | (torch.where(tb >= 0, tb, tb ^ 0x7FFFFFFF) + (1 << 31))
+    order = order[torch.argsort(key[order], stable=True)]
+    return hits[order].contiguous(), ids[order].contiguous()
 
 
 def RayFirstHits(triangles, nodes, root: int, count: int, rays, k: int, out, *, counters=None, status=None, stream=None) -> int:
@@ -1481,6 +1497,108 @@ def IntersectRaysInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count:
                                                       kAnyHit if any_hit else kClosestHit, int(num_primitives), flt,
                                                       _ptr(counters), _stream_ptr(stream)),
            "rt_intersect_rays_instanced_filtered")
+
+
+def _instance_filter_ref(filter, num_rays: int):
+    if filter is not None and not isinstance(filter, InstanceHitFilter):
+        raise ValueError("filter must be an InstanceHitFilter or None")
+    return _filter_ref(filter, num_rays)
+
+
+def RayHitsCountInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                  num_blas: int, rays, filter, offsets, *, scratch=None, counters=None, status=None,
+                                  stream=None) -> int:
+    """rt_ray_hits_count_instanced_filtered: RayHitsCountInstanced over the instances and candidates `filter` (an
+    InstanceHitFilter, or None for all) keeps (include/rt_abi.h, instanced set-filter block).  A masked-out instance is never
+    entered (no record load, no BLAS descent); a rejected triangle is not a crossing.  Everything else is the sibling's."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words")
+    flt = _instance_filter_ref(filter, n)
+    if n == 0:
+        return 0
+    if scratch is None:
+        scratch = device_bytes(RayHitsScratchBytes(n), rays.device)
+    elif _nbytes(scratch) < RayHitsScratchBytes(n):
+        raise ValueError(f"scratch must hold RayHitsScratchBytes({n}) bytes")
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_hits_count_instanced_filtered(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                      int(num_blas), _ptr(rays), n, flt, _ptr(offsets), _ptr(scratch),
+                                                      _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           "rt_ray_hits_count_instanced_filtered")
+    return n
+
+
+def RayHitsCollectInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                    num_blas: int, rays, filter, offsets, hits, instance_ids, *, counts=None, counters=None,
+                                    status=None, stream=None) -> int:
+    """rt_ray_hits_collect_instanced_filtered: RayHitsCollectInstanced over the instances and candidates `filter` (an
+    InstanceHitFilter, or None for all) keeps: the rows RayHitsCountInstancedFiltered counted under the same filter."""
+    n = _ray_batch(rays)
+    if not offsets.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or \
+            _nbytes(offsets) < 8 * (n + 1):
+        raise ValueError(f"offsets must be a contiguous device buffer of {n + 1} 64-bit words, hits / instance_ids contiguous "
+                         "device buffers")
+    if counts is not None and (not counts.is_contiguous() or _nbytes(counts) < 4 * n):
+        raise ValueError(f"counts must hold {n} words")
+    flt = _instance_filter_ref(filter, n)
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_hits_collect_instanced_filtered(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                        int(num_blas), _ptr(rays), n, flt, _ptr(offsets), _ptr(hits),
+                                                        _ptr(instance_ids), _ptr(counts), _ptr(counters), _ptr(status),
+                                                        _stream_ptr(stream)), "rt_ray_hits_collect_instanced_filtered")
+    return n
+
+
+def RayHitsInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                             num_blas: int, rays, filter, *, sort: bool = False, counters=None, status=None, stream=None):
+    """RayHitsInstanced over the instances and candidates `filter` (an InstanceHitFilter, or None for all) keeps:
+    RayHitsCountInstancedFiltered, the total READ BACK TO THE HOST (one synchronisation of `stream`), then
+    RayHitsCollectInstancedFiltered.  Returns (offsets, hits, instance_ids) as RayHitsInstanced does; sort=True orders every
+    row by ascending (t, instance, primitive_id)."""
+    torch = _torch()
+    n = _ray_batch(rays)
+    tree = (tlas_triangles, tlas_nodes, root, count, records, num_instances, blas_table, num_blas)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=rays.device)
+    RayHitsCountInstancedFiltered(*tree, rays, filter, offsets, counters=counters, status=status, stream=stream)
+    with _on_stream(stream):
+        if n == 0:
+            offsets.zero_()
+        total = int(offsets[n].item())
+        hits = torch.empty((max(total, 1), 4), dtype=torch.float32, device=rays.device)[:total]
+        ids = torch.empty(max(total, 1), dtype=torch.int32, device=rays.device)[:total]
+        RayHitsCollectInstancedFiltered(*tree, rays, filter, offsets, hits, ids, counters=counters, status=status, stream=stream)
+        if sort and total > 1:
+            hits, ids = _sort_instanced_rows(offsets, hits, ids, n, total)
+    return offsets, hits, ids
+
+
+def RayFirstHitsInstancedFiltered(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                  num_blas: int, rays, k: int, filter, hits, instance_ids, *, counters=None, status=None,
+                                  stream=None) -> int:
+    """rt_ray_first_hits_instanced_filtered: RayFirstHitsInstanced over the instances and candidates `filter` (an
+    InstanceHitFilter, or None for all) keeps: the k nearest KEPT crossings.  A rejected crossing never enters the list and
+    never shrinks the bound (include/rt_abi.h, instanced set-filter block)."""
+    torch = _torch()
+    k = int(k)
+    if not 1 <= k <= RT_RAY_FIRST_MAX_K:
+        raise ValueError(f"k must be in 1 .. {RT_RAY_FIRST_MAX_K}")
+    n = _ray_batch(rays)
+    if not hits.is_contiguous() or hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 4):
+        raise ValueError(f"hits must be a contiguous float32 tensor of shape [{n}, {k}, 4]")
+    if not instance_ids.is_contiguous() or instance_ids.dtype != torch.int32 or tuple(instance_ids.shape) != (n, k):
+        raise ValueError(f"instance_ids must be a contiguous int32 tensor of shape [{n}, {k}]")
+    flt = _instance_filter_ref(filter, n)
+    if n == 0:
+        return 0
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_ray_first_hits_instanced_filtered(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                      int(num_blas), _ptr(rays), n, k, flt, _ptr(hits), _ptr(instance_ids),
+                                                      _ptr(counters), _ptr(status), _stream_ptr(stream)),
+           "rt_ray_first_hits_instanced_filtered")
+    return n
 
 
 def TriOverlapsScratchBytes(num_queries: int) -> int:

@@ -28,14 +28,22 @@
 //     arm that would carry it cost ray_first_kernel up to 45 % for 1.5 % of the box tests.  The entered instance's root run meets
 //     the current b at once, so a stale entry costs one record load, one transform and the slab tests of one run.
 // A push onto a full stack of 64 (both levels together) is dropped and flagged (RT_RAY_FIRST_STACK_OVERFLOW): the row is then
-// a sorted subset of the instanced all-hit row.  No restart pass, no filter arm, no 8-byte pending arm.
+// a sorted subset of the instanced all-hit row.  No restart pass, no 8-byte pending arm.
+// FILTERED (rt_ray_first_hits_instanced_filtered; rt_abi.h, instanced set-filter block) is the same traversal
+// with the lane's InstanceRayFilter (rt_instance_filter.hpp): enter(id) is asked at the TLAS leaf before the record is read
+// (a popped entry of a masked instance goes on in the TLAS), set_instance once the rows are in registers, and `tri` is
+// intersect_tri's policy at its one acceptance point -- BEFORE the offer, so a rejected crossing never enters the list and
+// never moves the bound.
 // Compiled with -ffp-contract=off and IEEE division: every listed item is bit for bit the one rt_ray_hits_collect_instanced
 // emits for that instance and triangle.
 #include "rt_device.hpp"
+#include "rt_instance_filter.hpp"
 #include "rt_instance_traverse.hpp"
 #include "rt_launch.hpp"
 #include "rt_point_math.hpp"
 #include "rt_traverse.hpp"
+
+#include <type_traits>
 
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 16, "rt_ray: two 16-byte halves; rt_hit: one 16-byte record");
 static_assert(sizeof(rt_instance_record) == 64 && sizeof(rt_accel) == 24, "the record and table entry trace_instanced loads");
@@ -47,17 +55,28 @@ static_assert(rt::kQueryBlock == rt::kTraceWaves * 64, "rt_launch.hpp: one lane 
 #ifndef RT_RAY_FIRST_INSTANCED_WAVES
 #define RT_RAY_FIRST_INSTANCED_WAVES 6
 #endif
+// the FILTERED arm keeps six more values live per lane and has its own bound.  6, the sibling's (80 VGPRs, 42 spilled), ships:
+// 7 (72 VGPRs, 53 spilled) measured up to 4 % faster on an MI355X at k = 1 and 4 and on incoherent rays, and 3 to 12 % slower
+// on coherent rays at k = 32; 5 loses to 6 in ten of twelve cells (DESIGN section 31 has the tables)
+#ifndef RT_RAY_FIRST_INSTANCED_FILTERED_WAVES
+#define RT_RAY_FIRST_INSTANCED_FILTERED_WAVES 6
+#endif
 
 namespace rt {
 
 namespace {
 
+constexpr int kRayFirstInstancedWaves = RT_RAY_FIRST_INSTANCED_WAVES;
+constexpr int kRayFirstInstancedFilteredWaves = RT_RAY_FIRST_INSTANCED_FILTERED_WAVES;
 constexpr int kRfiStackLds = 16;  // LDS-resident entries per lane: 16 x 4 B x 256 lanes = 16 KB per workgroup
 
 // InstParams's fields as trace_instanced reads them (hits: rt_hit as one float4, row i at hits + i * k; instance_ids: parallel)
 struct RayFirstInstParams : InstParams {
     uint32_t k;
     uint32_t* status;
+};
+struct FilteredRayFirstInstParams : RayFirstInstParams {
+    InstanceFilterParams filter;
 };
 
 typedef uint32_t RfiSpill[kStackMax - kRfiStackLds];
@@ -69,8 +88,9 @@ __device__ __forceinline__ bool rfi_below(float t, uint32_t in, uint32_t id, flo
     return t < et || (!__builtin_isnan(t) && __builtin_isnan(et)) || (rfi_same_t(t, et) && (in < ein || (in == ein && id < eid)));
 }
 
-__global__ __launch_bounds__(kTraceWaves * 64, RT_RAY_FIRST_INSTANCED_WAVES)
-void ray_first_instanced_kernel(RayFirstInstParams p)
+template <bool FILTERED>
+__global__ __launch_bounds__(kTraceWaves * 64, FILTERED ? kRayFirstInstancedFilteredWaves : kRayFirstInstancedWaves)
+void ray_first_instanced_kernel(std::conditional_t<FILTERED, FilteredRayFirstInstParams, RayFirstInstParams> p)
 {
     // the counters' workgroup sums reuse the stack's LDS once every lane is done with it (no extra bytes)
     __shared__ alignas(8) uint32_t stack_lds[kTraceWaves][kRfiStackLds][64];
@@ -114,6 +134,9 @@ void ray_first_instanced_kernel(RayFirstInstParams p)
     uint32_t inst = kTop;
     int base = 0;
     bool leaving = false;             // the BLAS's part of the stack is used up: parked until the leaf phase takes the lane out
+    // the lane's filter, made HERE under `if constexpr`, not by a helper function (DESIGN sections 20 and 21)
+    std::conditional_t<FILTERED, InstanceRayFilter, NoInstanceFilter> flt;
+    if constexpr (FILTERED) flt = instance_ray_filter(p.filter, i, in_range);
 
     // an accepted triangle of the lane's instance (t <= bound, stored weights bu / bv, rotation rot)
     auto offer = [&](float t, uint32_t id, float bu, float bv, uint32_t rot) {
@@ -144,7 +167,12 @@ void ray_first_instanced_kernel(RayFirstInstParams p)
     auto test = [&](float c0x, float c0y, float c0z, float c1x, float c1y, float c1z, float c2x, float c2y, float c2z,
                     uint32_t prim, uint32_t rot) {
         Hit h;
-        if (intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim)) offer(r.tmax, prim, h.bu, h.bv, rot);
+        if constexpr (FILTERED) {
+            if (intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim, flt.tri))
+                offer(r.tmax, prim, h.bu, h.bv, rot);
+        } else {
+            if (intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim)) offer(r.tmax, prim, h.bu, h.bv, rot);
+        }
         r.tmax = bound;               // intersect_tri shrank it to t: the window's end is the bound, nothing else
     };
     auto next_from_stack = [&]() {
@@ -231,6 +259,9 @@ void ray_first_instanced_kernel(RayFirstInstParams p)
                 uint32_t nroot = 0, ncount = 0;
                 uint64_t ntris = 0, nnodes = 0;
                 float4 w0, w1, w2;
+                if constexpr (FILTERED) {
+                    if (ok) ok = flt.enter(id);   // the instance rule: asked first, a masked-out instance makes no further load
+                }
                 if (ok) {
                     const float4* rec = reinterpret_cast<const float4*>(p.records + id);
                     w0 = rec[0]; w1 = rec[1]; w2 = rec[2];
@@ -255,6 +286,7 @@ void ray_first_instanced_kernel(RayFirstInstParams p)
                     inst = id;
                     base = sp;
                     cur = (nroot & kIndexMask) | (ncount << 29);
+                    if constexpr (FILTERED) flt.set_instance(id, w0, w1, w2);
                 } else {
                     next_from_stack();
                 }
@@ -293,9 +325,10 @@ void ray_first_instanced_kernel(RayFirstInstParams p)
 
 }  // namespace
 
-hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, uint32_t* status, hipStream_t st)
+hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, const rt_instance_hit_filter* filter,
+                                           uint32_t* status, hipStream_t st)
 {
-    RayFirstInstParams p = {};
+    FilteredRayFirstInstParams p = {};
     p.tlas_nodes = q.tlas.nodes;
     p.tlas_leaves = q.tlas.triangles;
     p.root = q.tlas.root;
@@ -311,7 +344,13 @@ hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, u
     p.counters = reinterpret_cast<unsigned long long*>(q.counters);
     p.k = k;
     p.status = status;
-    ray_first_instanced_kernel<<<dim3(query_blocks(q.num_rays)), dim3(kQueryBlock), 0, st>>>(p);
+    const dim3 grid(query_blocks(q.num_rays)), block(kQueryBlock);
+    if (filter) {
+        p.filter = instance_filter_params(*filter);
+        ray_first_instanced_kernel<true><<<grid, block, 0, st>>>(p);
+    } else {
+        ray_first_instanced_kernel<false><<<grid, block, 0, st>>>(p);   // (its RayFirstInstParams part)
+    }
     return hipGetLastError();
 }
 

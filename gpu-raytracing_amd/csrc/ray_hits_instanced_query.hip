@@ -22,17 +22,34 @@
 //   * one stack of 64 for both levels: a BLAS entered at depth k pushes at k .. 63 and leaves when its pops reach k again.  A
 //     push onto a full stack is dropped and flagged (RT_RAY_HITS_STACK_OVERFLOW): the row is then a subset;
 //   * COLLECT: record j < room goes to hits[offsets[i] + j] and its instance to instance_ids[offsets[i] + j].
-// No pair-prefetch arm, no filter arm.  Compiled with -ffp-contract=off and IEEE division: inside an instance every record is
+// FILTERED (rt_ray_hits_count_instanced_filtered / rt_ray_hits_collect_instanced_filtered; rt_abi.h, instanced set-filter block;
+// DESIGN section 31) is the same traversal with the lane's InstanceRayFilter (rt_instance_filter.hpp): enter(id) is asked at the
+// TLAS leaf before the record is read, set_instance once the rows are in registers, and `tri` is intersect_tri's policy at its
+// one acceptance point.  The window does not move, so the filtered row is the unfiltered one less what the two rules reject.
+// No pair-prefetch arm.  Compiled with -ffp-contract=off and IEEE division: inside an instance every record is
 // bit for bit rt_ray_hits_collect's for the object ray, which is rt_intersect_rays_instanced's object ray.
 #include "rt_csr.hpp"
 #include "rt_device.hpp"
+#include "rt_instance_filter.hpp"
 #include "rt_instance_traverse.hpp"
 #include "rt_launch.hpp"
 #include "rt_point_math.hpp"
 #include "rt_traverse.hpp"
 
+#include <type_traits>
+
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 16, "rt_ray: two 16-byte halves; rt_hit: one 16-byte record");
 static_assert(sizeof(rt_instance_record) == 64 && sizeof(rt_accel) == 24, "the record and table entry trace_instanced loads");
+
+// the launch bounds of the FILTERED arms (below), overridable for the bound sweep of tools/instance_set_filter_bench.py.
+// Count: 7 (71 VGPRs, 40 spilled) measured 5 to 7 % faster on an MI355X than 6 in every cell, and faster than 5 and 8.
+// Collect: 6 (80 VGPRs, 37 spilled) measured faster than 5 in three of four cells and than 4 in all
+#ifndef RT_RAY_HITS_INSTANCED_COUNT_FILTERED_WAVES
+#define RT_RAY_HITS_INSTANCED_COUNT_FILTERED_WAVES 7
+#endif
+#ifndef RT_RAY_HITS_INSTANCED_COLLECT_FILTERED_WAVES
+#define RT_RAY_HITS_INSTANCED_COLLECT_FILTERED_WAVES 6
+#endif
 
 namespace rt {
 
@@ -42,6 +59,15 @@ namespace {
 // registers.  Count: 6 (80 VGPRs, no spill; at 7 it spills 18).  Collect: 5 (96 VGPRs, no spill; at 6 it spills 30 inside the
 // loop and measured 3 % slower on the SAH trees, no faster on the LBVH ones).  DESIGN section 29 has the table and the runs.
 constexpr int kRayHitsInstancedCountWaves = 6, kRayHitsInstancedCollectWaves = 5;
+// the FILTERED arms keep six more values live per lane (mask, skip_instance, skip_id, inst_flags, tri.cull, tri.skip) and spill
+// at the siblings' bounds: their own, measured ones (above)
+constexpr int kRayHitsInstancedCountFilteredWaves = RT_RAY_HITS_INSTANCED_COUNT_FILTERED_WAVES,
+              kRayHitsInstancedCollectFilteredWaves = RT_RAY_HITS_INSTANCED_COLLECT_FILTERED_WAVES;
+constexpr int ray_hits_instanced_waves(bool collect, bool filtered)
+{
+    return collect ? (filtered ? kRayHitsInstancedCollectFilteredWaves : kRayHitsInstancedCollectWaves)
+                   : (filtered ? kRayHitsInstancedCountFilteredWaves : kRayHitsInstancedCountWaves);
+}
 
 // InstParams's fields as trace_instanced reads them (hits: rt_hit as one float4; instance_ids: parallel to hits), and the CSR part
 struct RayHitsInstParams : InstParams {
@@ -50,13 +76,15 @@ struct RayHitsInstParams : InstParams {
     uint32_t* counts;             // collect, optional
     uint32_t* status;
 };
+struct FilteredRayHitsInstParams : RayHitsInstParams {
+    InstanceFilterParams filter;
+};
 
 typedef uint32_t RhiSpill[kStackMax - kCsrStackLds];
 
-template <bool COLLECT>
-__global__ __launch_bounds__(kTraceWaves * 64,
-                             COLLECT ? kRayHitsInstancedCollectWaves : kRayHitsInstancedCountWaves)
-void ray_hits_instanced_kernel(RayHitsInstParams p)
+template <bool COLLECT, bool FILTERED>
+__global__ __launch_bounds__(kTraceWaves * 64, ray_hits_instanced_waves(COLLECT, FILTERED))
+void ray_hits_instanced_kernel(std::conditional_t<FILTERED, FilteredRayHitsInstParams, RayHitsInstParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kCsrStackLds][64];
     __shared__ unsigned long long csum[2];
@@ -102,6 +130,9 @@ void ray_hits_instanced_kernel(RayHitsInstParams p)
     uint32_t inst = kTop;
     int base = 0;
     bool leaving = false;             // the BLAS's part of the stack is used up: parked until the leaf phase takes the lane out
+    // the lane's filter, made HERE under `if constexpr`, not by a helper function (DESIGN sections 20 and 21)
+    std::conditional_t<FILTERED, InstanceRayFilter, NoInstanceFilter> flt;
+    if constexpr (FILTERED) flt = instance_ray_filter(p.filter, i, in_range);
 
     auto next_from_stack = [&]() {
         if (sp == base) {
@@ -116,7 +147,11 @@ void ray_hits_instanced_kernel(RayHitsInstParams p)
     auto test = [&](float c0x, float c0y, float c0z, float c1x, float c1y, float c1z, float c2x, float c2y, float c2z,
                     uint32_t prim, uint32_t rot) {
         Hit h;
-        if (!intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim)) return;
+        if constexpr (FILTERED) {
+            if (!intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim, flt.tri)) return;
+        } else {
+            if (!intersect_tri(c0x, c0y, c0z, c1x, c1y, c1z, c2x, c2y, c2z, r, h, 0u, prim)) return;
+        }
         const float t = r.tmax;
         r.tmax = tmax0;
         if (COLLECT) {
@@ -194,6 +229,9 @@ void ray_hits_instanced_kernel(RayHitsInstParams p)
                 uint32_t nroot = 0, ncount = 0;
                 uint64_t ntris = 0, nnodes = 0;
                 float4 w0, w1, w2;
+                if constexpr (FILTERED) {
+                    if (ok) ok = flt.enter(id);   // the instance rule: asked first, a masked-out instance makes no further load
+                }
                 if (ok) {
                     const float4* rec = reinterpret_cast<const float4*>(p.records + id);
                     w0 = rec[0]; w1 = rec[1]; w2 = rec[2];
@@ -218,6 +256,7 @@ void ray_hits_instanced_kernel(RayHitsInstParams p)
                     inst = id;
                     base = sp;
                     cur = (nroot & kIndexMask) | (ncount << 29);
+                    if constexpr (FILTERED) flt.set_instance(id, w0, w1, w2);
                 } else {
                     next_from_stack();
                 }
@@ -258,10 +297,11 @@ void ray_hits_instanced_kernel(RayHitsInstParams p)
     }
 }
 
-// the fields both launches fill
-RayHitsInstParams hits_instanced_params(const InstanceQuery& q, uint32_t* status)
+// the fields both launches fill (filter: null for the unfiltered kernels, which are handed the RayHitsInstParams part)
+FilteredRayHitsInstParams hits_instanced_params(const InstanceQuery& q, const rt_instance_hit_filter* filter, uint32_t* status)
 {
-    RayHitsInstParams p = {};
+    FilteredRayHitsInstParams p = {};
+    if (filter) p.filter = instance_filter_params(*filter);
     p.tlas_nodes = q.tlas.nodes;
     p.tlas_leaves = q.tlas.triangles;
     p.root = q.tlas.root;
@@ -281,24 +321,28 @@ RayHitsInstParams hits_instanced_params(const InstanceQuery& q, uint32_t* status
 
 }  // namespace
 
-hipError_t launch_ray_hits_count_instanced(const InstanceQuery& q, uint64_t* offsets, void* scratch, uint32_t* status,
-                                           hipStream_t st)
+hipError_t launch_ray_hits_count_instanced(const InstanceQuery& q, const rt_instance_hit_filter* filter, uint64_t* offsets,
+                                           void* scratch, uint32_t* status, hipStream_t st)
 {
-    RayHitsInstParams p = hits_instanced_params(q, status);
+    FilteredRayHitsInstParams p = hits_instanced_params(q, filter, status);
     p.offsets = offsets;
     p.block_sums = static_cast<uint64_t*>(scratch);
     const uint32_t blocks = csr_blocks(q.num_rays);
-    if (blocks) ray_hits_instanced_kernel<false><<<blocks, kCsrBlock, 0, st>>>(p);
+    if (blocks) {
+        if (filter) ray_hits_instanced_kernel<false, true><<<blocks, kCsrBlock, 0, st>>>(p);
+        else ray_hits_instanced_kernel<false, false><<<blocks, kCsrBlock, 0, st>>>(p);   // (its RayHitsInstParams part)
+    }
     return launch_csr_offsets(offsets, p.block_sums, q.num_rays, st);
 }
 
-hipError_t launch_ray_hits_collect_instanced(const InstanceQuery& q, const uint64_t* offsets, uint32_t* counts,
-                                             uint32_t* status, hipStream_t st)
+hipError_t launch_ray_hits_collect_instanced(const InstanceQuery& q, const rt_instance_hit_filter* filter,
+                                             const uint64_t* offsets, uint32_t* counts, uint32_t* status, hipStream_t st)
 {
-    RayHitsInstParams p = hits_instanced_params(q, status);
+    FilteredRayHitsInstParams p = hits_instanced_params(q, filter, status);
     p.offsets = const_cast<uint64_t*>(offsets);   // (the collect instantiation only reads them)
     p.counts = counts;
-    ray_hits_instanced_kernel<true><<<csr_blocks(q.num_rays), kCsrBlock, 0, st>>>(p);
+    if (filter) ray_hits_instanced_kernel<true, true><<<csr_blocks(q.num_rays), kCsrBlock, 0, st>>>(p);
+    else ray_hits_instanced_kernel<true, false><<<csr_blocks(q.num_rays), kCsrBlock, 0, st>>>(p);
     return hipGetLastError();
 }
 

@@ -724,16 +724,48 @@ static bool hits_instanced_args(const rt_accel* tlas, const rt_instance_record* 
     return true;
 }
 
+// the instance filter's own checks (none: the unfiltered kernel), as rt_intersect_rays_instanced_filtered makes them
+static inline bool instance_filter_args(const rt_instance_hit_filter* f)
+{
+    return !f || !((f->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) || misaligned(f->per_instance, 8) ||
+                   misaligned(f->per_ray, 16));
+}
+
+int rt_ray_hits_count_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                         const rt_instance_hit_filter* filter, uint64_t* offsets, void* scratch,
+                                         uint64_t* counters, uint32_t* status, void* stream)
+{
+    InstanceQuery q;
+    if (!hits_instanced_args(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, offsets, counters, status, q) ||
+        !csr_count_args(scratch) || !instance_filter_args(filter))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0) return RT_OK;
+    return hip_rc(launch_ray_hits_count_instanced(q, filter, offsets, scratch, status, static_cast<hipStream_t>(stream)));
+}
+
 int rt_ray_hits_count_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                 const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
                                 uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream)
 {
+    return rt_ray_hits_count_instanced_filtered(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, nullptr,
+                                                offsets, scratch, counters, status, stream);
+}
+
+int rt_ray_hits_collect_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                           const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays,
+                                           uint32_t num_rays, const rt_instance_hit_filter* filter, const uint64_t* offsets,
+                                           rt_hit* hits, uint32_t* instance_ids, uint32_t* counts, uint64_t* counters,
+                                           uint32_t* status, void* stream)
+{
     InstanceQuery q;
     if (!hits_instanced_args(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, offsets, counters, status, q) ||
-        !csr_count_args(scratch))
+        !csr_collect_args(hits, 16, counts) || !instance_ids || misaligned(instance_ids, 4) || !instance_filter_args(filter))
         return RT_ERR_INVALID_ARGUMENT;
     if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_ray_hits_count_instanced(q, offsets, scratch, status, static_cast<hipStream_t>(stream)));
+    q.hits = hits;
+    q.instance_ids = instance_ids;
+    return hip_rc(launch_ray_hits_collect_instanced(q, filter, offsets, counts, status, static_cast<hipStream_t>(stream)));
 }
 
 int rt_ray_hits_collect_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
@@ -741,14 +773,8 @@ int rt_ray_hits_collect_instanced(const rt_accel* tlas, const rt_instance_record
                                   const uint64_t* offsets, rt_hit* hits, uint32_t* instance_ids, uint32_t* counts,
                                   uint64_t* counters, uint32_t* status, void* stream)
 {
-    InstanceQuery q;
-    if (!hits_instanced_args(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, offsets, counters, status, q) ||
-        !csr_collect_args(hits, 16, counts) || !instance_ids || misaligned(instance_ids, 4))
-        return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    q.hits = hits;
-    q.instance_ids = instance_ids;
-    return hip_rc(launch_ray_hits_collect_instanced(q, offsets, counts, status, static_cast<hipStream_t>(stream)));
+    return rt_ray_hits_collect_instanced_filtered(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, nullptr,
+                                                  offsets, hits, instance_ids, counts, counters, status, stream);
 }
 
 int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
@@ -768,12 +794,12 @@ int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
     return rt_ray_first_hits_filtered(as, rays, num_rays, k, nullptr, out, counters, status, stream);
 }
 
-int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
-                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
-                                uint32_t k, rt_hit* hits, uint32_t* instance_ids, uint64_t* counters, uint32_t* status,
-                                void* stream)
+int rt_ray_first_hits_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                         uint32_t k, const rt_instance_hit_filter* filter, rt_hit* hits, uint32_t* instance_ids,
+                                         uint64_t* counters, uint32_t* status, void* stream)
 {
-    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids || !instance_filter_args(filter)) return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (k == 0 || k > RT_RAY_FIRST_MAX_K) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(records, 16) || misaligned(blas_table, 8) ||
@@ -791,7 +817,16 @@ int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* 
     q.instance_ids = instance_ids;
     q.num_rays = num_rays;
     q.counters = counters;
-    return hip_rc(launch_ray_first_hits_instanced(q, k, status, static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_ray_first_hits_instanced(q, k, filter, status, static_cast<hipStream_t>(stream)));
+}
+
+int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                uint32_t k, rt_hit* hits, uint32_t* instance_ids, uint64_t* counters, uint32_t* status,
+                                void* stream)
+{
+    return rt_ray_first_hits_instanced_filtered(tlas, records, num_instances, blas_table, num_blas, rays, num_rays, k, nullptr,
+                                                hits, instance_ids, counters, status, stream);
 }
 
 size_t rt_tri_overlaps_scratch_bytes(uint32_t num_queries) { return tri_overlaps_scratch_bytes(num_queries); }
@@ -1046,7 +1081,11 @@ const char* rt_version_string(void)
            "ray_first_instanced: instanced first-K ray queries, the k <= 32 nearest crossings over placed copies in "
            "(t, instance, primitive_id) order with their instances, the first-K frame (shrinking bound, nearest-first step, "
            "4-byte pending entries, private list) with the instanced all-hit query's second level in its loop, one bound for "
-           "both levels, the instances in an array parallel to the list's records, one launch";
+           "both levels, the instances in an array parallel to the list's records, one launch | "
+           "instance_set_filter: the instanced all-hit and first-K queries with the instanced query's filter (instance mask "
+           "asked at the TLAS leaf before the record is read, world-space face culling, a per-ray (instance, primitive) skip) "
+           "as a FILTERED template arm of the siblings' kernels, a rejected crossing never enters the first-K list or moves "
+           "its bound";
 }
 
 }  // extern "C"

@@ -376,20 +376,23 @@ hipError_t launch_ray_hits_collect(const rt_accel& as, const rt_ray* rays, uint3
                                    const uint64_t* offsets, rt_hit* hits, uint32_t* counts, uint64_t* counters,
                                    uint32_t* status, hipStream_t st);
 
-// ray_hits_instanced_query.hip: rt_ray_hits_count_instanced / rt_ray_hits_collect_instanced after their argument checks (both
-// are called with num_rays > 0).  q.hits / q.instance_ids: the collect call's rows; q.any_hit and q.num_primitives are not read.
-hipError_t launch_ray_hits_count_instanced(const InstanceQuery& q, uint64_t* offsets, void* scratch, uint32_t* status,
-                                           hipStream_t st);
-hipError_t launch_ray_hits_collect_instanced(const InstanceQuery& q, const uint64_t* offsets, uint32_t* counts,
-                                             uint32_t* status, hipStream_t st);
+// ray_hits_instanced_query.hip: rt_ray_hits_count_instanced[_filtered] / rt_ray_hits_collect_instanced[_filtered] after their
+// argument checks (both are called with num_rays > 0).  q.hits / q.instance_ids: the collect call's rows; q.any_hit and
+// q.num_primitives are not read.  filter: null runs the unfiltered kernel, else (checked by the entry point: flags, alignments)
+// the FILTERED one.
+hipError_t launch_ray_hits_count_instanced(const InstanceQuery& q, const rt_instance_hit_filter* filter, uint64_t* offsets,
+                                           void* scratch, uint32_t* status, hipStream_t st);
+hipError_t launch_ray_hits_collect_instanced(const InstanceQuery& q, const rt_instance_hit_filter* filter,
+                                             const uint64_t* offsets, uint32_t* counts, uint32_t* status, hipStream_t st);
 
 // ray_first_query.hip: rt_ray_first_hits[_filtered] after its argument checks (num_rays > 0, 1 <= k <= RT_RAY_FIRST_MAX_K)
 hipError_t launch_ray_first_hits(const rt_accel& as, const rt_ray* rays, uint32_t num_rays, uint32_t k,
                                  const rt_hit_filter* filter, rt_hit* out, uint64_t* counters, uint32_t* status, hipStream_t st);
 
-// ray_first_instanced_query.hip: rt_ray_first_hits_instanced after its argument checks (num_rays > 0, 1 <= k <=
-// RT_RAY_FIRST_MAX_K).  q.hits / q.instance_ids: the rows of k; q.any_hit and q.num_primitives are not read.
-hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, uint32_t* status, hipStream_t st);
+// ray_first_instanced_query.hip: rt_ray_first_hits_instanced[_filtered] after its argument checks (num_rays > 0, 1 <= k <=
+// RT_RAY_FIRST_MAX_K).  q.hits / q.instance_ids: the rows of k; q.any_hit and q.num_primitives are not read.  filter: as above.
+hipError_t launch_ray_first_hits_instanced(const InstanceQuery& q, uint32_t k, const rt_instance_hit_filter* filter,
+                                           uint32_t* status, hipStream_t st);
 
 // tri_overlap_query.hip: rt_tri_overlaps_count / rt_tri_overlaps_collect after their argument checks.  Count runs for
 // num_queries = 0 too (it writes offsets[0] = 0); collect is called with num_queries > 0.  self: RT_TRI_SELF.

@@ -1149,8 +1149,10 @@ int rt_ray_hits_collect(const rt_accel* as, const rt_ray* rays, uint32_t num_ray
  * hits / instance_ids (collect); with num_instances > 0 a null records or blas_table, or num_blas = 0 (blas_table may be null
  * only when num_instances = 0); a TLAS with count > 0 and a null node or leaf pointer, tlas->count > 7; rays / hits / records
  * not 16-byte, offsets / blas_table not 8-byte, instance_ids / counts / status not 4-byte, scratch not 256-byte aligned.
- * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, an indexed form, the host mirror and
- * rt_cli.  (The first-K form is rt_ray_first_hits_instanced, the instanced first-K block below.) */
+ * Hit filters and instance masks: rt_ray_hits_count_instanced_filtered / rt_ray_hits_collect_instanced_filtered, the instanced
+ * set-filter block below.
+ * Out of scope: instance motion, mixed / sphere BLASes, an indexed form, the host mirror and rt_cli.  (The first-K form is
+ * rt_ray_first_hits_instanced, the instanced first-K block below.) */
 int rt_ray_hits_count_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                 const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
                                 uint64_t* offsets, void* scratch, uint64_t* counters, uint32_t* status, void* stream);
@@ -1289,8 +1291,8 @@ int rt_ray_first_hits(const rt_accel* as, const rt_ray* rays, uint32_t num_rays,
  * num_instances > 0 a null records or blas_table, or num_blas = 0 (blas_table may be null only when num_instances = 0); a TLAS
  * with count > 0 and a null node or leaf pointer, tlas->count > 7; k = 0 or k > RT_RAY_FIRST_MAX_K; rays / hits / records not
  * 16-byte, blas_table / counters not 8-byte, instance_ids / status not 4-byte aligned.
- * Out of scope: hit filters and instance masks, instance motion, mixed / sphere BLASes, an indexed form, the host mirror and
- * rt_cli. */
+ * Hit filters and instance masks: rt_ray_first_hits_instanced_filtered, the instanced set-filter block below.
+ * Out of scope: instance motion, mixed / sphere BLASes, an indexed form, the host mirror and rt_cli. */
 int rt_ray_first_hits_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                 const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
                                 uint32_t k, rt_hit* hits, uint32_t* instance_ids,
@@ -1441,8 +1443,8 @@ int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t 
  * other than RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT in filter->flags; per_instance not 8-byte aligned; per_ray not 16-byte
  * aligned.  num_instance_filters > 0 with a null per_instance is fine.  Asynchronous and hipGraph-capturable like the sibling.
  * Out of scope: there is no per-primitive mask in this call -- grouping is per instance --, and the indexed query
- * has no instanced form; the instanced all-hit and first-K queries (rt_ray_hits_collect_instanced, rt_ray_first_hits_instanced)
- * take no filter. */
+ * has no instanced form.  The instanced all-hit and first-K queries take this same filter through entry points of their own
+ * (the instanced set-filter block below). */
 enum { RT_INSTANCE_FILTER_CULL_DISABLE = 1, RT_INSTANCE_FILTER_FLIP_FACING = 2 };
 typedef struct rt_instance_filter {
     uint32_t mask;                        /* im of rule 1 */
@@ -1466,6 +1468,73 @@ int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance
                                          const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
                                          uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
                                          const rt_instance_hit_filter* filter, uint64_t* counters, void* stream);
+
+/* ---- instance filters for the instanced all-hit and first-K ray queries (no reference counterpart): the instanced set-filter
+ * block.  The two set-valued queries of a placed scene need the filter above more than the closest-hit query does: a ray that
+ * leaves a surface must skip the (instance, primitive) it stands on (depth peeling, layered transparency), visibility groups
+ * are instance masks that save the whole BLAS descent, thickness and entry / exit pairing need the WORLD-space facing on
+ * mirrored parts -- and a first-K row computed without the filter cannot be repaired afterwards: a rejected crossing that
+ * entered the list has shrunk the bound and evicted a kept one.
+ *
+ * rt_ray_hits_count_instanced_filtered, rt_ray_hits_collect_instanced_filtered, rt_ray_first_hits_instanced_filtered: each is
+ * its sibling's signature (rt_ray_hits_count_instanced, rt_ray_hits_collect_instanced, rt_ray_first_hits_instanced) with one
+ * more argument, `filter`, before the outputs.  rt_instance_hit_filter, its flag bits, rt_instance_filter and
+ * rt_instance_ray_filter are the instance-filter block's, unchanged; every other argument keeps the type and meaning it has in
+ * the sibling, and all of the sibling's rules carry over.  filter == NULL forwards to the unfiltered sibling.
+ *
+ * Rules 1 and 2 of the instance-filter block apply word for word:
+ * 1. Instance rule.  Asked at the TLAS leaf, for id < num_instances, BEFORE the instance record is read.  An instance that is
+ *    not entered contributes no BLAS box test, no leaf visit and no candidate; neither its record nor its rt_accel is read.
+ *    Its proxy's slab test in the TLAS is still counted.
+ * 2. Candidate rule.  Asked at the leaf test's ONE acceptance point (after the t window test), with det in the header's
+ *    operation order, the BACK / FRONT exchange under flip, CULL_DISABLE, and skip_id only inside skip_instance.  A rejected
+ *    candidate is treated exactly as if Moller-Trumbore had rejected it.
+ *
+ * All-hit.  Let W be the unfiltered instanced all-hit row of the ray.  The filtered row is the multiset of the items of W whose
+ * instance passes rule 1 and whose candidate passes rule 2.  The window never moves, so the row is again a function of the
+ * bytes, the ray and the filter; count and collect are one traversal compiled twice and cannot disagree (under the same
+ * filter).  Fixed-K mode, counts, RT_RAY_HITS_TRUNCATED, the one 64-entry stack and RT_RAY_HITS_STACK_OVERFLOW are the
+ * sibling's.
+ *
+ * First-K.  The instanced first-K block with W read as the FILTERED all-hit row: Ws, E, T1 and the decided rays are defined on
+ * it.  The bound b moves only on kept items: a rejected candidate never enters the list.  Key, list rule, padding, the gate
+ * g(w), the order and the note that a popped TLAS entry is not re-tested are unchanged; a popped entry of a masked instance
+ * fails rule 1 and the lane goes on in the TLAS.  Claims 1-4 hold on the filtered W (DESIGN section 31 has the proofs); claim 4
+ * compares with rt_ray_hits_count_instanced_filtered under the same filter.
+ *
+ * Contracts.
+ *   (a) Keep-all.  A filter that keeps everything -- null arrays with ray_mask all ones and flags 0, or arrays of all-ones
+ *       masks with zero flags and skip_instance = RT_MISS -- gives the unfiltered sibling's offsets, counts, counters[0..1] and
+ *       status byte for byte, and the same items in every row (all-hit) or the same bytes (first-K).
+ *   (b) Composition.  The all-hit row is the union, over the instances rule 1 lets in, of rt_ray_hits_collect_filtered's row on
+ *       the BLAS for the object ray under the effective single-tree filter (the cull bits rule 2 applies to `a`, skip_id inside
+ *       skip_instance, null masks), each record tagged with the instance.
+ *   (c) Closest hit.  The all-hit row holds the (instance, t, u, v) bits of rt_intersect_rays_instanced_filtered's closest-hit
+ *       answer under the same filter; a miss there is an empty row and the other way round.  First-K with k = 1 on a decided
+ *       ray gives a t at most that one.
+ *   (d) Masks.  With masks that admit no instance every row is empty (all-hit) or all pads (first-K), counters[1] adds 0 and
+ *       counters[0] adds exactly the TLAS slots examined.
+ *   (e) One identity instance with no per_instance equals the single-tree filtered sibling (rt_ray_hits_collect_filtered /
+ *       rt_ray_first_hits_filtered) with the same flags and per-ray records {mask, skip_id} for rays whose skip_instance is 0,
+ *       on rays without -0 components, all instances 0.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of the sibling's; a flag bit other than
+ * RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT in filter->flags; per_instance not 8-byte aligned; per_ray not 16-byte aligned.
+ * num_instance_filters > 0 with a null per_instance is fine (an absent array).  Asynchronous and hipGraph-capturable like the
+ * siblings.
+ * Out of scope: per-primitive masks, instance motion, mixed / sphere BLASes, an indexed form, the host mirror and rt_cli. */
+int rt_ray_hits_count_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                         const rt_instance_hit_filter* filter, uint64_t* offsets, void* scratch,
+                                         uint64_t* counters, uint32_t* status, void* stream);
+int rt_ray_hits_collect_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                           const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays,
+                                           uint32_t num_rays, const rt_instance_hit_filter* filter, const uint64_t* offsets,
+                                           rt_hit* hits, uint32_t* instance_ids, uint32_t* counts, uint64_t* counters,
+                                           uint32_t* status, void* stream);
+int rt_ray_first_hits_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                         uint32_t k, const rt_instance_hit_filter* filter, rt_hit* hits, uint32_t* instance_ids,
+                                         uint64_t* counters, uint32_t* status, void* stream);
 
 /* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
  * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
