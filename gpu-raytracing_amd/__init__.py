@@ -251,7 +251,10 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_generate_shadow_rays", "rt_shade_frame", "rt_shade_frame_instanced",
            "rt_ray_hits_count_instanced", "rt_ray_hits_collect_instanced", "rt_ray_first_hits_instanced",
            "rt_ray_hits_count_instanced_filtered", "rt_ray_hits_collect_instanced_filtered",
-           "rt_ray_first_hits_instanced_filtered", "rt_error_string", "rt_version_string"]
+           "rt_ray_first_hits_instanced_filtered",
+           "rt_intersect_rays_instanced_indexed", "rt_intersect_rays_instanced_motion_indexed",
+           "rt_intersect_rays_instanced_mixed_indexed", "rt_intersect_rays_motion_indexed",
+           "rt_error_string", "rt_version_string"]
 
 _lib = None
 
@@ -392,6 +395,17 @@ def lib() -> ctypes.CDLL:
     L.rt_ray_first_hits_instanced_filtered.restype = i32
     L.rt_ray_first_hits_instanced_filtered.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, u32, ifl, vp, vp, vp, vp,
                                                        vp]
+    L.rt_intersect_rays_instanced_indexed.restype = i32
+    L.rt_intersect_rays_instanced_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, u32, vp, u32, vp, u32, vp, vp, i32, u32,
+                                                      ifl, vp, vp]
+    L.rt_intersect_rays_instanced_motion_indexed.restype = i32
+    L.rt_intersect_rays_instanced_motion_indexed.argtypes = [ctypes.POINTER(_MotionAccel), vp, u32, vp, u32, vp, vp, u32, vp, u32,
+                                                             vp, vp, i32, vp, vp]
+    L.rt_intersect_rays_instanced_mixed_indexed.restype = i32
+    L.rt_intersect_rays_instanced_mixed_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp,
+                                                            i32, vp, vp]
+    L.rt_intersect_rays_motion_indexed.restype = i32
+    L.rt_intersect_rays_motion_indexed.argtypes = [ctypes.POINTER(_MotionAccel), vp, vp, u32, vp, u32, vp, i32, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
     L.rt_tri_overlaps_scratch_bytes.argtypes = [u32]
     L.rt_tri_overlaps_count.restype = i32
@@ -1830,6 +1844,98 @@ def IntersectRaysIndexed(triangles, nodes, root: int, count: int, rays, order, h
     _check(lib().rt_intersect_rays_indexed(ctypes.byref(a), _ptr(rays), n, _ptr(order), k, _ptr(hits),
                                            kAnyHit if any_hit else kClosestHit, int(num_primitives), _ptr(counters),
                                            _stream_ptr(stream)), "rt_intersect_rays_indexed")
+
+
+def _indexed_batch(rays, order, num_indices, hits, instance_ids=None, times=None):
+    """(N, K) of an indexed call after the buffer checks its four forms share: N rays, K words of `order` to use"""
+    bufs = [rays, order, hits] + [t for t in (instance_ids, times) if t is not None]
+    if any(not t.is_contiguous() for t in bufs) or _nbytes(rays) % 32:
+        raise ValueError("rays must be a contiguous device buffer of 32-byte records, order / hits / instance_ids / times "
+                         "contiguous device buffers")
+    n = _nbytes(rays) // 32
+    k = _nbytes(order) // 4 if num_indices is None else int(num_indices)
+    if _nbytes(hits) < 16 * n or _nbytes(order) < 4 * k:
+        raise ValueError(f"hits must hold {n} 16-byte records and order {k} words")
+    if instance_ids is not None and _nbytes(instance_ids) < 4 * n:
+        raise ValueError(f"instance_ids must hold {n} words")
+    if times is not None and _nbytes(times) < 4 * n:
+        raise ValueError(f"times must hold {n} floats")
+    return n, k
+
+
+def IntersectRaysInstancedIndexed(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int, blas_table,
+                                  num_blas: int, rays, order, hits, instance_ids, *, num_indices: Optional[int] = None,
+                                  filter=None, any_hit: bool = False, num_primitives: int = 0, counters=None,
+                                  stream=None) -> None:
+    """rt_intersect_rays_instanced_indexed: IntersectRaysInstanced (filter=None) or IntersectRaysInstancedFiltered (an
+    InstanceHitFilter) through an index list, with IntersectRaysIndexed's contract: launch position j (64 consecutive j per
+    wave) traces rays[order[j]] and writes hits[order[j]] and instance_ids[order[j]]; an index >= N is skipped and unlisted
+    records are not written.  The filter's per_ray records go by the ray's index too.  `order`: SortRays's output over the
+    TLAS (nodes, root, count), or any list of the rays still alive; num_indices: how many of its words to use (default: all).
+    Each written record equals the direct call's bit for bit.  Asynchronous on `stream`."""
+    n, k = _indexed_batch(rays, order, num_indices, hits, instance_ids)
+    flt = _instance_filter_ref(filter, n)
+    if n == 0 or k == 0:
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced_indexed(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                     int(num_blas), _ptr(rays), n, _ptr(order), k, _ptr(hits),
+                                                     _ptr(instance_ids), kAnyHit if any_hit else kClosestHit,
+                                                     int(num_primitives), flt, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_indexed")
+
+
+def IntersectRaysInstancedMotionIndexed(tlas_pose0, tlas_pose1, root: int, count: int, records, num_instances: int, blas_table,
+                                        num_blas: int, rays, times, order, hits, instance_ids, *,
+                                        num_indices: Optional[int] = None, any_hit: bool = False, counters=None,
+                                        stream=None) -> None:
+    """rt_intersect_rays_instanced_motion_indexed: IntersectRaysInstancedMotion through an index list (order / num_indices as
+    for IntersectRaysInstancedIndexed); `times` goes by the ray's index like rays, hits and instance_ids."""
+    n, k = _indexed_batch(rays, order, num_indices, hits, instance_ids, times)
+    if num_instances and (not records.is_contiguous() or _nbytes(records) < 128 * int(num_instances)):
+        raise ValueError(f"records must be a contiguous device buffer of {int(num_instances)} 128-byte records")
+    if n == 0 or k == 0:
+        return
+    a = _motion_accel(tlas_pose0, tlas_pose1, root, count)
+    _check(lib().rt_intersect_rays_instanced_motion_indexed(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                            int(num_blas), _ptr(rays), _ptr(times), n, _ptr(order), k,
+                                                            _ptr(hits), _ptr(instance_ids),
+                                                            kAnyHit if any_hit else kClosestHit, _ptr(counters),
+                                                            _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_motion_indexed")
+
+
+def IntersectRaysInstancedMixedIndexed(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int,
+                                       blas_table, geom_table, num_blas: int, rays, order, hits, instance_ids, *,
+                                       num_indices: Optional[int] = None, any_hit: bool = False, counters=None,
+                                       stream=None) -> None:
+    """rt_intersect_rays_instanced_mixed_indexed: IntersectRaysInstancedMixed through an index list (order / num_indices as for
+    IntersectRaysInstancedIndexed).  geom_table=None: IntersectRaysInstancedIndexed with num_primitives = 0 and no filter."""
+    n, k = _indexed_batch(rays, order, num_indices, hits, instance_ids)
+    if geom_table is not None and (not geom_table.is_contiguous() or _nbytes(geom_table) < 16 * int(num_blas)):
+        raise ValueError(f"geom_table must be a contiguous device buffer of {int(num_blas)} 16-byte records")
+    if n == 0 or k == 0:
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced_mixed_indexed(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                           _ptr(geom_table), int(num_blas), _ptr(rays), n, _ptr(order), k,
+                                                           _ptr(hits), _ptr(instance_ids),
+                                                           kAnyHit if any_hit else kClosestHit, _ptr(counters),
+                                                           _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_mixed_indexed")
+
+
+def IntersectRaysMotionIndexed(pose0, pose1, root: int, count: int, rays, times, order, hits, *,
+                               num_indices: Optional[int] = None, any_hit: bool = False, counters=None, stream=None) -> None:
+    """rt_intersect_rays_motion_indexed: IntersectRaysMotion through an index list (order / num_indices as for
+    IntersectRaysIndexed); `times` goes by the ray's index like rays and hits."""
+    n, k = _indexed_batch(rays, order, num_indices, hits, None, times)
+    if n == 0 or k == 0:
+        return
+    a = _motion_accel(pose0, pose1, root, count)
+    _check(lib().rt_intersect_rays_motion_indexed(ctypes.byref(a), _ptr(rays), _ptr(times), n, _ptr(order), k, _ptr(hits),
+                                                  kAnyHit if any_hit else kClosestHit, _ptr(counters), _stream_ptr(stream)),
+           "rt_intersect_rays_motion_indexed")
 
 
 def GenerateShadowRays(rays, hits, num_triangles: int, light, shadow_rays, stream=None) -> int:

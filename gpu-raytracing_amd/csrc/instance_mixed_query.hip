@@ -17,6 +17,8 @@
 #include "rt_launch.hpp"
 #include "rt_instance_mixed_traverse.hpp"
 
+#include <type_traits>
+
 static_assert(sizeof(rt_geometry) == 16 && offsetof(rt_geometry, data) == 0 && offsetof(rt_geometry, count) == 8 &&
               offsetof(rt_geometry, kind) == 12, "rt_geometry: one 16-byte record (data, count, kind)");
 static_assert(rt::kQueryBlock == rt::kTraceWaves * 64, "rt_launch.hpp: one lane per ray, kTraceWaves waves per workgroup");
@@ -25,9 +27,20 @@ namespace rt {
 
 namespace {
 
-template <bool ANY>
+// rt_intersect_rays_instanced_mixed_indexed: the same query through an index list (ray_query.hip's IndexedQueryParams: the
+// plain part's kernarg offsets do not move)
+struct IndexedMixedInstParams : MixedInstParams {
+    const uint32_t* order;
+    uint32_t num_indices;
+};
+
+// INDEXED only changes how the lane's ray index i is obtained: the launch position itself, or order[position] (positions
+// past num_indices and indices >= num_rays: no ray, nothing written).  rays, hits, instance_ids and the reload of the world
+// ray (trace_instanced_mixed's ri) are indexed by i.  The choice stands HERE, under `if constexpr`, not in a helper function
+// (DESIGN sections 20 and 32).
+template <bool ANY, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_INSTANCE_MIXED_WAVES)
-void mixed_instance_query_kernel(MixedInstParams p)
+void mixed_instance_query_kernel(std::conditional_t<INDEXED, IndexedMixedInstParams, MixedInstParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
@@ -37,7 +50,8 @@ void mixed_instance_query_kernel(MixedInstParams p)
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    if constexpr (INDEXED) i = i < p.num_indices ? p.order[i] : 0xFFFFFFFFull;   // (num_rays is a uint32: never in range)
     const bool in_range = i < p.num_rays;
 
     Ray r;
@@ -100,7 +114,7 @@ void mixed_instance_query_kernel(MixedInstParams p)
 
 hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, hipStream_t st)
 {
-    MixedInstParams p;
+    IndexedMixedInstParams p;
     p.tlas_nodes = q.tlas.nodes;
     p.tlas_leaves = q.tlas.triangles;
     p.root = q.tlas.root;
@@ -115,9 +129,16 @@ hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry
     p.instance_ids = q.instance_ids;
     p.num_rays = q.num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(q.counters);
-    const dim3 grid(query_blocks(q.num_rays)), block(kQueryBlock);
-    if (q.any_hit) mixed_instance_query_kernel<true><<<grid, block, 0, st>>>(p);
-    else mixed_instance_query_kernel<false><<<grid, block, 0, st>>>(p);
+    p.order = q.order;
+    p.num_indices = q.num_indices;
+    const dim3 grid(query_blocks(q.order ? q.num_indices : q.num_rays)), block(kQueryBlock);
+    if (q.order) {
+        if (q.any_hit) mixed_instance_query_kernel<true, true><<<grid, block, 0, st>>>(p);
+        else mixed_instance_query_kernel<false, true><<<grid, block, 0, st>>>(p);
+    } else {
+        if (q.any_hit) mixed_instance_query_kernel<true, false><<<grid, block, 0, st>>>(p);   // (its MixedInstParams part)
+        else mixed_instance_query_kernel<false, false><<<grid, block, 0, st>>>(p);
+    }
     return hipGetLastError();
 }
 

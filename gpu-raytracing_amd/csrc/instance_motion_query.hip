@@ -21,6 +21,8 @@
 #include "rt_instance_motion_traverse.hpp"
 #include "rt_instance_proxy.hpp"
 
+#include <type_traits>
+
 static_assert(sizeof(rt_motion_instance) == 128 && offsetof(rt_motion_instance, object_to_world1) == 48 &&
               offsetof(rt_motion_instance, blas) == 96, "rt_motion_instance: two 3x4 matrices, blas, 7 pads");
 static_assert(sizeof(rt_motion_instance_record) == 128 && offsetof(rt_motion_instance_record, object_to_world1) == 48 &&
@@ -86,9 +88,22 @@ __global__ __launch_bounds__(256) void prepare_motion_instances_kernel(const rt_
 }  // namespace
 
 // ---------------------------------------------------------------- query (the two-level loop: rt_instance_motion_traverse.hpp)
-template <bool ANY>
+// rt_intersect_rays_instanced_motion_indexed: the same query through an index list (ray_query.hip's IndexedQueryParams: the
+// plain part's kernarg offsets do not move)
+namespace {   // (beside its base: rt_instance_motion_traverse.hpp keeps InstMotionParams in the anonymous namespace)
+struct IndexedInstMotionParams : InstMotionParams {
+    const uint32_t* order;
+    uint32_t num_indices;
+};
+}  // namespace
+
+// INDEXED only changes how the lane's ray index i is obtained: the launch position itself, or order[position] (positions
+// past num_indices and indices >= num_rays: no ray, nothing written).  rays, times, hits, instance_ids and the reload of
+// the world ray (trace_instanced_motion's ri) are indexed by i.  The choice stands HERE, under `if constexpr`, not in a
+// helper function (DESIGN sections 20 and 32).
+template <bool ANY, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_INSTANCE_MOTION_WAVES)
-void instance_motion_query_kernel(InstMotionParams p)
+void instance_motion_query_kernel(std::conditional_t<INDEXED, IndexedInstMotionParams, InstMotionParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
@@ -98,7 +113,8 @@ void instance_motion_query_kernel(InstMotionParams p)
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    if constexpr (INDEXED) i = i < p.num_indices ? p.order[i] : 0xFFFFFFFFull;   // (num_rays is a uint32: never in range)
     const bool in_range = i < p.num_rays;
 
     Ray r;
@@ -170,10 +186,11 @@ hipError_t launch_prepare_motion_instances(const rt_motion_instance* instances, 
 
 hipError_t launch_instance_motion_query(const rt_motion_accel& tlas, const rt_motion_instance_record* records,
                                         uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays,
-                                        const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool any_hit,
-                                        uint64_t* counters, hipStream_t st)
+                                        const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays,
+                                        const uint32_t* order, uint32_t num_indices, bool any_hit, uint64_t* counters,
+                                        hipStream_t st)
 {
-    InstMotionParams p;
+    IndexedInstMotionParams p;
     p.tlas_nodes0 = tlas.nodes0;
     p.tlas_leaves0 = tlas.triangles0;
     p.tlas_nodes1 = tlas.nodes1;
@@ -189,9 +206,16 @@ hipError_t launch_instance_motion_query(const rt_motion_accel& tlas, const rt_mo
     p.instance_ids = instance_ids;
     p.num_rays = num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    const dim3 grid(query_blocks(num_rays)), block(kQueryBlock);
-    if (any_hit) instance_motion_query_kernel<true><<<grid, block, 0, st>>>(p);
-    else instance_motion_query_kernel<false><<<grid, block, 0, st>>>(p);
+    p.order = order;
+    p.num_indices = num_indices;
+    const dim3 grid(query_blocks(order ? num_indices : num_rays)), block(kQueryBlock);
+    if (order) {
+        if (any_hit) instance_motion_query_kernel<true, true><<<grid, block, 0, st>>>(p);
+        else instance_motion_query_kernel<false, true><<<grid, block, 0, st>>>(p);
+    } else {
+        if (any_hit) instance_motion_query_kernel<true, false><<<grid, block, 0, st>>>(p);   // (its InstMotionParams part)
+        else instance_motion_query_kernel<false, false><<<grid, block, 0, st>>>(p);
+    }
     return hipGetLastError();
 }
 

@@ -4,7 +4,7 @@
 // prepare_instances_kernel, one thread per instance: the world box of the BLAS's root run through object_to_world, the
 // padded box as a proxy triangle (the TLAS build input), world_to_object in double.
 //
-// instance_query_kernel<PF, ANY, FILTERED>: rt_traverse.hpp's wave-level two-phase loop with a second level (trace_instanced,
+// instance_query_kernel<PF, ANY, FILTERED, INDEXED>: rt_traverse.hpp's wave-level two-phase loop with a second level (trace_instanced,
 // rt_instance_traverse.hpp).  One lane per ray, the
 // launch geometry, LDS stack, XCD remap and counters of ray_query_kernel.  What the second level adds to a lane:
 //   * per-lane node / leaf base pointers: the lanes of one wave sit in different BLASes (and in the TLAS);
@@ -30,6 +30,9 @@
 //     wave-uniform) and the effective skip id;
 //   * leaf test: that per-instance part goes by value to intersect_tri, which asks it after the t window test and before
 //     r.tmax = t -- a rejected candidate shrinks no window and ends no any-hit ray.
+// INDEXED (rt_intersect_rays_instanced_indexed; rt_abi.h, indexed-instanced block) only changes how the
+// lane's ray index is obtained -- order[launch position] -- and so the grid; the ray, its filter record, its two output
+// records and the reload of the world ray in PH_EXIT all go by that index.  It combines with FILTERED.
 // Compiled with -ffp-contract=off: every float operation is the documented one.
 #include "rt_device.hpp"
 #include "rt_launch.hpp"
@@ -113,10 +116,22 @@ struct FilteredInstParams : InstParams {
     InstanceFilterParams filter;
 };
 
-// ray setup, the two-level traversal, the record and instance id of the hit, the per-workgroup counters
-template <bool PF, bool ANY, bool FILTERED>
+// the index list of the INDEXED arms, appended to either struct (ray_query.hip's IndexedQueryParams: the kernarg offsets of
+// the part in front do not move)
+template <class Base> struct IndexedParams : Base {
+    const uint32_t* order;
+    uint32_t num_indices;
+};
+
+// ray setup, the two-level traversal, the record and instance id of the hit, the per-workgroup counters.
+// INDEXED only changes how the lane's ray index i is obtained: the launch position itself, or order[position] (positions
+// past num_indices and indices >= num_rays: no ray, nothing written).  The choice stands HERE, under `if constexpr`, not in
+// a helper function (DESIGN sections 20 and 32).
+template <bool PF, bool ANY, bool FILTERED, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_INSTANCE_QUERY_WAVES)
-void instance_query_kernel(std::conditional_t<FILTERED, FilteredInstParams, InstParams> p)
+void instance_query_kernel(std::conditional_t<INDEXED,
+                                              IndexedParams<std::conditional_t<FILTERED, FilteredInstParams, InstParams>>,
+                                              std::conditional_t<FILTERED, FilteredInstParams, InstParams>> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
@@ -126,7 +141,8 @@ void instance_query_kernel(std::conditional_t<FILTERED, FilteredInstParams, Inst
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    if constexpr (INDEXED) i = i < p.num_indices ? p.order[i] : 0xFFFFFFFFull;   // (num_rays is a uint32: never in range)
     const bool in_range = i < p.num_rays;
 
     Ray r;
@@ -213,10 +229,25 @@ hipError_t launch_instance_query(const InstanceQuery& q, const rt_instance_hit_f
     p.num_rays = q.num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(q.counters);
     if (filter) p.filter = instance_filter_params(*filter);
-    const dim3 grid(query_blocks(q.num_rays)), block(kQueryBlock);
+    const dim3 grid(query_blocks(q.order ? q.num_indices : q.num_rays)), block(kQueryBlock);
+    if (q.order) {
+        // the index list goes behind the struct the launched arm takes: one copy of that part of p
+        auto indexed = [&](const auto& base) {
+            IndexedParams<std::decay_t<decltype(base)>> pi;
+            static_cast<std::decay_t<decltype(base)>&>(pi) = base;
+            pi.order = q.order;
+            pi.num_indices = q.num_indices;
+            return pi;
+        };
+        dispatch_pf_any(q.num_primitives >= kPrefetchMinPrims, q.any_hit, [&](auto pf, auto any) {
+            if (filter) instance_query_kernel<pf(), any(), true, true><<<grid, block, 0, st>>>(indexed(p));
+            else instance_query_kernel<pf(), any(), false, true><<<grid, block, 0, st>>>(indexed(static_cast<const InstParams&>(p)));
+        });
+        return hipGetLastError();
+    }
     dispatch_pf_any(q.num_primitives >= kPrefetchMinPrims, q.any_hit, [&](auto pf, auto any) {
-        if (filter) instance_query_kernel<pf(), any(), true><<<grid, block, 0, st>>>(p);
-        else instance_query_kernel<pf(), any(), false><<<grid, block, 0, st>>>(p);   // (its InstParams part)
+        if (filter) instance_query_kernel<pf(), any(), true, false><<<grid, block, 0, st>>>(p);
+        else instance_query_kernel<pf(), any(), false, false><<<grid, block, 0, st>>>(p);   // (its InstParams part)
     });
     return hipGetLastError();
 }

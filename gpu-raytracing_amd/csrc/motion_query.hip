@@ -19,11 +19,25 @@
 #include "rt_launch.hpp"
 #include "rt_motion_traverse.hpp"
 
+#include <type_traits>
+
 namespace rt {
 
-template <bool ANY>
+// rt_intersect_rays_motion_indexed: the same query through an index list (ray_query.hip's IndexedQueryParams: the plain
+// part's kernarg offsets do not move)
+namespace {   // (beside its base: rt_motion_traverse.hpp keeps MotionParams in the anonymous namespace)
+struct IndexedMotionParams : MotionParams {
+    const uint32_t* order;
+    uint32_t num_indices;
+};
+}  // namespace
+
+// INDEXED only changes how the lane's ray index i is obtained: the launch position itself, or order[position] (positions
+// past num_indices and indices >= num_rays: no ray, nothing written).  rays, times and hits are indexed by i.  The choice
+// stands HERE, under `if constexpr`, not in a helper function (DESIGN sections 20 and 32).
+template <bool ANY, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_MOTION_WAVES)
-void motion_query_kernel(MotionParams p)
+void motion_query_kernel(std::conditional_t<INDEXED, IndexedMotionParams, MotionParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
     __shared__ unsigned long long csum[4];
@@ -33,7 +47,8 @@ void motion_query_kernel(MotionParams p)
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    uint64_t i = ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane;
+    if constexpr (INDEXED) i = i < p.num_indices ? p.order[i] : 0xFFFFFFFFull;   // (num_rays is a uint32: never in range)
     const bool in_range = i < p.num_rays;
 
     float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, -1.f};
@@ -103,9 +118,9 @@ __global__ __launch_bounds__(256) void motion_validate_kernel(const uint4* nodes
 static_assert(kQueryBlock == kTraceWaves * 64, "rt_launch.hpp: one lane per ray, kTraceWaves waves per workgroup");
 
 hipError_t launch_motion_query(const rt_motion_accel& as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
-                               bool any_hit, uint64_t* counters, hipStream_t st)
+                               const uint32_t* order, uint32_t num_indices, bool any_hit, uint64_t* counters, hipStream_t st)
 {
-    MotionParams p;
+    IndexedMotionParams p;
     p.nodes0 = as.nodes0;
     p.leaves0 = as.triangles0;
     p.nodes1 = as.nodes1;
@@ -117,9 +132,16 @@ hipError_t launch_motion_query(const rt_motion_accel& as, const rt_ray* rays, co
     p.hits = reinterpret_cast<float4*>(hits);
     p.num_rays = num_rays;
     p.counters = reinterpret_cast<unsigned long long*>(counters);
-    const dim3 grid(query_blocks(num_rays)), block(kQueryBlock);
-    if (any_hit) motion_query_kernel<true><<<grid, block, 0, st>>>(p);
-    else motion_query_kernel<false><<<grid, block, 0, st>>>(p);
+    p.order = order;
+    p.num_indices = num_indices;
+    const dim3 grid(query_blocks(order ? num_indices : num_rays)), block(kQueryBlock);
+    if (order) {
+        if (any_hit) motion_query_kernel<true, true><<<grid, block, 0, st>>>(p);
+        else motion_query_kernel<false, true><<<grid, block, 0, st>>>(p);
+    } else {
+        if (any_hit) motion_query_kernel<true, false><<<grid, block, 0, st>>>(p);   // (its MotionParams part)
+        else motion_query_kernel<false, false><<<grid, block, 0, st>>>(p);
+    }
     return hipGetLastError();
 }
 

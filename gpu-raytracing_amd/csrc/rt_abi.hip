@@ -409,15 +409,33 @@ int rt_motion_validate(const rt_motion_accel* as, uint32_t num_triangles, uint32
     return hip_rc(launch_motion_validate(*as, num_triangles, status, static_cast<hipStream_t>(stream)));
 }
 
+// The indexed form of a ray query is its sibling with an index list: one set of checks per family, `indexed` adds the
+// list's own (non-null, 4-byte aligned) and an empty list is an empty call.  A launch function given no list runs the
+// sibling's instantiation of its kernel.
+static inline bool order_args(bool indexed, const uint32_t* order) { return !indexed || (order && !misaligned(order, 4)); }
+
+static int motion_query(const rt_motion_accel* as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
+                        bool indexed, const uint32_t* order, uint32_t num_indices, int mode, uint64_t* counters, void* stream)
+{
+    if (!motion_tree_args(as) || !rays || !times || !hits || !order_args(indexed, order)) return RT_ERR_INVALID_ARGUMENT;
+    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
+    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(times, 4)) return RT_ERR_INVALID_ARGUMENT;
+    if (num_rays == 0 || (indexed && num_indices == 0)) return RT_OK;
+    return hip_rc(launch_motion_query(*as, rays, times, hits, num_rays, indexed ? order : nullptr, num_indices,
+                                      mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
+}
+
 int rt_intersect_rays_motion(const rt_motion_accel* as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
                              int mode, uint64_t* counters, void* stream)
 {
-    if (!motion_tree_args(as) || !rays || !times || !hits) return RT_ERR_INVALID_ARGUMENT;
-    if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
-    if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(times, 4)) return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
-    return hip_rc(launch_motion_query(*as, rays, times, hits, num_rays, mode == RT_RAY_ANY_HIT, counters,
-                                      static_cast<hipStream_t>(stream)));
+    return motion_query(as, rays, times, hits, num_rays, false, nullptr, 0, mode, counters, stream);
+}
+
+int rt_intersect_rays_motion_indexed(const rt_motion_accel* as, const rt_ray* rays, const float* times, uint32_t num_rays,
+                                     const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode, uint64_t* counters,
+                                     void* stream)
+{
+    return motion_query(as, rays, times, hits, num_rays, true, order, num_indices, mode, counters, stream);
 }
 
 int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
@@ -436,12 +454,13 @@ int rt_prepare_instances(const rt_instance* instances, uint32_t num_instances, c
 static_assert(sizeof(rt_instance_filter) == 8 && sizeof(rt_instance_ray_filter) == 16 && sizeof(rt_instance_hit_filter) == 32,
               "rt_abi.h: the instance filter records' sizes");
 
-int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
-                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
-                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
-                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream)
+static int instanced_query(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                           const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                           uint32_t* instance_ids, uint32_t num_rays, bool indexed, const uint32_t* order, uint32_t num_indices,
+                           int mode, uint32_t num_primitives, const rt_instance_hit_filter* filter, uint64_t* counters,
+                           void* stream)
 {
-    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids || !order_args(indexed, order)) return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
@@ -451,7 +470,7 @@ int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance
     if (filter && ((filter->flags & ~(uint32_t)(RT_FILTER_CULL_BACK | RT_FILTER_CULL_FRONT)) ||
                    misaligned(filter->per_instance, 8) || misaligned(filter->per_ray, 16)))
         return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
+    if (num_rays == 0 || (indexed && num_indices == 0)) return RT_OK;
     InstanceQuery q;
     q.tlas = *tlas;
     q.records = records;
@@ -465,7 +484,28 @@ int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance
     q.any_hit = mode == RT_RAY_ANY_HIT;
     q.num_primitives = num_primitives;
     q.counters = counters;
+    q.order = indexed ? order : nullptr;
+    q.num_indices = num_indices;
     return hip_rc(launch_instance_query(q, filter, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced_filtered(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                         const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, rt_hit* hits,
+                                         uint32_t* instance_ids, uint32_t num_rays, int mode, uint32_t num_primitives,
+                                         const rt_instance_hit_filter* filter, uint64_t* counters, void* stream)
+{
+    return instanced_query(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays, false, nullptr,
+                           0, mode, num_primitives, filter, counters, stream);
+}
+
+int rt_intersect_rays_instanced_indexed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                        const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                        const uint32_t* order, uint32_t num_indices, rt_hit* hits, uint32_t* instance_ids,
+                                        int mode, uint32_t num_primitives, const rt_instance_hit_filter* filter,
+                                        uint64_t* counters, void* stream)
+{
+    return instanced_query(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays, true, order,
+                           num_indices, mode, num_primitives, filter, counters, stream);
 }
 
 int rt_intersect_rays_instanced(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
@@ -492,21 +532,41 @@ int rt_prepare_motion_instances(const rt_motion_instance* instances, uint32_t nu
                                                   status, static_cast<hipStream_t>(stream)));
 }
 
-int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
-                                       uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
-                                       const rt_ray* rays, const float* times, rt_hit* hits, uint32_t* instance_ids,
-                                       uint32_t num_rays, int mode, uint64_t* counters, void* stream)
+static int instanced_motion_query(const rt_motion_accel* tlas, const rt_motion_instance_record* records, uint32_t num_instances,
+                                  const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, const float* times,
+                                  rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool indexed, const uint32_t* order,
+                                  uint32_t num_indices, int mode, uint64_t* counters, void* stream)
 {
-    if (!motion_tree_args(tlas) || !rays || !times || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+    if (!motion_tree_args(tlas) || !rays || !times || !hits || !instance_ids || !order_args(indexed, order))
+        return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(times, 4) || misaligned(instance_ids, 4) ||
         misaligned(records, 16) || misaligned(blas_table, 8))
         return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
+    if (num_rays == 0 || (indexed && num_indices == 0)) return RT_OK;
     return hip_rc(launch_instance_motion_query(*tlas, records, num_instances, blas_table, num_blas, rays, times, hits,
-                                               instance_ids, num_rays, mode == RT_RAY_ANY_HIT, counters,
-                                               static_cast<hipStream_t>(stream)));
+                                               instance_ids, num_rays, indexed ? order : nullptr, num_indices,
+                                               mode == RT_RAY_ANY_HIT, counters, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced_motion(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
+                                       uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                                       const rt_ray* rays, const float* times, rt_hit* hits, uint32_t* instance_ids,
+                                       uint32_t num_rays, int mode, uint64_t* counters, void* stream)
+{
+    return instanced_motion_query(tlas, records, num_instances, blas_table, num_blas, rays, times, hits, instance_ids, num_rays,
+                                  false, nullptr, 0, mode, counters, stream);
+}
+
+int rt_intersect_rays_instanced_motion_indexed(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
+                                               uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                                               const rt_ray* rays, const float* times, uint32_t num_rays, const uint32_t* order,
+                                               uint32_t num_indices, rt_hit* hits, uint32_t* instance_ids, int mode,
+                                               uint64_t* counters, void* stream)
+{
+    return instanced_motion_query(tlas, records, num_instances, blas_table, num_blas, rays, times, hits, instance_ids, num_rays,
+                                  true, order, num_indices, mode, counters, stream);
 }
 
 static_assert(sizeof(rt_sphere) == 16, "rt_abi.h: rt_sphere is one 16-byte record");
@@ -580,22 +640,22 @@ int rt_sphere_cast(const rt_accel* as, const rt_ray* rays, const float* radii, f
 
 static_assert(sizeof(rt_geometry) == 16, "rt_abi.h: rt_geometry is one 16-byte record");
 
-int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
-                                      const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
-                                      const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, int mode,
-                                      uint64_t* counters, void* stream)
+static int instanced_mixed_query(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                 const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                 const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool indexed,
+                                 const uint32_t* order, uint32_t num_indices, int mode, uint64_t* counters, void* stream)
 {
     // no table: every BLAS holds triangles (the sibling, without the pair-prefetch arm)
     if (!geom_table)
-        return rt_intersect_rays_instanced(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays,
-                                           mode, 0u, counters, stream);
-    if (!tree_args(tlas) || !rays || !hits || !instance_ids) return RT_ERR_INVALID_ARGUMENT;
+        return instanced_query(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays, indexed,
+                               order, num_indices, mode, 0u, nullptr, counters, stream);
+    if (!tree_args(tlas) || !rays || !hits || !instance_ids || !order_args(indexed, order)) return RT_ERR_INVALID_ARGUMENT;
     if (num_instances && (!records || !blas_table || num_blas == 0)) return RT_ERR_INVALID_ARGUMENT;
     if (mode != RT_RAY_CLOSEST_HIT && mode != RT_RAY_ANY_HIT) return RT_ERR_INVALID_ARGUMENT;
     if (misaligned(rays, 16) || misaligned(hits, 16) || misaligned(instance_ids, 4) || misaligned(records, 16) ||
         misaligned(blas_table, 8) || misaligned(geom_table, 16))
         return RT_ERR_INVALID_ARGUMENT;
-    if (num_rays == 0) return RT_OK;
+    if (num_rays == 0 || (indexed && num_indices == 0)) return RT_OK;
     InstanceQuery q;
     q.tlas = *tlas;
     q.records = records;
@@ -609,7 +669,27 @@ int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_re
     q.any_hit = mode == RT_RAY_ANY_HIT;
     q.num_primitives = 0;
     q.counters = counters;
+    q.order = indexed ? order : nullptr;
+    q.num_indices = num_indices;
     return hip_rc(launch_instance_mixed_query(q, geom_table, static_cast<hipStream_t>(stream)));
+}
+
+int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                      const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                      const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, int mode,
+                                      uint64_t* counters, void* stream)
+{
+    return instanced_mixed_query(tlas, records, num_instances, blas_table, geom_table, num_blas, rays, hits, instance_ids,
+                                 num_rays, false, nullptr, 0, mode, counters, stream);
+}
+
+int rt_intersect_rays_instanced_mixed_indexed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                              const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                              const rt_ray* rays, uint32_t num_rays, const uint32_t* order, uint32_t num_indices,
+                                              rt_hit* hits, uint32_t* instance_ids, int mode, uint64_t* counters, void* stream)
+{
+    return instanced_mixed_query(tlas, records, num_instances, blas_table, geom_table, num_blas, rays, hits, instance_ids,
+                                 num_rays, true, order, num_indices, mode, counters, stream);
 }
 
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
@@ -1085,7 +1165,11 @@ const char* rt_version_string(void)
            "instance_set_filter: the instanced all-hit and first-K queries with the instanced query's filter (instance mask "
            "asked at the TLAS leaf before the record is read, world-space face culling, a per-ray (instance, primitive) skip) "
            "as a FILTERED template arm of the siblings' kernels, a rejected crossing never enters the first-K list or moves "
-           "its bound";
+           "its bound | "
+           "instance_indexed: the instanced (plain and filtered), instanced-motion, mixed-instanced and motion ray queries "
+           "through an index list as an INDEXED template arm of the siblings' kernels (lane j takes ray order[j]; rays, times, "
+           "per-ray filter records, hits and instance ids go by the ray index), the sorted order of rt_sort_rays over the TLAS "
+           "or any list of live rays";
 }
 
 }  // extern "C"

@@ -218,21 +218,23 @@ hipError_t launch_ray_query_indexed(const rt_accel& as, const rt_ray* rays, uint
                                     uint32_t num_indices, rt_hit* hits, bool any_hit, uint32_t num_primitives,
                                     uint64_t* counters, hipStream_t st);
 
-// motion_query.hip: rt_intersect_rays_motion (num_rays > 0) / rt_motion_validate after their argument checks
+// motion_query.hip: rt_intersect_rays_motion[_indexed] (num_rays > 0) / rt_motion_validate after their argument checks
+// order == null: lane j takes ray j; else (rt_intersect_rays_motion_indexed, num_indices > 0) lane j takes ray order[j]
 hipError_t launch_motion_query(const rt_motion_accel& as, const rt_ray* rays, const float* times, rt_hit* hits, uint32_t num_rays,
-                               bool any_hit, uint64_t* counters, hipStream_t st);
+                               const uint32_t* order, uint32_t num_indices, bool any_hit, uint64_t* counters, hipStream_t st);
 hipError_t launch_motion_validate(const rt_motion_accel& as, uint32_t num_triangles, uint32_t* status, hipStream_t st);
 
-// instance_motion_query.hip: rt_prepare_motion_instances / rt_intersect_rays_instanced_motion (num_rays > 0) after their
-// argument checks
+// instance_motion_query.hip: rt_prepare_motion_instances / rt_intersect_rays_instanced_motion[_indexed] (num_rays > 0) after
+// their argument checks (order: as launch_motion_query's)
 hipError_t launch_prepare_motion_instances(const rt_motion_instance* instances, uint32_t num_instances,
                                            const rt_accel* blas_table, uint32_t num_blas, rt_triangle* proxies0,
                                            rt_triangle* proxies1, rt_motion_instance_record* records, uint32_t* status,
                                            hipStream_t st);
 hipError_t launch_instance_motion_query(const rt_motion_accel& tlas, const rt_motion_instance_record* records,
                                         uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays,
-                                        const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool any_hit,
-                                        uint64_t* counters, hipStream_t st);
+                                        const float* times, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays,
+                                        const uint32_t* order, uint32_t num_indices, bool any_hit, uint64_t* counters,
+                                        hipStream_t st);
 
 // sphere_query.hip: rt_prepare_spheres / rt_intersect_rays_spheres after their argument checks (the query: a launch of at
 // least one lane; order == null: lane j takes ray j)
@@ -321,8 +323,8 @@ struct ShadeInstancedLaunch {
 };
 hipError_t launch_shade_frame_instanced(const ShadeInstancedLaunch& t, hipStream_t st);
 
-// instances.hip: rt_prepare_instances / rt_intersect_rays_instanced[_filtered] after their argument checks (the query:
-// num_rays > 0)
+// instances.hip: rt_prepare_instances / rt_intersect_rays_instanced[_filtered | _indexed] after their argument checks (the
+// query: num_rays > 0)
 hipError_t launch_prepare_instances(const rt_instance* instances, uint32_t num_instances, const rt_accel* blas_table,
                                     uint32_t num_blas, rt_triangle* proxies, rt_instance_record* records, uint32_t* status,
                                     hipStream_t st);
@@ -339,9 +341,13 @@ struct InstanceQuery {
     bool any_hit;
     uint32_t num_primitives;
     uint64_t* counters;
+    // the index list of rt_intersect_rays_instanced_indexed / _mixed_indexed (num_indices > 0); null: lane j takes ray j.
+    // The set-valued launches do not read it.
+    const uint32_t* order = nullptr;
+    uint32_t num_indices = 0;
 };
 hipError_t launch_instance_query(const InstanceQuery& q, const rt_instance_hit_filter* filter, hipStream_t st);
-// instance_mixed_query.hip: rt_intersect_rays_instanced_mixed after its argument checks (num_rays > 0, geom_table non-null;
+// instance_mixed_query.hip: rt_intersect_rays_instanced_mixed[_indexed] after its argument checks (num_rays > 0, geom_table non-null;
 // q.num_primitives is not read: no pair-prefetch arm)
 hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, hipStream_t st);
 

@@ -358,7 +358,8 @@ int rt_refit(const rt_build_input* input, uint32_t root, uint32_t count, void* p
  * Argument errors: RT_ERR_INVALID_ARGUMENT for a null as / status, a null tree pointer with count > 0, count > 7, a status not
  * 4-byte or a tree pointer not 16-byte aligned; RT_ERR_TOO_LARGE for num_triangles > RT_REFIT_MAX_TRIANGLES.
  *
- * Out of scope: more than two key poses (motion of instance transforms: the instance-motion block below); filtered, indexed, all-hit and first-K motion forms;
+ * Out of scope: more than two key poses (motion of instance transforms: the instance-motion block below); filtered, all-hit
+ * and first-K motion forms (the indexed form: rt_intersect_rays_motion_indexed, the indexed-instanced block below);
  * the pair-prefetch traversal; shading of motion hits; the C++ host mirror and rt_cli. */
 typedef struct rt_motion_accel {
     const rt_triangle_pair* triangles0; const rt_node* nodes0;   /* key pose at time 0 */
@@ -773,8 +774,9 @@ int rt_sphere_cast(const rt_accel* as, const rt_ray* rays, const float* radii, f
  * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): rt_intersect_rays_instanced's, and geom_table not
  * 16-byte aligned.  Errors win over num_rays = 0, which runs nothing.
  *
- * Out of scope: filtered, motion, indexed, all-hit and first-K mixed forms; triangles and spheres inside one BLAS; the C++ host
- * mirror and rt_cli. */
+ * Out of scope: filtered, motion, indexed, all-hit and first-K mixed forms of THIS call (the indexed one is an entry point of its
+ * own, rt_intersect_rays_instanced_mixed_indexed: the indexed-instanced block below); triangles and spheres inside one BLAS; the
+ * C++ host mirror and rt_cli. */
 enum { RT_GEOM_TRIANGLES = 0, RT_GEOM_SPHERES = 1 };
 typedef struct rt_geometry {      /* 16 bytes; DEVICE array parallel to the BLAS table */
     const void* data;             /* RT_GEOM_SPHERES: const rt_sphere*, 16-byte aligned (caller's duty); TRIANGLES: not read */
@@ -1442,8 +1444,8 @@ int rt_ray_first_hits_filtered(const rt_accel* as, const rt_ray* rays, uint32_t 
  * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of rt_intersect_rays_instanced's; a flag bit
  * other than RT_FILTER_CULL_BACK / RT_FILTER_CULL_FRONT in filter->flags; per_instance not 8-byte aligned; per_ray not 16-byte
  * aligned.  num_instance_filters > 0 with a null per_instance is fine.  Asynchronous and hipGraph-capturable like the sibling.
- * Out of scope: there is no per-primitive mask in this call -- grouping is per instance --, and the indexed query
- * has no instanced form.  The instanced all-hit and first-K queries take this same filter through entry points of their own
+ * Out of scope: there is no per-primitive mask in this call -- grouping is per instance.  The indexed form of this call is
+ * rt_intersect_rays_instanced_indexed with the same filter (the indexed-instanced block below).  The instanced all-hit and first-K queries take this same filter through entry points of their own
  * (the instanced set-filter block below). */
 enum { RT_INSTANCE_FILTER_CULL_DISABLE = 1, RT_INSTANCE_FILTER_FLIP_FACING = 2 };
 typedef struct rt_instance_filter {
@@ -1535,6 +1537,53 @@ int rt_ray_first_hits_instanced_filtered(const rt_accel* tlas, const rt_instance
                                          const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
                                          uint32_t k, const rt_instance_hit_filter* filter, rt_hit* hits, uint32_t* instance_ids,
                                          uint64_t* counters, uint32_t* status, void* stream);
+
+/* ---- indexed forms of the instanced and motion ray queries (no reference counterpart): the indexed-instanced block.
+ * rt_sort_rays takes a TLAS as its tree, and secondary rays over a placed scene are the least coherent batches there are (the
+ * lanes of one wave sit in different BLASes).  These four calls are their siblings through an index list, with exactly
+ * rt_intersect_rays_indexed's contract, so a sorted order or a list of the rays still alive is traced without moving a
+ * 32-byte ray record, a hit record or an instance id:
+ *   rt_intersect_rays_instanced_indexed          sibling: rt_intersect_rays_instanced (filter == NULL) or
+ *                                                rt_intersect_rays_instanced_filtered (any other filter) -- one entry point
+ *                                                serves both, there is no separate filtered-indexed symbol
+ *   rt_intersect_rays_instanced_motion_indexed   sibling: rt_intersect_rays_instanced_motion
+ *   rt_intersect_rays_instanced_mixed_indexed    sibling: rt_intersect_rays_instanced_mixed (a null geom_table forwards to
+ *                                                rt_intersect_rays_instanced_indexed as the sibling forwards to its own)
+ *   rt_intersect_rays_motion_indexed             sibling: rt_intersect_rays_motion
+ * The arguments are the sibling's in the sibling's order, with (order, num_indices) after num_rays and the output arrays
+ * behind them, as in rt_intersect_rays_indexed.
+ *   Index choice.  Lane j of the launch (j < num_indices, 64 consecutive j per wave) takes i = order[j].  If i >= num_rays
+ *   (0xFFFFFFFF for instance) the lane does nothing.  The grid is sized by num_indices, which may exceed num_rays.
+ *   Indexed by ray index.  Everything per ray goes by i, never by j: rays[i], times[i], filter->per_ray[i], hits[i],
+ *   instance_ids[i], and the reload of the world ray when a lane leaves an instance.
+ *   Written records.  For any index list each written hits[i] / instance_ids[i] equals the sibling's bytes (a ray's result
+ *   does not depend on its wave neighbours; the kernel body after the choice of i is the sibling's).  Records whose index
+ *   is not listed are not written, in neither array; a duplicated index writes the same bytes twice.
+ *   Counters.  When order is a permutation counters[0] and [1] equal the sibling's; with the identity list all four do;
+ *   [2] / [3] (wave steps) depend on the order: they measure its coherence.
+ *   Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): all of the sibling's, plus a null order or one
+ *   not 4-byte aligned.  num_indices = 0 (like num_rays = 0) runs nothing; errors win over both.
+ *   Asynchronous: no host copy, no synchronisation, one launch -- hipGraph-capturable on one stream, behind rt_sort_rays.
+ * Out of scope: indexed forms of the set-valued queries (all-hit and first-K, flat or instanced: their row / CSR layout by ray
+ * index is a design of its own); a sort key that knows about instances (rt_sort_rays sees the TLAS root box only); the host
+ * mirror and rt_cli. */
+int rt_intersect_rays_instanced_indexed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                        const rt_accel* blas_table, uint32_t num_blas, const rt_ray* rays, uint32_t num_rays,
+                                        const uint32_t* order, uint32_t num_indices, rt_hit* hits, uint32_t* instance_ids,
+                                        int mode, uint32_t num_primitives, const rt_instance_hit_filter* filter,
+                                        uint64_t* counters, void* stream);
+int rt_intersect_rays_instanced_motion_indexed(const rt_motion_accel* tlas, const rt_motion_instance_record* records,
+                                               uint32_t num_instances, const rt_accel* blas_table, uint32_t num_blas,
+                                               const rt_ray* rays, const float* times, uint32_t num_rays, const uint32_t* order,
+                                               uint32_t num_indices, rt_hit* hits, uint32_t* instance_ids, int mode,
+                                               uint64_t* counters, void* stream);
+int rt_intersect_rays_instanced_mixed_indexed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                              const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                              const rt_ray* rays, uint32_t num_rays, const uint32_t* order, uint32_t num_indices,
+                                              rt_hit* hits, uint32_t* instance_ids, int mode, uint64_t* counters, void* stream);
+int rt_intersect_rays_motion_indexed(const rt_motion_accel* as, const rt_ray* rays, const float* times, uint32_t num_rays,
+                                     const uint32_t* order, uint32_t num_indices, rt_hit* hits, int mode, uint64_t* counters,
+                                     void* stream);
 
 /* ---- triangle-overlap queries (no reference counterpart).  For each caller triangle: WHICH triangles of the tree it cuts --
  * the narrow phase of mesh-against-mesh collision, self-intersection of a deforming mesh, interpenetration checks -- through
