@@ -3,10 +3,11 @@
 // told per BLAS by a table parallel to the BLAS table (semantics: rt_abi.h, mixed-instancing block).
 //
 // trace_instanced_mixed is trace_instanced<false, ANY> (rt_instance_traverse.hpp: the vote / park loop, the box step of both
-// levels, leaving and entering instances) written as a loop of its own, as rt_instance_motion_traverse.hpp is: a parameter
-// threaded through trace_instanced would change the code of the existing kernels.  The box step
-// (inst_box_step<false>), inst_advance, inst_second_slot, load_world_ray, load_accel, intersect_tri and intersect_sphere are
-// the existing headers' code, called from here.  What this file adds:
+// levels, leaving and entering instances) written as a loop of its own.  As a leaf-primitive policy of trace_instanced it
+// left the existing kernels untouched, but these four kernels came out neither instruction-identical nor within the parent's
+// run-to-run spread in tools/instance_mixed_bench.py, so the loop stays here and shares what leaves it
+// identical: the box step (inst_box_step<false>), inst_advance, inst_second_slot, load_world_ray, to_object_ray, load_accel,
+// intersect_tri and intersect_sphere are the existing headers' code, called from here.  What this file adds:
 //   * three values per lane -- the kind of the BLAS the lane is in, its sphere array and its sphere count --, read as ONE
 //     16-byte load of geom_table[blas] when the instance is entered, after its rt_accel;
 //   * the entry rules of the table: a kind that is neither RT_GEOM_* value, and a sphere BLAS without a sphere array, are
@@ -155,14 +156,7 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
                     }
                 }
                 if (ok) {
-                    const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz;
-                    r.ox = ((w0.x * ox + w0.y * oy) + w0.z * oz) + w0.w;
-                    r.oy = ((w1.x * ox + w1.y * oy) + w1.z * oz) + w1.w;
-                    r.oz = ((w2.x * ox + w2.y * oy) + w2.z * oz) + w2.w;
-                    r.dx = (w0.x * dx + w0.y * dy) + w0.z * dz;
-                    r.dy = (w1.x * dx + w1.y * dy) + w1.z * dz;
-                    r.dz = (w2.x * dx + w2.y * dy) + w2.z * dz;
-                    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
+                    to_object_ray(w0, w1, w2, r);
                     ln.nodes = reinterpret_cast<const rt_node*>(nnodes);
                     leaves = reinterpret_cast<const rt_triangle_pair*>(ntris);
                     kind = gkind;

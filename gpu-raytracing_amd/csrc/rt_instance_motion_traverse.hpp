@@ -1,17 +1,20 @@
-// rt_instance_motion_traverse.hpp -- the traversal of the instance-motion ray query of instance_motion_query.hip
-// (rt_intersect_rays_instanced_motion; rt_abi.h, instance-motion block): trace_instanced's two-level loop
-// (rt_instance_traverse.hpp) over a TLAS with two key poses and instances whose object_to_world moves between two keys, at
-// a time per ray.  What this file adds to that loop:
+// rt_instance_motion_traverse.hpp -- the TLAS policy of the instance-motion ray query of instance_motion_query.hip
+// (rt_intersect_rays_instanced_motion; rt_abi.h, instance-motion block): a TLAS with two key poses and
+// instances whose object_to_world moves between two keys, at a time per ray.
+//
+// The traversal is trace_instanced<false, ANY> (rt_instance_traverse.hpp: the vote / park loop, TLAS leaves as entries, one
+// 64-entry stack with the BLAS's base depth, the record's tail and its usability rule, the world ray reloaded on exit, the
+// triangle-pair test) with MovingTlas as its `Tlas` policy.  What the policy adds:
 //   * a TLAS step fetches the pair from both TLAS poses (eight 16-byte loads) and interpolates it with Lerp
 //     (rt_motion_traverse.hpp: fl(fl(w0 * a) + fl(tau * b)), w12 / w28 from pose 0); a BLAS step fetches the lane's static
 //     pair alone and tests the stored bits -- the pose-1 fetch and the interpolation sit under the lane's `top` predicate, a
 //     BLAS bound is never multiplied by a weight (0 * inf is NaN);
-//   * PH_ENTER loads the record's two matrices (six 16-byte loads and the tail), interpolates the twelve entries at the
-//     lane's time and inverts the result in float32: cofactors and determinant as prepare_instances_kernel writes them,
-//     inv_det = 1 / det, W = adj * inv_det, o' = W * (o - T), d' = W * d.  A matrix that is singular AT THIS TIME (det == 0,
-//     det or 1 / det not finite) is not entered by this ray.
-// Everything else -- TLAS leaves as entries, one 64-entry stack with the BLAS's base depth, the world ray reloaded on exit,
-// the leaf test -- is trace_instanced's, called or restated from there.  No PF arm, no filter.
+//   * the record is rt_motion_instance_record: two matrices (six 16-byte rows) in front of the tail;
+//   * enter interpolates the twelve entries at the lane's time and inverts the result in float32: cofactors and
+//     determinant as prepare_instances_kernel writes them, inv_det = 1 / det, W = adj * inv_det, o' = W * (o - T),
+//     d' = W * d.  A matrix that is singular AT THIS TIME (det == 0, det or 1 / det not finite) is not entered by this ray;
+//   * the TLAS arrays are the params struct's pose-0 ones (both poses hold the same ids).
+// No PF arm, no filter.
 // Device code only; every function is force-inlined into its kernel.
 #pragma once
 
@@ -46,14 +49,6 @@ struct InstMotionParams {
     static constexpr int park_num = kParkNum, park_den = kParkDen;
 };
 
-__device__ __forceinline__ void load_world_ray(const InstMotionParams& p, uint64_t i, Ray& r)
-{
-    const float4 a = p.rays[2 * i], b = p.rays[2 * i + 1];
-    r.ox = a.x; r.oy = a.y; r.oz = a.z;
-    r.dx = b.x; r.dy = b.y; r.dz = b.z;
-    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
-}
-
 // inst_box_step with the TLAS seen at the lane's time: in the TLAS the pair comes from both poses and is interpolated
 // (motion_box_step's fetch and arithmetic), in a BLAS it is the stored pair
 __device__ __forceinline__ void inst_motion_box_step(const LaneNodes& ln, const rt_node* tlas_nodes1, const Ray& r, Trav& t,
@@ -72,14 +67,14 @@ __device__ __forceinline__ void inst_motion_box_step(const LaneNodes& ln, const 
     inst_box_step_on<false>(ln, r, t, base, top, two, a0, b0, a1, b1);
 }
 
-// The object-space ray of world ray r under the record's matrix at the lane's time (k0 / k1: the rows of the record's two key
-// matrices, three 16-byte words each).  Returns false, r untouched, when that matrix cannot be inverted in float32.
-__device__ __forceinline__ bool enter_moving_instance(const float4 (&k0)[3], const float4 (&k1)[3], const Lerp& lerp, Ray& r)
+// The object-space ray of world ray r under the record's matrix at the lane's time (k[0..2] / k[3..5]: the rows of the
+// record's two key matrices).  Returns false, r untouched, when that matrix cannot be inverted in float32.
+__device__ __forceinline__ bool enter_moving_instance(const float4 (&k)[6], const Lerp& lerp, Ray& r)
 {
     auto mix = [&](float a, float b) { return lerp.w0 * a + lerp.tau * b; };
-    const float a00 = mix(k0[0].x, k1[0].x), a01 = mix(k0[0].y, k1[0].y), a02 = mix(k0[0].z, k1[0].z), t0 = mix(k0[0].w, k1[0].w);
-    const float a10 = mix(k0[1].x, k1[1].x), a11 = mix(k0[1].y, k1[1].y), a12 = mix(k0[1].z, k1[1].z), t1 = mix(k0[1].w, k1[1].w);
-    const float a20 = mix(k0[2].x, k1[2].x), a21 = mix(k0[2].y, k1[2].y), a22 = mix(k0[2].z, k1[2].z), t2 = mix(k0[2].w, k1[2].w);
+    const float a00 = mix(k[0].x, k[3].x), a01 = mix(k[0].y, k[3].y), a02 = mix(k[0].z, k[3].z), t0 = mix(k[0].w, k[3].w);
+    const float a10 = mix(k[1].x, k[4].x), a11 = mix(k[1].y, k[4].y), a12 = mix(k[1].z, k[4].z), t1 = mix(k[1].w, k[4].w);
+    const float a20 = mix(k[2].x, k[5].x), a21 = mix(k[2].y, k[5].y), a22 = mix(k[2].z, k[5].z), t2 = mix(k[2].w, k[5].w);
     // prepare_instances_kernel's cofactors and determinant, in float32
     const float c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
     const float det = (a00 * c00 + a01 * c01) + a02 * c02;
@@ -99,112 +94,35 @@ __device__ __forceinline__ bool enter_moving_instance(const float4 (&k0)[3], con
     return true;
 }
 
-// trace_instanced<false, ANY> with the two steps above.  tau: the lane's time, in [0, 1] for an active lane.  Returns tri_hit;
-// *hit_inst = the instance of h; steps[0] / steps[1] as trace_ray.
+// trace_instanced's TLAS policy (StaticTlas: rt_instance_traverse.hpp) for a TLAS and records seen at the lane's time
+struct MovingTlas {
+    static constexpr bool moving = true;
+    Lerp lerp;
+    __device__ __forceinline__ static const rt_node* nodes(const InstMotionParams& p) { return p.tlas_nodes0; }
+    __device__ __forceinline__ static const rt_triangle_pair* leaves(const InstMotionParams& p) { return p.tlas_leaves0; }
+    template <bool PF>
+    __device__ __forceinline__ void box_step(const InstMotionParams& p, const LaneNodes& ln, const Ray& r, Trav& t, int base,
+                                             bool top) const
+    {
+        static_assert(!PF, "the instance-motion query has no pair-prefetch arm");
+        inst_motion_box_step(ln, p.tlas_nodes1, r, t, base, top, lerp);
+    }
+    // rt_motion_instance_record: the rows of two key matrices in front of the tail
+    __device__ __forceinline__ bool enter(const InstMotionParams& p, uint32_t id, Ray& r, BlasRef& b) const
+    {
+        float4 k[6];
+        if (!load_instance(p, id, b, k[0], k[1], k[2], k[3], k[4], k[5])) return false;
+        return enter_moving_instance(k, lerp, r);
+    }
+};
+
+// tau: the lane's time, in [0, 1] for an active lane
 template <bool ANY>
 __device__ __forceinline__ bool trace_instanced_motion(const InstMotionParams& p, uint64_t ri, Ray& r, float tau, Hit& h,
                                                        uint32_t& hit_inst, Trav& t, bool active, uint32_t* steps)
 {
-    const Lerp lerp = {1.0f - tau, tau};
-    LaneNodes ln = {p.tlas_nodes0};
-    const rt_triangle_pair* leaves = p.tlas_leaves0;
-    uint32_t inst = kTop;
-    int base = 0;
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    bool tri_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-
-    while (true) {
-        // ---------------------------------------------------- box phase (both levels)
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase != PH_STEP) & (t.phase != PH_DONE));
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;
-            if (t.phase == PH_STEP) inst_motion_box_step(ln, p.tlas_nodes1, r, t, base, inst == kTop, lerp);
-            if (t.phase == PH_STEP) inst_motion_box_step(ln, p.tlas_nodes1, r, t, base, inst == kTop, lerp);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase: triangle tests, leaving and entering instances
-        nleaf++;
-        if ((t.phase != PH_STEP) & (t.phase != PH_DONE)) {
-            if ((t.phase - 1u) < 2u) {   // PH_LEAF0 / PH_LEAF1: a leaf of the static BLAS, as trace_instanced
-                t.tri_tests++;
-                const uint32_t li = t.leaf & kIndexMask;
-                const uint4* tp = reinterpret_cast<const uint4*>(leaves + li);
-                const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-                bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                             __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                             __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                             r, h, li << 1, l0.w);
-                if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
-                    hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                             __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                             __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                             r, h, (li << 1) + 1, l1.w);
-                tri_hit |= hit_tri;
-                if (hit_tri) hit_inst = inst;
-                if (ANY && hit_tri) {
-                    t.phase = PH_DONE;
-                } else {
-                    const bool was_first = t.phase == PH_LEAF0;
-                    t.phase = PH_STEP;
-                    if (was_first) inst_second_slot(t, r.tmin, r.tmax, false);
-                    if (t.phase == PH_STEP) inst_advance(t, base, false);
-                }
-            }
-            if (t.phase == PH_EXIT) {    // the BLAS is done: back to the world ray and the TLAS
-                load_world_ray(p, ri, r);
-                ln.nodes = p.tlas_nodes0;
-                inst = kTop;
-                base = 0;
-                t.phase = PH_STEP;
-                inst_advance(t, 0, true);
-            }
-            if (t.phase == PH_ENTER) {   // a TLAS leaf (pose 0's: both poses hold the same ids): enter its instance, or go on
-                const uint32_t id = reinterpret_cast<const uint4*>(p.tlas_leaves0 + (t.cur & kIndexMask))[0].w;
-                bool ok = id < p.num_instances;
-                uint32_t nroot = 0, ncount = 0;
-                uint64_t ntris = 0, nnodes = 0;
-                if (ok) {
-                    const float4* rec = reinterpret_cast<const float4*>(p.records + id);
-                    const float4 k0[3] = {rec[0], rec[1], rec[2]}, k1[3] = {rec[3], rec[4], rec[5]};
-                    const uint4 tail = reinterpret_cast<const uint4*>(rec)[6];   // blas, flags, spare
-                    ok = (tail.y == 0u) & (tail.x < p.num_blas);
-                    if (ok) {
-                        load_accel(p.blas_table, tail.x, ntris, nnodes, nroot, ncount);
-                        ok = (ncount - 1u) < 7u;
-                    }
-                    if (ok) ok = enter_moving_instance(k0, k1, lerp, r);
-                }
-                if (ok) {
-                    ln.nodes = reinterpret_cast<const rt_node*>(nnodes);
-                    leaves = reinterpret_cast<const rt_triangle_pair*>(ntris);
-                    inst = id;
-                    base = t.sp;
-                    t.cur = (nroot & kIndexMask) | (ncount << 29);
-                    t.phase = PH_STEP;
-                } else {
-                    t.phase = PH_STEP;
-                    inst_advance(t, 0, true);
-                }
-            }
-        }
-    }
-    steps[0] += nbox;
-    steps[1] += nleaf;
-    return tri_hit;
+    return trace_instanced<false, ANY, NoInstanceFilter, MovingTlas>(p, ri, r, h, hit_inst, t, active, steps, NoInstanceFilter(),
+                                                                     MovingTlas{{1.0f - tau, tau}});
 }
 
 }  // namespace

@@ -1,8 +1,18 @@
-// rt_instance_traverse.hpp -- the two-level traversal of the instanced ray queries of instances.hip
-// (rt_intersect_rays_instanced and rt_intersect_rays_instanced_filtered, the two arms of one kernel): the kernel parameters, the
-// TLAS-aware box step and trace_instanced, the wave-level two-phase loop with its second level (what the second level adds to a
-// lane: instances.hip's header; DESIGN sections 9 and 21).  trace_instanced takes an instance-filter policy the way trace_ray
-// takes a hit-filter policy: with NoInstanceFilter the code is instance_query_kernel's, instruction for instruction.
+// rt_instance_traverse.hpp -- the two-level traversal of the closest / any-hit instanced ray queries: instances.hip
+// (rt_intersect_rays_instanced and rt_intersect_rays_instanced_filtered, the two arms of one kernel) and
+// instance_motion_query.hip.  Here: the kernel parameters, the TLAS-aware box step, and trace_instanced, the wave-level
+// two-phase loop with a second level (what the second level adds to a lane: instances.hip's header; DESIGN sections 9 and 21).
+//
+// What is shared, each defined once: the Trav initialisation and the vote / park box phase; the triangle-pair leaf test with
+// its was_first / second-slot / advance tail; the exit to the TLAS (load_world_ray, for any params struct with `rays`); the
+// skeleton of entering an instance -- the id bound, load_instance (the record's rows and tail, the usability rule, load_accel,
+// the root-run rule), to_object_ray, the commit of the lane's BLAS.  What differs travels as two policies, by value, the way
+// trace_ray takes its hit-filter policy: the instance filter (rt_instance_filter.hpp) and the TLAS (StaticTlas here, MovingTlas
+// in rt_instance_motion_traverse.hpp).  With the defaults the code is instance_query_kernel's, instruction for instruction;
+// how each policy is spelled is what keeps it so, and the motion kernels too ("Policies and helpers").
+// Three traversals keep loops of their own and use the small helpers from here: rt_instance_mixed_traverse.hpp (a policy for
+// its leaf primitives left its kernels neither identical nor within the measured bar: DESIGN section 25), and
+// ray_hits_instanced_query.hip and ray_first_instanced_query.hip (an unordered and a nearest-first traversal).
 // Device code only; every function is force-inlined into its kernel.
 #pragma once
 
@@ -104,13 +114,35 @@ __device__ __forceinline__ void inst_box_step(const LaneNodes& ln, const Ray& r,
     inst_box_step_on<PF>(ln, r, t, base, top, two, a0, b0, a1, b1);
 }
 
-__device__ __forceinline__ void load_world_ray(const InstParams& p, uint64_t i, Ray& r)
+// the world ray of ray i (origin, direction and its reciprocal; tmin / tmax are not the transform's and stay), for any
+// params struct that has `rays`
+template <class P>
+__device__ __forceinline__ void load_world_ray(const P& p, uint64_t i, Ray& r)
 {
     const float4 a = p.rays[2 * i], b = p.rays[2 * i + 1];
     r.ox = a.x; r.oy = a.y; r.oz = a.z;
     r.dx = b.x; r.dy = b.y; r.dz = b.z;
     r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
 }
+
+// world ray r to the object ray of an instance: w0, w1, w2 are the rows of the record's world_to_object
+__device__ __forceinline__ void to_object_ray(const float4& w0, const float4& w1, const float4& w2, Ray& r)
+{
+    const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz;
+    r.ox = ((w0.x * ox + w0.y * oy) + w0.z * oz) + w0.w;
+    r.oy = ((w1.x * ox + w1.y * oy) + w1.z * oz) + w1.w;
+    r.oz = ((w2.x * ox + w2.y * oy) + w2.z * oz) + w2.w;
+    r.dx = (w0.x * dx + w0.y * dy) + w0.z * dz;
+    r.dy = (w1.x * dx + w1.y * dy) + w1.z * dz;
+    r.dz = (w2.x * dx + w2.y * dy) + w2.z * dz;
+    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
+}
+
+// a BLAS as its rt_accel tells it: the root run, the leaf and node arrays
+struct BlasRef {
+    uint32_t root, count;
+    uint64_t tris, nodes;
+};
 
 // rt_accel of table entry b: three 8-byte loads (the entries are 24 bytes apart)
 __device__ __forceinline__ void load_accel(const rt_accel* table, uint32_t b, uint64_t& tris, uint64_t& nodes, uint32_t& root,
@@ -124,22 +156,57 @@ __device__ __forceinline__ void load_accel(const rt_accel* table, uint32_t b, ui
     count = z.y;
 }
 
-// The instance-filter policy of trace_instanced.  NoInstanceFilter: every usable instance is entered and every triangle
-// Moller-Trumbore accepts is accepted (instance_query_kernel; `if constexpr` leaves no trace of the policy in it).  A policy with
-// active = true (rt_instance_filter.hpp) supplies enter(id), asked at the TLAS leaf before the instance record is read,
-// set_instance(id, w0, w1, w2), called once the instance is entered, and `tri`, the intersect_tri policy of the entered
-// instance.  The object travels by value, as NoFilter does.
+// The two policies of trace_instanced.  Both travel by value, as NoFilter does, and every difference is taken under
+// `if constexpr` or inside a policy's force-inlined members: the defaults leave no trace in instance_query_kernel.
+//
+// The instance filter.  NoInstanceFilter: every usable instance is entered and every triangle Moller-Trumbore accepts is
+// accepted.  A policy with active = true (rt_instance_filter.hpp) supplies enter(id), asked at the TLAS leaf before the
+// instance record is read, set_instance(id, w0, w1, w2), called once the instance is entered, and `tri`, the intersect_tri
+// policy of the entered instance.
 struct NoInstanceFilter {
     static constexpr bool active = false;
 };
 
-// The two-level traversal of ray `ri` (r: its world ray, loaded by the caller).  Returns tri_hit; *hit_inst = the instance of h.
-template <bool PF, bool ANY, class IFilter = NoInstanceFilter>
-__device__ __forceinline__ bool trace_instanced(const InstParams& p, uint64_t ri, Ray& r, Hit& h, uint32_t& hit_inst, Trav& t,
-                                                bool active, uint32_t* steps, IFilter flt = IFilter())
+// The record of instance `id` -- its rows w..., as many as are handed in, then (blas, flags, spare) -- and its BLAS's table
+// entry.  False: the instance is unusable -- flags set, a BLAS index past the table, a root run of 0 or more than 7 slots.
+template <class P, class... Rows>
+__device__ __forceinline__ bool load_instance(const P& p, uint32_t id, BlasRef& b, Rows&... w)
 {
-    LaneNodes ln = {p.tlas_nodes};
-    const rt_triangle_pair* leaves = p.tlas_leaves;
+    const float4* rec = reinterpret_cast<const float4*>(p.records + id);
+    int k = 0;
+    ((w = rec[k++]), ...);
+    const uint4 tail = reinterpret_cast<const uint4*>(rec)[sizeof...(Rows)];   // blas, flags, spare
+    bool ok = (tail.y == 0u) & (tail.x < p.num_blas);
+    if (ok) {
+        load_accel(p.blas_table, tail.x, b.tris, b.nodes, b.root, b.count);
+        ok = (b.count - 1u) < 7u;
+    }
+    return ok;
+}
+
+// The TLAS.  StaticTlas: one pose (p.tlas_nodes / p.tlas_leaves) and rt_instance_record, three rows of world_to_object, which
+// trace_instanced loads and applies itself (the filter is shown them).  A policy names the TLAS arrays of its params struct and
+// takes the box step of both levels; one with moving = true (MovingTlas, rt_instance_motion_traverse.hpp) also supplies
+// enter(...): load_instance with its own record's rows and the world ray r made the object ray, or false, r untouched.
+struct StaticTlas {
+    static constexpr bool moving = false;
+    template <class P> __device__ __forceinline__ static const rt_node* nodes(const P& p) { return p.tlas_nodes; }
+    template <class P> __device__ __forceinline__ static const rt_triangle_pair* leaves(const P& p) { return p.tlas_leaves; }
+    template <bool PF, class P>
+    __device__ __forceinline__ static void box_step(const P&, const LaneNodes& ln, const Ray& r, Trav& t, int base, bool top)
+    {
+        inst_box_step<PF>(ln, r, t, base, top);
+    }
+};
+
+// The two-level traversal of ray `ri` (r: its world ray, loaded by the caller).  Returns tri_hit; *hit_inst = the instance of
+// h; steps[0] / steps[1] as trace_ray.
+template <bool PF, bool ANY, class IFilter = NoInstanceFilter, class Tlas = StaticTlas, class P>
+__device__ __forceinline__ bool trace_instanced(const P& p, uint64_t ri, Ray& r, Hit& h, uint32_t& hit_inst, Trav& t,
+                                                bool active, uint32_t* steps, IFilter flt = IFilter(), Tlas tlas = Tlas())
+{
+    LaneNodes ln = {tlas.nodes(p)};
+    const rt_triangle_pair* leaves = tlas.leaves(p);
     uint32_t inst = kTop;
     int base = 0;
     t.sp = 0;
@@ -156,6 +223,8 @@ __device__ __forceinline__ bool trace_instanced(const InstParams& p, uint64_t ri
     prefetch_pair<PF>(ln, t);
     bool tri_hit = false;
     uint32_t nbox = 0, nleaf = 0;
+    // the entered instance's intersect_tri policy, or none
+    auto tri_flt = [&] { if constexpr (IFilter::active) return flt.tri; else return NoFilter(); };
 
     while (true) {
         // ---------------------------------------------------- box phase (both levels)
@@ -165,40 +234,28 @@ __device__ __forceinline__ bool trace_instanced(const InstParams& p, uint64_t ri
             parked = __builtin_amdgcn_ballot_w64((t.phase != PH_STEP) & (t.phase != PH_DONE));
             if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
             nbox += 2;
-            if (t.phase == PH_STEP) inst_box_step<PF>(ln, r, t, base, inst == kTop);
-            if (t.phase == PH_STEP) inst_box_step<PF>(ln, r, t, base, inst == kTop);
+            if (t.phase == PH_STEP) tlas.template box_step<PF>(p, ln, r, t, base, inst == kTop);
+            if (t.phase == PH_STEP) tlas.template box_step<PF>(p, ln, r, t, base, inst == kTop);
         }
         if ((stepping | parked) == 0) break;
         // ---------------------------------------------------- leaf phase: triangle tests, leaving and entering instances
         nleaf++;
         if ((t.phase != PH_STEP) & (t.phase != PH_DONE)) {
             if ((t.phase - 1u) < 2u) {   // PH_LEAF0 / PH_LEAF1: a BLAS leaf, as trace_ray
+                // triangle A = (v0, v1, v2) and, unless v3 == v2 bit for bit (a single triangle), B = (v2, v1, v3)
                 t.tri_tests++;
                 const uint32_t li = t.leaf & kIndexMask;
                 const uint4* tp = reinterpret_cast<const uint4*>(leaves + li);
                 const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
-                bool hit_tri;
-                if constexpr (IFilter::active) {
-                    hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                            __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                            __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                            r, h, li << 1, l0.w, flt.tri);
-                    if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
-                        hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                 __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                 __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                                 r, h, (li << 1) + 1, l1.w, flt.tri);
-                } else {
-                    hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
-                                            __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                            __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                            r, h, li << 1, l0.w);
-                    if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
-                        hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
-                                                 __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
-                                                 __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
-                                                 r, h, (li << 1) + 1, l1.w);
-                }
+                bool hit_tri = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
+                                             __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
+                                             __uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
+                                             r, h, li << 1, l0.w, tri_flt());
+                if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
+                    hit_tri |= intersect_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z),
+                                             __uint_as_float(l1.x), __uint_as_float(l1.y), __uint_as_float(l1.z),
+                                             __uint_as_float(l3.x), __uint_as_float(l3.y), __uint_as_float(l3.z),
+                                             r, h, (li << 1) + 1, l1.w, tri_flt());
                 tri_hit |= hit_tri;
                 if (hit_tri) hit_inst = inst;
                 if (ANY && hit_tri) {
@@ -212,46 +269,35 @@ __device__ __forceinline__ bool trace_instanced(const InstParams& p, uint64_t ri
             }
             if (t.phase == PH_EXIT) {    // the BLAS is done: back to the world ray and the TLAS
                 load_world_ray(p, ri, r);
-                ln.nodes = p.tlas_nodes;
+                ln.nodes = tlas.nodes(p);
                 inst = kTop;
                 base = 0;
                 t.phase = PH_STEP;
                 inst_advance(t, 0, true);
             }
             if (t.phase == PH_ENTER) {   // a TLAS leaf: enter its instance, or go on in the TLAS
-                const uint32_t id = reinterpret_cast<const uint4*>(p.tlas_leaves + (t.cur & kIndexMask))[0].w;
+                const uint32_t id = reinterpret_cast<const uint4*>(tlas.leaves(p) + (t.cur & kIndexMask))[0].w;
                 bool ok = id < p.num_instances;
                 if constexpr (IFilter::active) {
                     if (ok) ok = flt.enter(id);   // the instance rule: asked first, a masked-out instance makes no further load
                 }
-                uint32_t nroot = 0, ncount = 0;
-                uint64_t ntris = 0, nnodes = 0;
-                float4 w0, w1, w2;
-                if (ok) {
-                    const float4* rec = reinterpret_cast<const float4*>(p.records + id);
-                    w0 = rec[0]; w1 = rec[1]; w2 = rec[2];
-                    const uint4 tail = reinterpret_cast<const uint4*>(rec)[3];   // blas, flags, spare
-                    ok = (tail.y == 0u) & (tail.x < p.num_blas);
+                BlasRef b = {0u, 0u, 0ull, 0ull};
+                if constexpr (Tlas::moving) {
+                    if (ok) ok = tlas.enter(p, id, r, b);
+                } else {
+                    float4 w0, w1, w2;
+                    if (ok) ok = load_instance(p, id, b, w0, w1, w2);
                     if (ok) {
-                        load_accel(p.blas_table, tail.x, ntris, nnodes, nroot, ncount);
-                        ok = (ncount - 1u) < 7u;
+                        if constexpr (IFilter::active) flt.set_instance(id, w0, w1, w2);
+                        to_object_ray(w0, w1, w2, r);
                     }
                 }
                 if (ok) {
-                    if constexpr (IFilter::active) flt.set_instance(id, w0, w1, w2);
-                    const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz;
-                    r.ox = ((w0.x * ox + w0.y * oy) + w0.z * oz) + w0.w;
-                    r.oy = ((w1.x * ox + w1.y * oy) + w1.z * oz) + w1.w;
-                    r.oz = ((w2.x * ox + w2.y * oy) + w2.z * oz) + w2.w;
-                    r.dx = (w0.x * dx + w0.y * dy) + w0.z * dz;
-                    r.dy = (w1.x * dx + w1.y * dy) + w1.z * dz;
-                    r.dz = (w2.x * dx + w2.y * dy) + w2.z * dz;
-                    r.ix = 1.0f / r.dx; r.iy = 1.0f / r.dy; r.iz = 1.0f / r.dz;
-                    ln.nodes = reinterpret_cast<const rt_node*>(nnodes);
-                    leaves = reinterpret_cast<const rt_triangle_pair*>(ntris);
+                    ln.nodes = reinterpret_cast<const rt_node*>(b.nodes);
+                    leaves = reinterpret_cast<const rt_triangle_pair*>(b.tris);
                     inst = id;
                     base = t.sp;
-                    t.cur = (nroot & kIndexMask) | (ncount << 29);
+                    t.cur = (b.root & kIndexMask) | (b.count << 29);
                     t.phase = PH_STEP;
                 } else {
                     t.phase = PH_STEP;
