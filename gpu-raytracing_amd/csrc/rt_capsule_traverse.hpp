@@ -3,8 +3,8 @@
 // trace_ray tests a leaf's triangles.  The slab test, the ordered compares and the nearest-child choice of box_step, Trav's
 // stack and second_slot are rt_traverse.hpp's code and intersect_sphere is rt_sphere_traverse.hpp's, called from here.  What
 // this file adds is the leaf phase -- the leaf's first 16 bytes for the capsule index (its primitive_id_0), capsules[id] as
-// two independent 16-byte loads, the test below -- and the loop that drives the two (trace_ray_spheres's loop: the plain vote
-// / park loop; no PF arm, no hold at pop).
+// two independent 16-byte loads, the test below -- as CapsuleWalk, the policy that hands box_step and that leaf phase to
+// trace_plain (rt_plain_traverse.hpp: the plain vote / park loop trace_ray_spheres walks through; no PF arm, no hold at pop).
 //
 // The test (rt_abi.h, capsule block, has it operation by operation): the ray is re-based at its point nearest the capsule's
 // midpoint, so no term is of the size of |o - m|^2; the infinite cylinder's roots pick the body or, by the side on which
@@ -15,6 +15,7 @@
 
 #include "rt_device.hpp"
 #include "rt_sphere_traverse.hpp"
+#include "rt_plain_traverse.hpp"
 #include "rt_traverse.hpp"
 
 // waves per SIMD the capsule kernel's register allocation must fit: one step below the sphere kernel's 8.  The leaf keeps the
@@ -146,67 +147,32 @@ __device__ __forceinline__ bool intersect_capsule(const float4& c0, const float4
     return true;
 }
 
-// the leaf phase's work for one parked lane: the capsule index, the capsule, the test.  A leaf whose index is not below
-// num_capsules and a capsule that is not valid (a negative, NaN or infinite radius) are skipped: no test counted.
-__device__ __forceinline__ bool capsule_leaf_test(const CapsuleParams& p, Ray& r, CapsuleHit& h, Trav& t)
-{
-    const uint32_t id = reinterpret_cast<const uint4*>(p.leaves + (t.leaf & kIndexMask))[0].w;
-    if (id >= p.num_capsules) return false;
-    const float4 c0 = p.capsules[2 * (uint64_t)id], c1 = p.capsules[2 * (uint64_t)id + 1];
-    if (!(c0.w >= 0.0f) || c0.w == __builtin_inff()) return false;
-    t.tri_tests++;
-    return intersect_capsule(c0, c1, r, h, id);
-}
+// trace_plain's policy: trace_ray's box step, the capsule test at the leaf
+struct CapsuleWalk {
+    CapsuleHit& h;
+    __device__ __forceinline__ void begin(const CapsuleParams&) {}
+    __device__ __forceinline__ void box(const CapsuleParams& p, const Ray& r, Trav& t) { box_step<false>(p, r, t); }
+    // the leaf phase's work for one parked lane: the capsule index, the capsule, the test.  A leaf whose index is not below
+    // num_capsules and a capsule that is not valid (a negative, NaN or infinite radius) are skipped: no test counted.  (The
+    // member is the leaf test itself, not a call of one: a level of calls between them renumbers three VGPRs of the kernels)
+    __device__ __forceinline__ bool leaf(const CapsuleParams& p, Ray& r, Trav& t)
+    {
+        const uint32_t id = reinterpret_cast<const uint4*>(p.leaves + (t.leaf & kIndexMask))[0].w;
+        if (id >= p.num_capsules) return false;
+        const float4 c0 = p.capsules[2 * (uint64_t)id], c1 = p.capsules[2 * (uint64_t)id + 1];
+        if (!(c0.w >= 0.0f) || c0.w == __builtin_inff()) return false;
+        t.tri_tests++;
+        return intersect_capsule(c0, c1, r, h, id);
+    }
+};
 
-// trace_ray_spheres with the leaf phase above.  Returns whether a capsule was accepted; steps[0] / steps[1] as trace_ray.
+// Returns whether a capsule was accepted; steps[0] / steps[1] as trace_ray.
 template <bool ANY>
 __device__ __forceinline__ bool trace_ray_capsules(const CapsuleParams& p, Ray& r, CapsuleHit& h, Trav& t, bool active,
                                                    uint32_t* steps)
 {
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    bool any_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-
-    while (true) {
-        // ---------------------------------------------------- box phase: step while enough lanes want to
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;   // two box steps per vote, as trace_ray
-            if (t.phase == PH_STEP) box_step<false>(p, r, t);
-            if (t.phase == PH_STEP) box_step<false>(p, r, t);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase
-        nleaf++;
-        if ((t.phase - 1u) < 2u) {
-            const bool hit = capsule_leaf_test(p, r, h, t);
-            any_hit |= hit;
-            if (ANY && hit) {
-                t.phase = PH_DONE;
-            } else {
-                const bool was_first = t.phase == PH_LEAF0;
-                t.phase = PH_STEP;
-                if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) t.advance();
-            }
-        }
-    }
-    steps[0] += nbox;
-    steps[1] += nleaf;
-    return any_hit;
+    CapsuleWalk w = {h};
+    return trace_plain<ANY>(p, r, t, active, steps, w);
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 // ray.  A lane sees every box bound and every leaf corner interpolated at its own time and runs trace_ray's tests on the
 // interpolated values: the slab test and the ordered compares of box_step_on, intersect_tri, Trav's stack -- all of them
 // rt_traverse.hpp's code, called from here.  What this file adds is the fetch of a pair from both poses, the interpolation
-// and the loop that drives them (trace_ray's non-QW vote / park loop; no PF arm, no uniform arm).
+// and MotionWalk, the policy that hands the two steps and the lane's weights to trace_plain (rt_plain_traverse.hpp: trace_ray's
+// non-QW vote / park loop, written once; no PF arm, no uniform arm).
 //
 // The interpolation is  w0 = 1 - tau (once per ray);  v = fl(fl(w0 * a) + fl(tau * b))  -- two multiplies and one add, never
 // contracted (-ffp-contract=off) and never rewritten as a + tau * (b - a):
@@ -16,6 +17,7 @@
 #pragma once
 
 #include "rt_device.hpp"
+#include "rt_plain_traverse.hpp"
 #include "rt_traverse.hpp"
 
 // waves per SIMD the motion kernel's register allocation must fit: a box step holds eight 16-byte loads in flight instead of
@@ -99,58 +101,26 @@ __device__ __forceinline__ bool motion_leaf_test(const MotionParams& p, Ray& r, 
     return hit_tri;
 }
 
-// trace_ray<false, ANY> of rt_traverse.hpp (its plain vote / park loop) with the two steps above.  tau: the lane's time, in
-// [0, 1] for an active lane.  Returns tri_hit; steps[0] / steps[1] as trace_ray.
+// trace_plain's policy: the two steps above at the lane's weights
+struct MotionWalk {
+    Hit& h;
+    const Lerp lerp;
+    __device__ __forceinline__ void begin(const MotionParams&) {}
+    __device__ __forceinline__ void box(const MotionParams& p, const Ray& r, Trav& t) { motion_box_step(p, r, t, lerp); }
+    __device__ __forceinline__ bool leaf(const MotionParams& p, Ray& r, Trav& t)
+    {
+        t.tri_tests++;
+        return motion_leaf_test(p, r, h, t, lerp);
+    }
+};
+
+// tau: the lane's time, in [0, 1] for an active lane.  Returns tri_hit; steps[0] / steps[1] as trace_ray.
 template <bool ANY>
 __device__ __forceinline__ bool trace_ray_motion(const MotionParams& p, Ray& r, float tau, Hit& h, Trav& t, bool active,
                                                  uint32_t* steps)
 {
-    const Lerp lerp = {1.0f - tau, tau};
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    bool tri_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-
-    while (true) {
-        // ---------------------------------------------------- box phase: step while enough lanes want to
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;   // two box steps per vote, as trace_ray
-            if (t.phase == PH_STEP) motion_box_step(p, r, t, lerp);
-            if (t.phase == PH_STEP) motion_box_step(p, r, t, lerp);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase
-        nleaf++;
-        if ((t.phase - 1u) < 2u) {
-            t.tri_tests++;
-            const bool hit_tri = motion_leaf_test(p, r, h, t, lerp);
-            tri_hit |= hit_tri;
-            if (ANY && hit_tri) {
-                t.phase = PH_DONE;
-            } else {
-                const bool was_first = t.phase == PH_LEAF0;
-                t.phase = PH_STEP;
-                if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) t.advance();
-            }
-        }
-    }
-    steps[0] += nbox;
-    steps[1] += nleaf;
-    return tri_hit;
+    MotionWalk w = {h, {1.0f - tau, tau}};
+    return trace_plain<ANY>(p, r, t, active, steps, w);
 }
 
 }  // namespace

@@ -10,7 +10,8 @@
 //     caller's corner order, the range query's), else the facing offset face (intersect_tri on an origin shifted by rad along
 //     the unit normal) and the near roots of the three edge capsules, accepted in that order against one shrinking tmax;
 //     rad == 0: intersect_tri alone, the ray query's leaf test;
-//   * the loop that drives the two (trace_ray_spheres's: the plain vote / park loop; no PF arm, no hold at pop).
+//   * CastWalk, the policy that hands the two, the lane's radius and its growth to trace_plain (rt_plain_traverse.hpp: the
+//     plain vote / park loop trace_ray_spheres walks through; no PF arm, no hold at pop).
 // Every operation is rounded on its own (-ffp-contract=off), the divisions are IEEE and the square roots correctly rounded.
 // Device code only; every function is force-inlined into its kernel.
 #pragma once
@@ -18,6 +19,7 @@
 #include "rt_device.hpp"
 #include "rt_capsule_traverse.hpp"
 #include "rt_point_math.hpp"
+#include "rt_plain_traverse.hpp"
 #include "rt_traverse.hpp"
 
 // waves per SIMD the cast kernel's register allocation must fit.  The leaf holds nine corner coordinates, the re-based ray and
@@ -220,70 +222,39 @@ __device__ __forceinline__ bool cast_leaf_tri(float s0x, float s0y, float s0z, f
     return cast_tri(s0x, s0y, s0z, s1x, s1y, s1z, s2x, s2y, s2z, rot, r, rad, ch, tri_id, prim_id);
 }
 
-// trace_ray_spheres with the grown box step and the leaf phase above.  Returns whether a triangle was accepted; steps[0] /
-// steps[1] as trace_ray.
+// trace_plain's policy: the growth made once per ray, the grown box step, trace_ray's leaf phase with the cast's triangle test
+struct CastWalk {
+    CastHit& ch;
+    const float rad;
+    float elo, ehi;
+    __device__ __forceinline__ void begin(const CastParams& p) { cast_grow(p, rad, elo, ehi); }
+    __device__ __forceinline__ void box(const CastParams& p, const Ray& r, Trav& t) { cast_box_step(p, r, t, elo, ehi); }
+    __device__ __forceinline__ bool leaf(const CastParams& p, Ray& r, Trav& t)
+    {
+        t.tri_tests++;
+        const uint32_t li = t.leaf & kIndexMask;
+        uint4 l0, l1, l2, l3;
+        load_leaf_wide(p.leaves + li, l0, l1, l2, l3);
+        bool hit = cast_leaf_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z), __uint_as_float(l1.x),
+                                 __uint_as_float(l1.y), __uint_as_float(l1.z), __uint_as_float(l2.x), __uint_as_float(l2.y),
+                                 __uint_as_float(l2.z), l2.w & 0xFFFFu, r, rad, ch, li << 1, l0.w);
+        // triangle B = (v2, v1, v3), skipped when v3 == v2 bit for bit (a single triangle), as the ray query skips it.  Its
+        // edge v2-v1 is A's edge v1-v2: tested again, as B's own.  (Any-hit tests B after a hit on A too: the ray query does)
+        if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
+            hit |= cast_leaf_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z), __uint_as_float(l1.x),
+                                 __uint_as_float(l1.y), __uint_as_float(l1.z), __uint_as_float(l3.x), __uint_as_float(l3.y),
+                                 __uint_as_float(l3.z), l2.w >> 16, r, rad, ch, (li << 1) + 1, l1.w);
+        return hit;
+    }
+};
+
+// Returns whether a triangle was accepted; steps[0] / steps[1] as trace_ray.
 template <bool ANY>
 __device__ __forceinline__ bool trace_sphere_cast(const CastParams& p, Ray& r, float rad, CastHit& ch, Trav& t, bool active,
                                                   uint32_t* steps)
 {
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    float elo, ehi;
-    cast_grow(p, rad, elo, ehi);
-    bool any_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-
-    while (true) {
-        // ---------------------------------------------------- box phase: step while enough lanes want to
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;   // two box steps per vote, as trace_ray
-            if (t.phase == PH_STEP) cast_box_step(p, r, t, elo, ehi);
-            if (t.phase == PH_STEP) cast_box_step(p, r, t, elo, ehi);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase: trace_ray's, with the cast's triangle test
-        nleaf++;
-        if ((t.phase - 1u) < 2u) {
-            t.tri_tests++;
-            const uint32_t li = t.leaf & kIndexMask;
-            uint4 l0, l1, l2, l3;
-            load_leaf_wide(p.leaves + li, l0, l1, l2, l3);
-            bool hit = cast_leaf_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z), __uint_as_float(l1.x),
-                                     __uint_as_float(l1.y), __uint_as_float(l1.z), __uint_as_float(l2.x), __uint_as_float(l2.y),
-                                     __uint_as_float(l2.z), l2.w & 0xFFFFu, r, rad, ch, li << 1, l0.w);
-            // triangle B = (v2, v1, v3), skipped when v3 == v2 bit for bit (a single triangle), as the ray query skips it.  Its
-            // edge v2-v1 is A's edge v1-v2: tested again, as B's own.  (Any-hit tests B after a hit on A too: the ray query does)
-            if ((t.leaf >> 29) > 0 && (l3.x != l2.x || l3.y != l2.y || l3.z != l2.z))
-                hit |= cast_leaf_tri(__uint_as_float(l2.x), __uint_as_float(l2.y), __uint_as_float(l2.z), __uint_as_float(l1.x),
-                                     __uint_as_float(l1.y), __uint_as_float(l1.z), __uint_as_float(l3.x), __uint_as_float(l3.y),
-                                     __uint_as_float(l3.z), l2.w >> 16, r, rad, ch, (li << 1) + 1, l1.w);
-            any_hit |= hit;
-            if (ANY && hit) {
-                t.phase = PH_DONE;
-            } else {
-                const bool was_first = t.phase == PH_LEAF0;
-                t.phase = PH_STEP;
-                if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) t.advance();
-            }
-        }
-    }
-    steps[0] += nbox;
-    steps[1] += nleaf;
-    return any_hit;
+    CastWalk w = {ch, rad, 0.0f, 0.0f};
+    return trace_plain<ANY>(p, r, t, active, steps, w);
 }
 
 }  // namespace

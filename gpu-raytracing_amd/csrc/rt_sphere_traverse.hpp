@@ -3,7 +3,8 @@
 // tests a leaf's triangles.  The slab test, the ordered compares and the nearest-child choice of box_step, Trav's stack and
 // second_slot are rt_traverse.hpp's code, called from here.  What this file adds is the leaf phase -- the leaf's first 16
 // bytes for the sphere index (its primitive_id_0, as the TLAS leaf read of rt_instance_traverse.hpp), spheres[id] as one
-// 16-byte load, the test below -- and the loop that drives the two (trace_ray's non-QW vote / park loop; no PF arm).
+// 16-byte load, the test below -- and SphereWalk, the policy that hands box_step and that leaf phase to trace_plain
+// (rt_plain_traverse.hpp: trace_ray's non-QW vote / park loop, written once; no PF arm).
 //
 // The test (rt_abi.h, sphere block, has it operation by operation): the discriminant comes from the perpendicular offset
 // p = f + s*d of the centre from the ray's line, not from b*b - a*c.  Every operation is rounded on its own
@@ -12,6 +13,7 @@
 #pragma once
 
 #include "rt_device.hpp"
+#include "rt_plain_traverse.hpp"
 #include "rt_traverse.hpp"
 
 // waves per SIMD the sphere kernel's register allocation must fit: ray_query_kernel<false, ..>'s (64 VGPRs; DESIGN section
@@ -79,56 +81,21 @@ __device__ __forceinline__ bool sphere_leaf_test(const SphereParams& p, Ray& r, 
     return intersect_sphere(sp, r, h, id);
 }
 
-// trace_ray<false, ANY> of rt_traverse.hpp (its plain vote / park loop) with the leaf phase above.  Returns whether a sphere
-// was accepted; steps[0] / steps[1] as trace_ray.
+// trace_plain's policy: trace_ray's box step, the leaf phase above
+struct SphereWalk {
+    SphereHit& h;
+    __device__ __forceinline__ void begin(const SphereParams&) {}
+    __device__ __forceinline__ void box(const SphereParams& p, const Ray& r, Trav& t) { box_step<false>(p, r, t); }
+    __device__ __forceinline__ bool leaf(const SphereParams& p, Ray& r, Trav& t) { return sphere_leaf_test(p, r, h, t); }
+};
+
+// Returns whether a sphere was accepted; steps[0] / steps[1] as trace_ray.
 template <bool ANY>
 __device__ __forceinline__ bool trace_ray_spheres(const SphereParams& p, Ray& r, SphereHit& h, Trav& t, bool active,
                                                   uint32_t* steps)
 {
-    t.sp = 0;
-    t.cur = (p.root & kIndexMask) | (p.count << 29);
-    t.near_e = kNoNear;
-    t.near_d = __builtin_inff();
-    t.phase = (active && p.count > 0) ? PH_STEP : PH_DONE;
-    t.box_tests = 0;
-    t.tri_tests = 0;
-    t.t1 = 0;
-    t.e1 = 0;
-    t.f1 = t.k1 = 0.0f;
-    t.leaf = 0;
-    bool any_hit = false;
-    uint32_t nbox = 0, nleaf = 0;
-
-    while (true) {
-        // ---------------------------------------------------- box phase: step while enough lanes want to
-        uint64_t stepping, parked;
-        while (true) {
-            stepping = __builtin_amdgcn_ballot_w64(t.phase == PH_STEP);
-            parked = __builtin_amdgcn_ballot_w64((t.phase - 1u) < 2u);
-            if (stepping == 0 || __popcll(stepping) * p.park_den < __popcll(parked) * p.park_num) break;
-            nbox += 2;   // two box steps per vote, as trace_ray
-            if (t.phase == PH_STEP) box_step<false>(p, r, t);
-            if (t.phase == PH_STEP) box_step<false>(p, r, t);
-        }
-        if ((stepping | parked) == 0) break;
-        // ---------------------------------------------------- leaf phase
-        nleaf++;
-        if ((t.phase - 1u) < 2u) {
-            const bool hit = sphere_leaf_test(p, r, h, t);
-            any_hit |= hit;
-            if (ANY && hit) {
-                t.phase = PH_DONE;
-            } else {
-                const bool was_first = t.phase == PH_LEAF0;
-                t.phase = PH_STEP;
-                if (was_first) t.second_slot(r.tmin, r.tmax);
-                if (t.phase == PH_STEP) t.advance();
-            }
-        }
-    }
-    steps[0] += nbox;
-    steps[1] += nleaf;
-    return any_hit;
+    SphereWalk w = {h};
+    return trace_plain<ANY>(p, r, t, active, steps, w);
 }
 
 }  // namespace

@@ -23,14 +23,6 @@ namespace rt {
 
 namespace {
 
-// launch position j -> ray index (0xFFFFFFFF: no ray -- num_rays is a uint32, so it is never in range)
-template <bool INDEXED>
-__device__ __forceinline__ uint64_t cast_ray_index(const CastParams& p, uint64_t j)
-{
-    if constexpr (INDEXED) return j < p.num_indices ? p.order[j] : 0xFFFFFFFFull;
-    else return j;
-}
-
 template <bool ANY, bool INDEXED>
 __global__ __launch_bounds__(kTraceWaves * 64, RT_SPHERE_CAST_WAVES)
 void sphere_cast_kernel(CastParams p)
@@ -43,7 +35,7 @@ void sphere_cast_kernel(CastParams p)
         __syncthreads();
     }
     const uint32_t vb = xcd_chunk_block(blockIdx.x, gridDim.x);
-    const uint64_t i = cast_ray_index<INDEXED>(p, ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane);
+    const uint64_t i = ray_index<INDEXED>(p, ((uint64_t)vb * kTraceWaves + (uint32_t)wave) * 64u + (uint32_t)lane);
     const bool in_range = i < p.num_rays;
 
     float4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, -1.f};
