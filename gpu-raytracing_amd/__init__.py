@@ -90,6 +90,7 @@ RT_SWEEP_NONE, RT_SWEEP_FACE, RT_SWEEP_EDGE, RT_SWEEP_CORNER, RT_SWEEP_OVERLAP =
 GEOMETRY = np.dtype([("data", "<u8"), ("count", "<u4"), ("kind", "<u4")])                                    # 16 B
 RT_GEOM_TRIANGLES = 0
 RT_GEOM_SPHERES = 1
+RT_GEOM_CAPSULES = 2      # entered by rt_intersect_rays_instanced_mixed_capsules only
 # instanced deferred shading (rt_shade_frame_instanced): what a hit in BLAS b is shaded from, parallel to the BLAS table
 SHADE_GEOMETRY = np.dtype([("triangles", "<u8"), ("attributes", "<u8"), ("num_triangles", "<u4"), ("material_base", "<i4"),
                            ("pad", "<u4", 2)])                                                                # 32 B
@@ -254,6 +255,7 @@ EXPORTS = ["rt_bu_memory_requirements", "rt_nodes_bytes", "rt_run_bottom_up_buil
            "rt_ray_first_hits_instanced_filtered",
            "rt_intersect_rays_instanced_indexed", "rt_intersect_rays_instanced_motion_indexed",
            "rt_intersect_rays_instanced_mixed_indexed", "rt_intersect_rays_motion_indexed",
+           "rt_intersect_rays_instanced_mixed_capsules",
            "rt_error_string", "rt_version_string"]
 
 _lib = None
@@ -404,6 +406,9 @@ def lib() -> ctypes.CDLL:
     L.rt_intersect_rays_instanced_mixed_indexed.restype = i32
     L.rt_intersect_rays_instanced_mixed_indexed.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp,
                                                             i32, vp, vp]
+    L.rt_intersect_rays_instanced_mixed_capsules.restype = i32
+    L.rt_intersect_rays_instanced_mixed_capsules.argtypes = [ctypes.POINTER(_Accel), vp, u32, vp, vp, u32, vp, u32, vp, u32, vp,
+                                                             vp, i32, vp, vp]
     L.rt_intersect_rays_motion_indexed.restype = i32
     L.rt_intersect_rays_motion_indexed.argtypes = [ctypes.POINTER(_MotionAccel), vp, vp, u32, vp, u32, vp, i32, vp, vp]
     L.rt_tri_overlaps_scratch_bytes.restype = ctypes.c_size_t
@@ -1007,13 +1012,24 @@ def SphereCast(triangles, nodes, root: int, count: int, rays, hits, radii=None, 
 
 def geometry_table(entries, device="cuda"):
     """The device geometry table of mixed instancing, parallel to accel_table's: one rt_geometry per BLAS.  An entry is None
-    for a triangle BLAS, or (spheres, num_spheres) for a sphere BLAS -- the device SPHERE buffer its tree was prepared from.
-    The caller keeps the sphere buffers alive."""
+    for a triangle BLAS, (spheres, num_spheres) for a sphere BLAS -- the device SPHERE buffer its tree was prepared from --, or
+    (buffer, n, kind) with kind RT_GEOM_SPHERES or RT_GEOM_CAPSULES: for capsules the device CAPSULE buffer (32-byte records)
+    the tree was prepared from, which only IntersectRaysInstancedMixedCapsules enters.  The caller keeps the buffers alive."""
     tab = np.zeros(len(entries), GEOMETRY)
     for k, e in enumerate(entries):
         if e is None:
             tab[k] = (0, 0, RT_GEOM_TRIANGLES)
             continue
+        if len(e) == 3:
+            buf, ns, kind = e
+            if kind not in (RT_GEOM_SPHERES, RT_GEOM_CAPSULES):
+                raise ValueError(f"entry {k}: kind must be RT_GEOM_SPHERES or RT_GEOM_CAPSULES")
+            if kind == RT_GEOM_CAPSULES:
+                if int(ns) and (not buf.is_contiguous() or _nbytes(buf) < 32 * int(ns)):
+                    raise ValueError(f"entry {k}: capsules must be a contiguous device buffer of {int(ns)} 32-byte records")
+                tab[k] = (_ptr(buf), int(ns), RT_GEOM_CAPSULES)
+                continue
+            e = (buf, ns)
         spheres, ns = e
         if int(ns) and (not spheres.is_contiguous() or _nbytes(spheres) < 16 * int(ns)):
             raise ValueError(f"entry {k}: spheres must be a contiguous device buffer of {int(ns)} 16-byte records")
@@ -1923,6 +1939,38 @@ def IntersectRaysInstancedMixedIndexed(tlas_triangles, tlas_nodes, root: int, co
                                                            kAnyHit if any_hit else kClosestHit, _ptr(counters),
                                                            _stream_ptr(stream)),
            "rt_intersect_rays_instanced_mixed_indexed")
+
+
+def IntersectRaysInstancedMixedCapsules(tlas_triangles, tlas_nodes, root: int, count: int, records, num_instances: int,
+                                        blas_table, geom_table, num_blas: int, rays, hits, instance_ids, order=None, *,
+                                        num_indices: Optional[int] = None, any_hit: bool = False, counters=None,
+                                        stream=None) -> None:
+    """rt_intersect_rays_instanced_mixed_capsules: IntersectRaysInstancedMixed over a table that may also hold capsule BLASes
+    (geometry_table's (capsules, n, RT_GEOM_CAPSULES) entries).  A hit in a capsule BLAS is IntersectRaysCapsules's record: t,
+    the capsule index, u = 1 for the far root, v = the axial parameter.  order=None is the direct form; with `order` the call
+    is IntersectRaysInstancedMixedIndexed's.  `geom_table` is required: the all-triangle shortcut stays with the two older
+    calls, whose kernels these are not.  Asynchronous on `stream`."""
+    if geom_table is None:
+        raise ValueError("geom_table is required (IntersectRaysInstancedMixed takes None for an all-triangle table)")
+    if order is not None:
+        n, k = _indexed_batch(rays, order, num_indices, hits, instance_ids)
+    else:
+        if not rays.is_contiguous() or not hits.is_contiguous() or not instance_ids.is_contiguous() or _nbytes(rays) % 32:
+            raise ValueError("rays must be a contiguous device buffer of 32-byte records, hits / instance_ids contiguous buffers")
+        n, k = _nbytes(rays) // 32, 0
+        if _nbytes(hits) < 16 * n or _nbytes(instance_ids) < 4 * n:
+            raise ValueError(f"hits must hold {n} 16-byte records and instance_ids {n} words")
+    if not geom_table.is_contiguous() or _nbytes(geom_table) < 16 * int(num_blas):
+        raise ValueError(f"geom_table must be a contiguous device buffer of {int(num_blas)} 16-byte records")
+    if n == 0 or (order is not None and k == 0):
+        return
+    a = _Accel(_ptr(tlas_triangles), _ptr(tlas_nodes), root, count)
+    _check(lib().rt_intersect_rays_instanced_mixed_capsules(ctypes.byref(a), _ptr(records), int(num_instances), _ptr(blas_table),
+                                                            _ptr(geom_table), int(num_blas), _ptr(rays), n, _ptr(order), k,
+                                                            _ptr(hits), _ptr(instance_ids),
+                                                            kAnyHit if any_hit else kClosestHit, _ptr(counters),
+                                                            _stream_ptr(stream)),
+           "rt_intersect_rays_instanced_mixed_capsules")
 
 
 def IntersectRaysMotionIndexed(pose0, pose1, root: int, count: int, rays, times, order, hits, *,

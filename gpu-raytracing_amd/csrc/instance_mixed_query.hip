@@ -11,6 +11,8 @@
 //     BLAS; the kind is re-read from the hit instance's table entry, as instance_query_kernel re-reads the rotation;
 //   * lanes past num_rays and rays rt_intersect_rays would not trace trace nothing (a miss, RT_MISS, no tests counted) but
 //     still take part in the ballots.
+// mixed_instance_query_kernel<ANY, INDEXED, true> is rt_intersect_rays_instanced_mixed_capsules's: capsule BLASes as a third
+// kind, launched by that entry point alone.
 // No pair-prefetch arm, no hold at pop.
 // Compiled with -ffp-contract=off: every float operation is the documented one.
 #include "rt_device.hpp"
@@ -38,8 +40,10 @@ struct IndexedMixedInstParams : MixedInstParams {
 // past num_indices and indices >= num_rays: no ray, nothing written).  rays, hits, instance_ids and the reload of the world
 // ray (trace_instanced_mixed's ri) are indexed by i.  The choice stands HERE, under `if constexpr`, not in a helper function
 // (DESIGN sections 20 and 32).
-template <bool ANY, bool INDEXED>
-__global__ __launch_bounds__(kTraceWaves * 64, RT_INSTANCE_MIXED_WAVES)
+// CAPS (rt_intersect_rays_instanced_mixed_capsules): trace_instanced_mixed's capsule arm, a register bound
+// of its own and the capsule record at the write-out; the four <ANY, INDEXED, false> kernels are the ones from before the arm.
+template <bool ANY, bool INDEXED, bool CAPS = false>
+__global__ __launch_bounds__(kTraceWaves * 64, CAPS ? RT_INSTANCE_MIXED_CAPSULE_WAVES : RT_INSTANCE_MIXED_WAVES)
 void mixed_instance_query_kernel(std::conditional_t<INDEXED, IndexedMixedInstParams, MixedInstParams> p)
 {
     __shared__ uint32_t stack_lds[kTraceWaves][kStackLds][64];
@@ -74,7 +78,7 @@ void mixed_instance_query_kernel(std::conditional_t<INDEXED, IndexedMixedInstPar
     uint32_t steps[2] = {0u, 0u};
     Hit h = {0u, 0u, 0.f, 0.f};
     uint32_t hit_inst = RT_MISS;
-    const bool hit = trace_instanced_mixed<ANY>(p, i, r, h, hit_inst, t, active, steps);
+    const bool hit = trace_instanced_mixed<ANY, CAPS>(p, i, r, h, hit_inst, t, active, steps);
 
     if (in_range) {
         float4 o = {__builtin_inff(), __uint_as_float(RT_MISS), 0.f, 0.f};
@@ -82,9 +86,15 @@ void mixed_instance_query_kernel(std::conditional_t<INDEXED, IndexedMixedInstPar
             // the hit instance's BLAS and its kind: a sphere record as sphere_query_kernel writes it, or (u, v) back to the
             // caller's corners through the BLAS's leaves as instance_query_kernel does
             const uint32_t b = reinterpret_cast<const uint4*>(p.records + hit_inst)[3].x;
-            if (reinterpret_cast<const uint4*>(p.geom_table + b)[0].w == RT_GEOM_SPHERES) {
+            const uint32_t kind = reinterpret_cast<const uint4*>(p.geom_table + b)[0].w;
+            bool tri_rec = kind != RT_GEOM_SPHERES;
+            if constexpr (CAPS) {   // a capsule record as capsule_query_kernel writes it
+                tri_rec = kind == RT_GEOM_TRIANGLES;
+                if (kind == RT_GEOM_CAPSULES) o = float4{r.tmax, __uint_as_float(h.primitive_id), h.bu, h.bv};
+            }
+            if (kind == RT_GEOM_SPHERES) {
                 o = float4{r.tmax, __uint_as_float(h.primitive_id), h.bu, 0.f};
-            } else {
+            } else if (tri_rec) {
                 const rt_triangle_pair* lv = reinterpret_cast<const rt_triangle_pair*>(
                     *reinterpret_cast<const uint64_t*>(p.blas_table + b));
                 const uint32_t rot = lv[h.tri_id >> 1].rotations[h.tri_id & 1];
@@ -112,7 +122,7 @@ void mixed_instance_query_kernel(std::conditional_t<INDEXED, IndexedMixedInstPar
 
 }  // namespace
 
-hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, hipStream_t st)
+hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, bool capsules, hipStream_t st)
 {
     IndexedMixedInstParams p;
     p.tlas_nodes = q.tlas.nodes;
@@ -132,7 +142,15 @@ hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry
     p.order = q.order;
     p.num_indices = q.num_indices;
     const dim3 grid(query_blocks(q.order ? q.num_indices : q.num_rays)), block(kQueryBlock);
-    if (q.order) {
+    if (capsules) {   // the CAPS kernels: rt_intersect_rays_instanced_mixed_capsules alone
+        if (q.order) {
+            if (q.any_hit) mixed_instance_query_kernel<true, true, true><<<grid, block, 0, st>>>(p);
+            else mixed_instance_query_kernel<false, true, true><<<grid, block, 0, st>>>(p);
+        } else {
+            if (q.any_hit) mixed_instance_query_kernel<true, false, true><<<grid, block, 0, st>>>(p);
+            else mixed_instance_query_kernel<false, false, true><<<grid, block, 0, st>>>(p);
+        }
+    } else if (q.order) {
         if (q.any_hit) mixed_instance_query_kernel<true, true><<<grid, block, 0, st>>>(p);
         else mixed_instance_query_kernel<false, true><<<grid, block, 0, st>>>(p);
     } else {

@@ -643,9 +643,11 @@ static_assert(sizeof(rt_geometry) == 16, "rt_abi.h: rt_geometry is one 16-byte r
 static int instanced_mixed_query(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                  const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
                                  const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays, bool indexed,
-                                 const uint32_t* order, uint32_t num_indices, int mode, uint64_t* counters, void* stream)
+                                 const uint32_t* order, uint32_t num_indices, int mode, uint64_t* counters, void* stream,
+                                 bool capsules = false)
 {
-    // no table: every BLAS holds triangles (the sibling, without the pair-prefetch arm)
+    // no table: every BLAS holds triangles (the sibling, without the pair-prefetch arm); the capsule call has no such shortcut
+    if (!geom_table && capsules) return RT_ERR_INVALID_ARGUMENT;
     if (!geom_table)
         return instanced_query(tlas, records, num_instances, blas_table, num_blas, rays, hits, instance_ids, num_rays, indexed,
                                order, num_indices, mode, 0u, nullptr, counters, stream);
@@ -671,7 +673,7 @@ static int instanced_mixed_query(const rt_accel* tlas, const rt_instance_record*
     q.counters = counters;
     q.order = indexed ? order : nullptr;
     q.num_indices = num_indices;
-    return hip_rc(launch_instance_mixed_query(q, geom_table, static_cast<hipStream_t>(stream)));
+    return hip_rc(launch_instance_mixed_query(q, geom_table, capsules, static_cast<hipStream_t>(stream)));
 }
 
 int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
@@ -690,6 +692,16 @@ int rt_intersect_rays_instanced_mixed_indexed(const rt_accel* tlas, const rt_ins
 {
     return instanced_mixed_query(tlas, records, num_instances, blas_table, geom_table, num_blas, rays, hits, instance_ids,
                                  num_rays, true, order, num_indices, mode, counters, stream);
+}
+
+int rt_intersect_rays_instanced_mixed_capsules(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                               const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                               const rt_ray* rays, uint32_t num_rays, const uint32_t* order, uint32_t num_indices,
+                                               rt_hit* hits, uint32_t* instance_ids, int mode, uint64_t* counters, void* stream)
+{
+    // a null order is the direct form, as in rt_intersect_rays_capsules
+    return instanced_mixed_query(tlas, records, num_instances, blas_table, geom_table, num_blas, rays, hits, instance_ids,
+                                 num_rays, order != nullptr, order, num_indices, mode, counters, stream, true);
 }
 
 int rt_closest_points(const rt_accel* as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,
@@ -1120,6 +1132,9 @@ const char* rt_version_string(void)
            "instance_mixed: the instanced ray query over triangle and sphere BLASes in one TLAS, a 16-byte geometry record per "
            "BLAS read on entry (kind, sphere array, count kept per lane), the leaf phase tests a triangle pair or a sphere by "
            "the lane's kind on the object-space ray, one tmax across both, the record shape by the hit instance's kind | "
+           "instance_mixed_capsules: the mixed instanced query with capsule BLASes as a third kind, a CAPS template arm of "
+           "the mixed kernels (the capsule query's leaf test on the object-space ray, the capsule record), kernels and a "
+           "register bound of its own, direct or indexed | "
            "points: closest-point queries, one lane per query, distance-ordered traversal with re-culled pops (64-entry stack, "
            "16 entries + distances in LDS), exact d2 = Ericson + vertex-box clamp, lexicographic (dist2, id) | "
            "range: sphere / box range queries, one lane per query, unordered traversal on a 64-entry stack of 4-byte entries "

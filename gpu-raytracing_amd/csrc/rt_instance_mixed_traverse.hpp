@@ -16,10 +16,15 @@
 //     sphere_leaf_test's steps (rt_sphere_traverse.hpp) on its object-space ray, by its kind.
 // A sphere hit is kept in the lane's Hit as (primitive_id = sphere index, bu = far-root flag); the kernel's write-out picks
 // the record shape by the kind of the hit instance's BLAS.  No pair-prefetch arm, no hold at pop.
+// The CAPS arm (rt_intersect_rays_instanced_mixed_capsules) adds capsule BLASes as a third kind: the entry
+// rule admits RT_GEOM_CAPSULES with a capsule array, and a lane of that kind runs CapsuleWalk::leaf's steps
+// (rt_capsule_traverse.hpp: two independent 16-byte loads, intersect_capsule) on its object-space ray, through the same data
+// pointer and count.  A capsule hit is kept as (primitive_id = capsule index, bu = far-root flag, bv = axial parameter).
 // Device code only; every function is force-inlined into its kernel.
 #pragma once
 
 #include "rt_device.hpp"
+#include "rt_capsule_traverse.hpp"
 #include "rt_instance_traverse.hpp"
 #include "rt_sphere_traverse.hpp"
 #include "rt_traverse.hpp"
@@ -28,6 +33,13 @@
 // compiler's figures)
 #ifndef RT_INSTANCE_MIXED_WAVES
 #define RT_INSTANCE_MIXED_WAVES RT_INSTANCE_QUERY_WAVES
+#endif
+
+// ... and the CAPS kernels': one above the highest bound without spills.  At 4 waves (116 to 118 VGPRs) nothing spills, at 5
+// (96) 37 to 39 registers do, at 6 (80) 81 to 84; tools/instance_capsule_bench.py put 5 ahead of 3, 4 and 6 in every
+// comparison (DESIGN section 33 has the compiler's figures per candidate and the rates)
+#ifndef RT_INSTANCE_MIXED_CAPSULE_WAVES
+#define RT_INSTANCE_MIXED_CAPSULE_WAVES 5
 #endif
 
 namespace rt {
@@ -49,8 +61,12 @@ __device__ __forceinline__ void load_geometry(const rt_geometry* table, uint32_t
 }
 
 // The two-level traversal of ray `ri` (r: its world ray, loaded by the caller).  Returns whether a primitive was accepted;
-// *hit_inst = the instance of h.  h of a sphere hit: primitive_id = the sphere index, bu = the far-root flag.
-template <bool ANY>
+// *hit_inst = the instance of h.  h of a sphere hit: primitive_id = the sphere index, bu = the far-root flag; of a capsule hit
+// (CAPS): primitive_id = the capsule index, bu = the far-root flag, bv = the axial parameter.
+// CAPS (rt_intersect_rays_instanced_mixed_capsules) admits RT_GEOM_CAPSULES at the entry rule and gives the
+// leaf phase its third arm; each of the two places asks `if constexpr (CAPS)` where it stands, so the <ANY, false> code is the
+// code from before the arm, instruction for instruction.
+template <bool ANY, bool CAPS = false>
 __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, uint64_t ri, Ray& r, Hit& h, uint32_t& hit_inst,
                                                       Trav& t, bool active, uint32_t* steps)
 {
@@ -58,8 +74,8 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
     const rt_triangle_pair* leaves = p.tlas_leaves;
     uint32_t inst = kTop;
     uint32_t kind = RT_GEOM_TRIANGLES;    // of the BLAS the lane is in
-    const float4* spheres = nullptr;      // ... its sphere array (RT_GEOM_SPHERES)
-    uint32_t num_spheres = 0;             // ... and count
+    const float4* data = nullptr;         // ... its sphere or capsule array (every kind but RT_GEOM_TRIANGLES)
+    uint32_t count = 0;                   // ... and count
     int base = 0;
     t.sp = 0;
     t.cur = (p.root & kIndexMask) | (p.count << 29);
@@ -94,10 +110,26 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
                 const uint32_t li = t.leaf & kIndexMask;
                 const uint4* tp = reinterpret_cast<const uint4*>(leaves + li);
                 bool hit_prim = false;
+                bool tri_lane = kind != RT_GEOM_SPHERES;
+                if constexpr (CAPS) {            // CapsuleWalk::leaf's steps on the object-space ray
+                    tri_lane = kind == RT_GEOM_TRIANGLES;
+                    if (kind == RT_GEOM_CAPSULES) {
+                        const uint32_t id = tp[0].w;
+                        if (id < count) {
+                            const float4 c0 = data[2 * (uint64_t)id], c1 = data[2 * (uint64_t)id + 1];
+                            if (c0.w >= 0.0f && c0.w != __builtin_inff()) {
+                                t.tri_tests++;
+                                CapsuleHit ch;
+                                hit_prim = intersect_capsule(c0, c1, r, ch, id);
+                                if (hit_prim) { h.primitive_id = ch.id; h.tri_id = 0u; h.bu = ch.far_root; h.bv = ch.v; }
+                            }
+                        }
+                    }
+                }
                 if (kind == RT_GEOM_SPHERES) {   // sphere_leaf_test's steps on the object-space ray
                     const uint32_t id = tp[0].w;
-                    if (id < num_spheres) {
-                        const float4 sp = spheres[id];
+                    if (id < count) {
+                        const float4 sp = data[id];
                         if (sp.w >= 0.0f && sp.w != __builtin_inff()) {
                             t.tri_tests++;
                             SphereHit sh;
@@ -105,7 +137,7 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
                             if (hit_prim) { h.primitive_id = sh.id; h.tri_id = 0u; h.bu = sh.far_root; h.bv = 0.0f; }
                         }
                     }
-                } else {                         // trace_instanced's triangle arm
+                } else if (tri_lane) {           // trace_instanced's triangle arm
                     t.tri_tests++;
                     const uint4 l0 = tp[0], l1 = tp[1], l2 = tp[2], l3 = tp[3];
                     hit_prim = intersect_tri(__uint_as_float(l0.x), __uint_as_float(l0.y), __uint_as_float(l0.z),
@@ -153,6 +185,7 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
                         load_geometry(p.geom_table, tail.x, gdata, gcount, gkind);
                         ok = ((ncount - 1u) < 7u) &
                              ((gkind == RT_GEOM_TRIANGLES) | ((gkind == RT_GEOM_SPHERES) & (gdata != 0ull)));
+                        if constexpr (CAPS) ok |= ((ncount - 1u) < 7u) & (gkind == RT_GEOM_CAPSULES) & (gdata != 0ull);
                     }
                 }
                 if (ok) {
@@ -160,8 +193,8 @@ __device__ __forceinline__ bool trace_instanced_mixed(const MixedInstParams& p, 
                     ln.nodes = reinterpret_cast<const rt_node*>(nnodes);
                     leaves = reinterpret_cast<const rt_triangle_pair*>(ntris);
                     kind = gkind;
-                    spheres = reinterpret_cast<const float4*>(gdata);
-                    num_spheres = gcount;
+                    data = reinterpret_cast<const float4*>(gdata);
+                    count = gcount;
                     inst = id;
                     base = t.sp;
                     t.cur = (nroot & kIndexMask) | (ncount << 29);

@@ -348,8 +348,9 @@ struct InstanceQuery {
 };
 hipError_t launch_instance_query(const InstanceQuery& q, const rt_instance_hit_filter* filter, hipStream_t st);
 // instance_mixed_query.hip: rt_intersect_rays_instanced_mixed[_indexed] after its argument checks (num_rays > 0, geom_table non-null;
-// q.num_primitives is not read: no pair-prefetch arm)
-hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, hipStream_t st);
+// q.num_primitives is not read: no pair-prefetch arm).  capsules: rt_intersect_rays_instanced_mixed_capsules's kernels, which
+// also enter RT_GEOM_CAPSULES entries
+hipError_t launch_instance_mixed_query(const InstanceQuery& q, const rt_geometry* geom_table, bool capsules, hipStream_t st);
 
 // point_query.hip: rt_closest_points after its argument checks (num_queries > 0)
 hipError_t launch_point_query(const rt_accel& as, const rt_point_query* queries, rt_point_hit* hits, uint32_t num_queries,

@@ -641,9 +641,10 @@ int rt_intersect_rays_spheres(const rt_accel* as, const rt_sphere* spheres, uint
  * not 4-byte aligned; as->count > 7 (or a null tree pointer with count > 0); a bad mode.  Zero counts run nothing, except that
  * prepare still clears *status.
  *
- * Out of scope: per-vertex radii (cone-spheres); a capsule kind in rt_geometry / the mixed instanced query; motion, filters,
- * all-hit and first-K forms; point queries against capsules; capsules and other kinds in one tree; the C++ host mirror and
- * rt_cli. */
+ * Capsules as a BLAS kind under a TLAS, beside triangle and sphere BLASes (rt_geometry's RT_GEOM_CAPSULES):
+ * rt_intersect_rays_instanced_mixed_capsules below.
+ * Out of scope: per-vertex radii (cone-spheres); motion, filters, all-hit and first-K forms; point queries against capsules;
+ * capsules and other kinds in one tree; the C++ host mirror and rt_cli. */
 typedef struct rt_capsule { rt_float3 p0; float radius; rt_float3 p1; uint32_t pad; } rt_capsule;   /* 32 bytes; pad not read */
 enum { RT_CAPSULE_BAD = 1 };
 int rt_prepare_capsules(const rt_capsule* capsules, uint32_t num_capsules, rt_triangle* proxies, uint32_t* status, void* stream);
@@ -751,8 +752,9 @@ int rt_sphere_cast(const rt_accel* as, const rt_ray* rays, const float* radii, f
  * ray reloaded from rays[i] on leaving an instance, the cases in which an instance is never entered, asynchronous execution and
  * hipGraph capture.  There is NO num_primitives hint and no pair-prefetch arm, as in the sphere and instance-motion queries.
  *   Entering an instance: its record, then blas_table[blas] (three 8-byte loads), then geom_table[blas] as ONE 16-byte load.
- *   Besides rt_intersect_rays_instanced's cases an instance is NOT ENTERED when kind is neither RT_GEOM_* value, or kind ==
- *   RT_GEOM_SPHERES and data is null.  count == 0 enters the instance and tests nothing.
+ *   Besides rt_intersect_rays_instanced's cases an instance is NOT ENTERED when kind is neither RT_GEOM_TRIANGLES nor
+ *   RT_GEOM_SPHERES (an RT_GEOM_CAPSULES entry included: the capsule block of mixed instancing below has the call that enters
+ *   it), or kind == RT_GEOM_SPHERES and data is null.  count == 0 enters the instance and tests nothing.
  *   Triangle BLAS: the walk, the leaf test and the record are rt_intersect_rays_instanced's: t, primitive_id, (u, v) for the
  *   caller's corners through the leaf's rotations.
  *   Sphere BLAS: the box phase is the same, on the object-space ray.  At a leaf, with the object-space ray, the sphere
@@ -781,12 +783,61 @@ enum { RT_GEOM_TRIANGLES = 0, RT_GEOM_SPHERES = 1 };
 typedef struct rt_geometry {      /* 16 bytes; DEVICE array parallel to the BLAS table */
     const void* data;             /* RT_GEOM_SPHERES: const rt_sphere*, 16-byte aligned (caller's duty); TRIANGLES: not read */
     uint32_t    count;            /* RT_GEOM_SPHERES: num_spheres; TRIANGLES: not read */
-    uint32_t    kind;             /* RT_GEOM_* */
+    uint32_t    kind;             /* RT_GEOM_* (RT_GEOM_CAPSULES: the capsule block of mixed instancing, below) */
 } rt_geometry;
 int rt_intersect_rays_instanced_mixed(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
                                       const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
                                       const rt_ray* rays, rt_hit* hits, uint32_t* instance_ids, uint32_t num_rays,
                                       int mode, uint64_t* counters, void* stream);
+
+/* ---- mixed instancing with capsules (no reference counterpart).  Capsule BLASes as a third kind of the mixed instanced query:
+ * bonds between atoms, fibres on a mesh, cables, the link capsules of a robot cell are capsule sets PLACED by a transform next to
+ * meshes and sphere sets -- one TLAS, one walk, one tmax across the three kinds, an any-hit ray that stops at the first primitive
+ * of any of them.  Nothing new is prepared or built: rt_prepare_instances reads only a BLAS's root run, so a capsule tree
+ * (capsule block) is a valid BLAS as it is.
+ *
+ * RT_GEOM_CAPSULES (a third value of rt_geometry's kind): a tree built by any builder over rt_prepare_capsules's proxies with
+ * enable_pairs = enable_splits = 0; data = the const rt_capsule* array the proxies were prepared from (16-byte aligned: the
+ * caller's duty), count = num_capsules.
+ *
+ * rt_intersect_rays_instanced_mixed_capsules: order == NULL is the direct form (num_indices is not read) and everything
+ * rt_intersect_rays_instanced_mixed says holds word for word; with order != NULL everything
+ * rt_intersect_rays_instanced_mixed_indexed says holds (launch position j takes ray order[j]; positions past num_indices and
+ * entries >= num_rays do nothing; hits and instance_ids are written at the ray's index, unlisted records untouched).
+ *   Entering an instance: an instance is NOT ENTERED when kind is none of the three RT_GEOM_* values, or kind is
+ *   RT_GEOM_SPHERES or RT_GEOM_CAPSULES and data is null.  count == 0 enters the instance and tests nothing.
+ *   Triangle and sphere BLASes: as in rt_intersect_rays_instanced_mixed, bit for bit -- a table without capsule entries gives
+ *   that call's hits, instance ids, box tests and primitive tests.
+ *   Capsule BLAS: the box phase is the same, on the object-space ray.  At a leaf, with the object-space ray, the capsule
+ *   block's steps in its order: id = the leaf's primitive_id_0 (its first 16 bytes); the leaf is skipped when id >= count;
+ *   data[id] as two independent 16-byte loads; the capsule is skipped when !(r >= 0) || r == +inf; one test is counted; the
+ *   capsule block's test, operation by operation.  The test never assumes a unit direction (a = d'.d' stands in every root)
+ *   and an affine map preserves t, so t is the world-space distance in units of |dir|; under a non-uniform or sheared
+ *   object_to_world the world shape is the affine image of the capsule (an elliptic cylinder with ellipsoidal caps), not a
+ *   capsule.  The record is rt_intersect_rays_capsules's: t, primitive_id = the capsule index, u = 1.0f when t_far was taken
+ *   else 0.0f, v = the axial parameter (of the object-space capsule).  A capsule with p0 == p1 gives the sphere arm's record
+ *   for the sphere (p0, r), byte for byte.  The caller tells the three record shapes apart by instance_ids[i] ->
+ *   records[].blas -> geom_table[].kind.
+ *   One tmax runs across all instances of the three kinds; an equal t is accepted, so ties go to the primitive tested later.
+ *   mode RT_RAY_ANY_HIT ends the ray at the first accepted primitive of any kind.
+ *   Counters (optional, added to): [0] box tests of both levels together, [1] triangle-leaf tests plus sphere tests plus
+ *   capsule tests, each counted as its own query counts them, [2] / [3] wave steps.
+ *   Identity instance over a capsule tree: the same hit records and capsule tests as rt_intersect_rays_capsules on that tree
+ *   for rays without -0 components.
+ * The kernels are this call's own (a register bound of their own): rt_intersect_rays_instanced_mixed[_indexed] run the kernels
+ * they ran before this call existed and still do not enter an RT_GEOM_CAPSULES entry.
+ * Argument errors, returned before any GPU work (RT_ERR_INVALID_ARGUMENT): geom_table == NULL (there is no all-triangle
+ * shortcut here) or not 16-byte aligned; order not 4-byte aligned; every other error of the two siblings.  Errors win over
+ * num_rays = 0 and over num_indices = 0 with an order list, which run nothing.
+ *
+ * Out of scope: filtered, motion, all-hit and first-K forms; a stack-depth pin for a capsule BLAS entered deep in a TLAS (it
+ * needs a mixed two-level walker in the test oracle); kinds mixed inside one BLAS; shading of capsule hits; the C++ host mirror
+ * and rt_cli. */
+enum { RT_GEOM_CAPSULES = 2 };    /* rt_geometry.kind: data = const rt_capsule*, 16-byte aligned; count = num_capsules */
+int rt_intersect_rays_instanced_mixed_capsules(const rt_accel* tlas, const rt_instance_record* records, uint32_t num_instances,
+                                               const rt_accel* blas_table, const rt_geometry* geom_table, uint32_t num_blas,
+                                               const rt_ray* rays, uint32_t num_rays, const uint32_t* order, uint32_t num_indices,
+                                               rt_hit* hits, uint32_t* instance_ids, int mode, uint64_t* counters, void* stream);
 
 /* ---- closest-point queries (no reference counterpart).  For each caller point: which triangle is nearest, where on it, and
  * how far away -- through any tree rt_intersect_rays takes (runs of 1..7 slots; an empty tree, count = 0, is accepted and

@@ -9,6 +9,14 @@
 # arm -- the line count and "identical" or "DIFFERS" -- and exits non-zero if anything differs or fails to compile.  A file
 # of this tree's SRCS that <rev> does not have is reported as new and is no failure: there is nothing to compare it with.
 #   JOBS=n tools/device_asm_diff.sh 30690cb > profiles/retired_arms_asm_diff.txt
+#
+# PER_KERNEL="a.hip ..." compares the named files kernel by kernel instead of as a whole, for a change that ADDS kernels to a
+# file and must leave the old ones alone: every kernel of <rev>'s file is looked up in this tree's and its text -- from its
+# label to its .Lfunc_end label, which takes in the .amdhsa_kernel block with its register counts -- is compared, one line per
+# kernel.  The kernel's own symbol and the per-function number of the local labels (.LBB<n>_, .Lfunc_end<n>: a kernel's
+# position in the file, also where trailing comments name a block as BB<n>_) are the only things made equal first.  RENAME='<sed expression>' turns a kernel symbol of <rev> into
+# this tree's where a template parameter was added.  A kernel <rev> does not have is reported as new and is no failure.
+#   PER_KERNEL=instance_mixed_query.hip RENAME='s/ELb\([01]\)EEEvNSt/ELb\1ELb0EEEvNSt/' tools/device_asm_diff.sh HEAD
 set -uo pipefail
 rev=${1:?usage: device_asm_diff.sh <rev>}
 here=$(git -C "$(dirname "$0")" rev-parse --show-toplevel) || exit 2
@@ -41,12 +49,38 @@ emit() {
 emit "$here" "$tmp/head"
 emit "$tmp/other" "$tmp/rev"
 
+# kernel_text <file.s> <symbol>: the kernel from its label to its end label, its own name and label numbers made neutral
+kernel_text() {
+    awk -v s="$2:" 'index($0, s) == 1 { on = 1 } on { print } on && /^\.Lfunc_end[0-9]+:/ { exit }' "$1" |
+        sed -e "s/$2/KERNEL/g" -e 's/\([^A-Za-z0-9_]L\{0,1\}\)BB[0-9]*_/\1BB_/g' -e 's/\.Lfunc_end[0-9]*/.Lfunc_end/g'
+}
+# per_kernel <file> <head.s> <rev.s>: one line per kernel of either side
+per_kernel() {
+    local f=$1 a=$2 b=$3 k h n
+    for k in $(sed -n 's/^[[:space:]]*\.amdhsa_kernel[[:space:]]*//p' "$b"); do
+        h=$(printf '%s\n' "$k" | sed -e "${RENAME:-s/^//}")
+        n=$(kernel_text "$b" "$k" | wc -l)
+        if ! grep -q "^$h:" "$a"; then echo "$f kernel $k: MISSING in this tree (looked for $h)"; bad=1
+        elif [ "$n" -gt 2 ] && cmp -s <(kernel_text "$a" "$h") <(kernel_text "$b" "$k"); then
+            echo "$f kernel $k: $n lines, identical$([ "$h" != "$k" ] && echo " (here $h)")"
+        else echo "$f kernel $k: DIFFERS ($(diff <(kernel_text "$a" "$h") <(kernel_text "$b" "$k") | grep -c '^[<>]') lines of diff)"; bad=1
+        fi
+    done
+    for h in $(sed -n 's/^[[:space:]]*\.amdhsa_kernel[[:space:]]*//p' "$a"); do
+        for k in $(sed -n 's/^[[:space:]]*\.amdhsa_kernel[[:space:]]*//p' "$b"); do
+            [ "$(printf '%s\n' "$k" | sed -e "${RENAME:-s/^//}")" = "$h" ] && continue 2
+        done
+        echo "$f kernel $h: $(kernel_text "$a" "$h" | wc -l) lines, new in this tree"
+    done
+}
+
 echo "# tools/device_asm_diff.sh $rev: the device assembly of this tree against $rev's, per file and arm"
 bad=0
 for c in "${cases[@]}"; do
     IFS="|" read -r name def f <<< "$c"
     a=$tmp/head/$name.$f.s b=$tmp/rev/$name.$f.s
-    if [ -s "$a" ] && [ ! -e "$tmp/other/$csrc/$f" ]; then echo "$f $name: $(wc -l < "$a") lines, new in this tree ($rev has no such file)"
+    if [ -s "$a" ] && [ -s "$b" ] && [[ " ${PER_KERNEL:-} " == *" $f "* ]]; then per_kernel "$f $name" "$a" "$b"
+    elif [ -s "$a" ] && [ ! -e "$tmp/other/$csrc/$f" ]; then echo "$f $name: $(wc -l < "$a") lines, new in this tree ($rev has no such file)"
     elif [ ! -s "$a" ] || [ ! -s "$b" ]; then echo "$f $name: FAILED TO COMPILE"; cat "$tmp/head/$name.$f.err" "$tmp/rev/$name.$f.err" >&2; bad=1
     elif cmp -s "$a" "$b"; then echo "$f $name: $(wc -l < "$a") lines, identical"
     else echo "$f $name: $(wc -l < "$a") / $(wc -l < "$b") lines, DIFFERS ($(diff "$a" "$b" | grep -c '^[<>]') lines of diff)"; bad=1
